@@ -37,6 +37,30 @@ sys.path.insert(0, ROOT)
 PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: dense f32-input MFMA = f32 vector peak
 PEAK_F32_VALU_TFLOPS = 157.3
 PEAK_F16_MFMA_TFLOPS = 2500.0    # dense f16/bf16 MFMA (spec; the 5 PF headline includes 2:1 sparsity)
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: the whole set of arrays, bytes
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as out_dir/<name>.npy; float32 stays float32, everything else goes out as float64
+    (exact for the indices, counts and masks).  A set larger than `limit` is cut to a fixed, seeded sample of rows: every
+    array of n >= 1024 rows keeps the same sorted rows for the same n, and <name>_rows.npy records them."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    rowed = {k for k, v in arrays.items() if v.ndim >= 1 and v.shape[0] >= 1024}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        fixed = sum(v.nbytes for k, v in arrays.items() if k not in rowed)
+        per_row = sum(v.nbytes + 8 * v.shape[0] for k, v in arrays.items() if k in rowed)     # + the float64 row ids
+        frac = (limit - fixed) / per_row
+        for k in sorted(rowed):
+            n = arrays[k].shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+            arrays[k] = arrays[k][rows]
+            arrays[k + "_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return sorted(arrays)
 
 
 def _kernel_source_sha():
@@ -137,6 +161,11 @@ def bench_c5(args, world, rank, local_rank, dev, multi, saved_stdout):
         tt = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
+    last = None
+    if args.dump_outputs and rank == 0:         # the results of the last timed batch, one row per pair of this rank
+        last = {"pair_index": my_pairs, "pair_F": [list(r.F) for r in res], "pair_n_matches": [r.n_good for r in res],
+                "pair_n_inliers": [r.n_inliers for r in res], "pair_best_hyp": [pm.api.ransac_key_hyp(r.best_key) for r in res],
+                "pair_status": [r.status for r in res]}
 
     parity = "skipped"
     if not args.no_verify and rank == 0:
@@ -184,6 +213,8 @@ def bench_c5(args, world, rank, local_rank, dev, multi, saved_stdout):
                  "note": "per-GPU host->device rate sustained by the pipeline; the inputs are %.1f MB per pair" % (h2d / 1e6)},
         "parity": parity,
     }
+    if last:
+        write_outputs(args.dump_outputs, last)
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
@@ -258,6 +289,9 @@ def main():
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
                     help="skip the general-float leg and the forced f32-route leg (clean kernel traces of the headline path)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step (rank 0) as DIR/<name>.npy, float32 or "
+                         "float64, at most 64 MB in all; the inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This parent has not
@@ -439,6 +473,24 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def outputs_of(S):
+        """--dump-outputs: what a caller of the step receives from slot S, as host arrays (after a fence).  Matcher and
+        filter rows are this rank's; N > 1: xy1 / xy2 are the gathered correspondences that F and the mask refer to."""
+        n_loc = int(S.n.item())
+        n_all = int((S.ntot if multi else S.n).item())
+        o = {}
+        for pre, m in (("knn", S.knn.cpu().numpy().view(pm.MATCH_DTYPE).reshape(nq, K)),
+                       ("good", S.good[:n_loc].cpu().numpy().view(pm.MATCH_DTYPE).reshape(n_loc))):
+            for f, name in (("queryIdx", "query_idx"), ("trainIdx", "train_idx"), ("imgIdx", "img_idx"), ("distance", "distance")):
+                o["%s_%s" % (pre, name)] = m[f]
+        if multi:
+            o["xy1"], o["xy2"], _ = shard.concat_blocks(S.g_blk, nq)
+        else:
+            o["xy1"], o["xy2"] = S.xy1[:n_all].cpu().numpy(), S.xy2[:n_all].cpu().numpy()
+        o.update(F=S.F.cpu().numpy().reshape(3, 3), inlier_mask=S.mask[:n_all].cpu().numpy(), n_matches=n_all,
+                 n_inliers=int(S.ninl.item()), best_hyp=pm.api.ransac_key_hyp(int(S.key.item())))
+        return o
+
     def timed(fn, n):
         fence()
         t0 = time.perf_counter()
@@ -466,8 +518,13 @@ def main():
         pipelined = bool(tr[1].item() < tr[0].item())
         form_trial = {"steps": n_trial, "serial_ms_per_step": tr[0].item() / n_trial * 1e3,
                       "pipelined_ms_per_step": tr[1].item() / n_trial * 1e3}
+    # --dump-outputs: the last step of the form `ms_per_step` reports, read back after its timed region has ended
+    dump = bool(args.dump_outputs) and rank == 0
     wall_serial = timed(lambda i: step(), args.steps)
+    last = outputs_of(S0) if dump and not pipelined else None
     wall_pipe = timed(step_pipe, args.steps)
+    if dump and pipelined:
+        last = outputs_of(slots[(args.steps - 1) & 1])
     for i in range(args.steps):
         step(ev[i])
     fence()
@@ -921,6 +978,8 @@ def main():
                                     "best of 3, %d threads (the job's CPU share: cgroup quota if any, else the fastest of %s threads)"
                                     % (nq, nt, nth, cands)},
         }
+    if last:
+        write_outputs(args.dump_outputs, last)
     print(json.dumps(out))
     if multi:
         dist.destroy_process_group()
