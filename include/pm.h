@@ -69,7 +69,7 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
  * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
- * "lmeds_final", "fm_count", "flann_search". */
+ * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -360,6 +360,39 @@ static inline uint64_t pm_ransac_key(uint32_t inliers, uint32_t hyp) {
 }
 static inline uint32_t pm_ransac_key_hyp(uint64_t key)     { return 0xFFFFFFFFu - (uint32_t)key; }
 static inline uint32_t pm_ransac_key_inliers(uint64_t key) { return (uint32_t)(key >> 32); }
+
+/* ---- robust homography (cv::findHomography(pts1, pts2, RANSAC, thr): the planar-scene / pure-rotation sibling
+ * of the findFundamentalMat call at main.cpp:95-98) — docs/SPEC.md S19-S22.  pm_ransac_params as above, with
+ * error_kind = PM_ERR_REPROJ (the only kind accepted here; anything else -> PM_E_INVALID).  Every hypothesis h in
+ * [hyp_begin, hyp_end) (non-empty): sample 4 correspondences (S19, a stream of its own), Hartley-normalised 4-point
+ * DLT in fp64 (S20), score ALL n correspondences with the fp32 one-way reprojection test
+ * ||x2 - H x1||^2 <= thresh_px^2, division-free (S21), count inliers.  Winner: most inliers, ties -> lowest h (S22).
+ * A sample is invalid (key 0) when 3 of its 4 points are collinear in either image or the orientations of its
+ * triples disagree between the images (OpenCV's sample check: reflections stay valid).  No refinement on the inliers.
+ *   H        : 3x3 row-major, x2 ~ H x1, unit Frobenius norm, H[8] >= 0 (pm_f_scale_f33 gives OpenCV's H[8] = 1)
+ *   best_key : pm_ransac_key(inliers, h) of the winner, 0 = no valid model
+ * One launch per call (solve + score + winner + mask).  Graph capture: as the RANSAC-F entry points — no per-call
+ * epoch argument (the arrival ticket returns to zero in the launch), so the call is not refused on a capturing
+ * stream; the host forms synchronise and therefore cannot be captured. */
+enum { PM_ERR_REPROJ = 2 };
+/* Host in, host out (mirrors pm_ransac_fundamental).  mask (n bytes), n_inliers, best_key may be NULL.
+ * Statuses: PM_E_INVALID (null params or points, bad range, error_kind != PM_ERR_REPROJ, null ctx),
+ * n < 4 -> PM_E_TOO_FEW, all hypotheses invalid -> PM_E_NO_MODEL with H = 0, mask = 0 (*best_key = 0). */
+int pm_ransac_homography(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
+                         double H[9], uint8_t* mask, int* n_inliers, uint64_t* best_key);
+/* Whole run on the device over a correspondence view (a plain array is parts = 1, optionally with a device-side
+ * count): the count is read on the device, so it chains after pm_filter_ratio_gather_dev /
+ * pm_bf_knn_l2_*_ratio_dev with no host round trip.  Writes *d_best_key, d_H (9 doubles), d_mask[0..mask_len)
+ * (zero beyond n) and *d_n_inliers; n < 4 or no valid model leaves key 0, H = 0, mask = 0, count 0.  All four
+ * output pointers are required.  PM_E_INVALID for bad arguments, as above. */
+int pm_ransac_homography_run_dev(pm_ctx* ctx, const pm_points_view* view, const pm_ransac_params* p,
+                                 uint64_t* d_best_key, double* d_H, uint8_t* d_mask, int mask_len,
+                                 int32_t* d_n_inliers);
+/* H, mask and inlier count of ONE hypothesis id (0 <= hyp < 2^32; p's hypothesis range is ignored): the same
+ * launch over [hyp, hyp + 1).  An invalid sample -> PM_E_NO_MODEL with H = 0, mask = 0. */
+int pm_ransac_homography_from_hyp(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
+                                  const pm_ransac_params* p, int64_t hyp, double H[9], uint8_t* mask,
+                                  int* n_inliers);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

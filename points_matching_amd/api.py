@@ -22,6 +22,7 @@ PM_KNN_HINT_U8 = 8
 PM_KNN_HINT_UNIT_NORM = 16
 PM_ERR_SAMPSON = 0
 PM_ERR_SYM_EPIPOLAR = 1
+PM_ERR_REPROJ = 2          # robust homography (pm_ransac_homography*)
 PM_OK, PM_E_INVALID, PM_E_TOO_FEW, PM_E_NO_MODEL, PM_E_HIP, PM_E_NOMEM, PM_E_UNSUPPORTED = \
     0, -1, -2, -3, -4, -5, -6
 
@@ -47,6 +48,7 @@ EXPORTS = [
     "pm_bf_knn_l2_u8", "pm_bf_knn_l2_u8_dev", "pm_bf_knn_l2_u8_ratio_dev", "pm_host_register", "pm_host_unregister",
     "pm_lmeds_fundamental", "pm_lmeds_fundamental_dev", "pm_lmeds_default_iters", "pm_ransac7_adaptive",
     "pm_epipolar_residuals", "pm_f_scale_f33", "pm_epilines", "pm_epiline_endpoints",
+    "pm_ransac_homography", "pm_ransac_homography_run_dev", "pm_ransac_homography_from_hyp",
 ]
 
 
@@ -418,6 +420,46 @@ class Context:
         prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)
         _check(lib().pm_ransac_score_dev(self._h, C.c_void_p(dxy1_ptr), C.c_void_p(dxy2_ptr), n,
                                          C.byref(prm), C.c_void_p(dkey_ptr)))
+
+    # -- robust H (cv::findHomography(..., RANSAC, thr), sibling of main.cpp:95-98) -----------------
+    def ransac_homography(self, xy1, xy2, iters, thresh_px, seed, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """Hypotheses [hyp_begin, iters).  Returns (status, H(3x3), mask, n_inliers, best_key); raises on anything other
+        than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        H = np.zeros(9, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        rc = lib().pm_ransac_homography(self._h, _p(xy1), _p(xy2), n, C.byref(prm), _p(H), _p(mask),
+                                        C.byref(ninl), C.byref(key))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value
+
+    def ransac_homography_from_hyp(self, xy1, xy2, hyp, thresh_px, seed, kind=PM_ERR_REPROJ):
+        """H, mask and count of one hypothesis id: (status, H(3x3), mask, n_inliers)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(0, 0, seed, thresh_px, kind)
+        H = np.zeros(9, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl = C.c_int()
+        rc = lib().pm_ransac_homography_from_hyp(self._h, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp),
+                                                 _p(H), _p(mask), C.byref(ninl))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, H.reshape(3, 3), mask[:n], ninl.value
+
+    def ransac_homography_run_dev(self, view, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dH_ptr, dmask_ptr, mask_len,
+                                  dninl_ptr, kind=PM_ERR_REPROJ):
+        """Device-resident run over a PointsView (count read on the device); outputs are device pointers."""
+        prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)
+        _check(lib().pm_ransac_homography_run_dev(self._h, C.byref(view), C.byref(prm), C.c_void_p(dkey_ptr),
+                                                  C.c_void_p(dH_ptr), C.c_void_p(dmask_ptr), mask_len,
+                                                  C.c_void_p(dninl_ptr)))
 
 
 class LmedsParams(C.Structure):

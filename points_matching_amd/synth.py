@@ -191,3 +191,37 @@ def pair_workload(nq=8192, nt=8192, dim=128, seed=0xC3, rank=0, planted=0.28, ou
     return {"q": np.ascontiguousarray(q[perm]), "t": np.ascontiguousarray(t),
             "kp1": np.ascontiguousarray(kp1[perm].astype(np.float32)), "kp2": np.ascontiguousarray(kp2),
             "truth": truth[perm], "true_inlier": true_inlier[perm], "F_gt": F}
+
+
+def planar_view(n, seed=0xC5, outlier_frac=0.3, noise_px=0.5, width=993, height=660):
+    """Correspondences of a planar scene (or a pure camera rotation): image-2 points are image-1 points mapped by a known,
+    well-conditioned homography (rotation up to 6 degrees, scale 0.9-1.1, shift up to 40 px, mild perspective about
+    the image centre), plus N(0, noise_px) in both images; `outlier_frac` of the pairs get uniform-random image-2
+    positions.
+
+    Returns xy1, xy2 (n x 2 float32 pixels), H_gt (3x3 float64, x2 ~ H x1, unit Frobenius norm, H[2,2] > 0) and the
+    boolean ground-truth inlier flags.
+    """
+    rng = np.random.default_rng([seed, 0x4817])
+    a = rng.uniform(-0.1, 0.1)
+    sc = rng.uniform(0.9, 1.1)
+    A = np.array([[sc * np.cos(a), -sc * np.sin(a), rng.uniform(-40, 40)],
+                  [sc * np.sin(a), sc * np.cos(a), rng.uniform(-40, 40)],
+                  [rng.uniform(-1e-4, 1e-4), rng.uniform(-1e-4, 1e-4), 1.0]])
+    C = np.array([[1.0, 0, width / 2.0], [0, 1.0, height / 2.0], [0, 0, 1.0]])
+    H = C @ A @ np.linalg.inv(C)
+    H /= np.linalg.norm(H)
+    if H[2, 2] < 0:
+        H = -H
+    x1 = rng.uniform([0, 0], [width, height], (n, 2))
+    p = np.column_stack([x1, np.ones(n)]) @ H.T
+    x2 = p[:, :2] / p[:, 2:3]
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl
