@@ -69,7 +69,7 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
  * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
- * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused". */
+ * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -368,7 +368,8 @@ static inline uint32_t pm_ransac_key_inliers(uint64_t key) { return (uint32_t)(k
  * DLT in fp64 (S20), score ALL n correspondences with the fp32 one-way reprojection test
  * ||x2 - H x1||^2 <= thresh_px^2, division-free (S21), count inliers.  Winner: most inliers, ties -> lowest h (S22).
  * A sample is invalid (key 0) when 3 of its 4 points are collinear in either image or the orientations of its
- * triples disagree between the images (OpenCV's sample check: reflections stay valid).  No refinement on the inliers.
+ * triples disagree between the images (OpenCV's sample check: reflections stay valid).  The H here is the winning
+ * 4-point solve; pm_homography_refine* (below) refines it on its inliers, pm_ransac_homography_refined does both.
  *   H        : 3x3 row-major, x2 ~ H x1, unit Frobenius norm, H[8] >= 0 (pm_f_scale_f33 gives OpenCV's H[8] = 1)
  *   best_key : pm_ransac_key(inliers, h) of the winner, 0 = no valid model
  * One launch per call (solve + score + winner + mask).  Graph capture: as the RANSAC-F entry points — no per-call
@@ -393,6 +394,36 @@ int pm_ransac_homography_run_dev(pm_ctx* ctx, const pm_points_view* view, const 
 int pm_ransac_homography_from_hyp(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
                                   const pm_ransac_params* p, int64_t hyp, double H[9], uint8_t* mask,
                                   int* n_inliers);
+
+/* ---- refinement of the robust homography on its inliers (what cv::findHomography runs after its RANSAC loop) —
+ * docs/SPEC.md S23-S25.  Over the correspondences with mask[i] != 0: a Hartley-normalised least-squares DLT refit on
+ * all of them (S23, fp64, Jacobi eigen-solve), then Levenberg-Marquardt on the forward transfer error
+ * sum ||x2 - H x1||^2 with H[8] = 1 fixed (S24, up to max_iters iterations, one pass over the inliers each).  LM starts
+ * from the refit or from H_in, whichever has the lower cost (ties -> the refit), and accepts only cost decreases, so
+ * cost_out <= cost_in.  The mask is not recomputed.  Output H: x2 ~ H x1, unit Frobenius norm, H[8] >= 0 (S20).
+ * max_iters in [0, 100]; 0 = refit only; 10 is OpenCV's default.  status: 0 = refined, 1 = kept H_in (fewer than 4
+ * inliers, or no refit and no LM gain; H_out = H_in bit for bit), 2 = H_in is zero (no model; H_out = 0).
+ * One launch of one workgroup.  Graph capture: the launch keeps no per-call state, so the device form is not refused on
+ * a capturing stream; the host forms synchronise and therefore cannot be captured. */
+typedef struct pm_h_refine_info {
+    double  cost_in, cost_out;   /* sum of squared forward transfer errors over the inliers, px^2 */
+    int32_t n_used, iters, status, reserved;
+} pm_h_refine_info;
+/* Host in, host out.  mask: n bytes 0/1 (e.g. from pm_ransac_homography); H_out may alias H_in; info may be NULL.
+ * Statuses: PM_E_INVALID (null arrays, max_iters out of range, null ctx), n < 4 -> PM_E_TOO_FEW (H_out = H_in),
+ * H_in zero -> PM_E_NO_MODEL (status 2). */
+int pm_homography_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
+                         const double H_in[9], int max_iters, double H_out[9], pm_h_refine_info* info);
+/* Device form over a view (count read on the device, as pm_ransac_homography_run_dev): chains after it with no host
+ * round trip.  d_mask covers the view's correspondences in view order; d_H_out may equal d_H_in; d_info may be NULL.
+ * Data outcomes (zero H, fewer than 4 inliers) are reported in *d_info only. */
+int pm_homography_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask, const double* d_H_in,
+                             int max_iters, double* d_H_out, pm_h_refine_info* d_info);
+/* Convenience: pm_ransac_homography + refinement, one synchronisation; mask/n_inliers/best_key as the RANSAC call
+ * (the RANSAC mask), H refined, info may be NULL.  Statuses as pm_ransac_homography. */
+int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
+                                 int max_iters, double H[9], uint8_t* mask, int* n_inliers, uint64_t* best_key,
+                                 pm_h_refine_info* info);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

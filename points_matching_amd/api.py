@@ -49,6 +49,7 @@ EXPORTS = [
     "pm_lmeds_fundamental", "pm_lmeds_fundamental_dev", "pm_lmeds_default_iters", "pm_ransac7_adaptive",
     "pm_epipolar_residuals", "pm_f_scale_f33", "pm_epilines", "pm_epiline_endpoints",
     "pm_ransac_homography", "pm_ransac_homography_run_dev", "pm_ransac_homography_from_hyp",
+    "pm_homography_refine", "pm_homography_refine_dev", "pm_ransac_homography_refined",
 ]
 
 
@@ -68,6 +69,15 @@ class PointsView(C.Structure):
     _fields_ = [("xy1", C.c_void_p), ("xy2", C.c_void_p), ("counts", C.c_void_p), ("parts", C.c_int32),
                 ("cap", C.c_int32), ("pitch_xy", C.c_int64), ("pitch_cnt", C.c_int32), ("reserved", C.c_int32)]
 
+
+class HRefineInfo(C.Structure):
+    """pm_h_refine_info (include/pm.h): costs in px^2, inliers used, LM iterations, status 0/1/2."""
+    _fields_ = [("cost_in", C.c_double), ("cost_out", C.c_double), ("n_used", C.c_int32), ("iters", C.c_int32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+H_REFINE_INFO_DTYPE = np.dtype([("cost_in", "<f8"), ("cost_out", "<f8"), ("n_used", "<i4"), ("iters", "<i4"),
+                                ("status", "<i4"), ("reserved", "<i4")])   # the same record, 32 bytes
 
 RANSAC_RECORD_DTYPE = np.dtype([("key", "<u8"), ("F", "<f8", (9,))])       # pm_ransac_record, 80 bytes
 PM_MAX_PARTS = 64
@@ -460,6 +470,45 @@ class Context:
         _check(lib().pm_ransac_homography_run_dev(self._h, C.byref(view), C.byref(prm), C.c_void_p(dkey_ptr),
                                                   C.c_void_p(dH_ptr), C.c_void_p(dmask_ptr), mask_len,
                                                   C.c_void_p(dninl_ptr)))
+
+    # -- refinement of the robust H on its inliers (DLT refit + LM, SPEC S23-S25) ------------------------------------
+    def homography_refine(self, xy1, xy2, mask, H_in, max_iters=10):
+        """Returns (status, H(3x3), HRefineInfo); raises on anything other than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n or xy2.shape[0] != n:
+            raise ValueError("xy1, xy2 and mask must have the same length")
+        Hin = np.ascontiguousarray(H_in, np.float64).reshape(9)
+        H = np.zeros(9, np.float64)
+        info = HRefineInfo()
+        rc = lib().pm_homography_refine(self._h, _p(xy1), _p(xy2), n, _p(mask), _p(Hin), max_iters, _p(H),
+                                        C.byref(info))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, H.reshape(3, 3), info
+
+    def homography_refine_dev(self, view, dmask_ptr, dHin_ptr, max_iters, dHout_ptr, dinfo_ptr=None):
+        """Device form over a PointsView; dinfo_ptr (32 bytes, H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_homography_refine_dev(self._h, C.byref(view), C.c_void_p(dmask_ptr), C.c_void_p(dHin_ptr),
+                                              max_iters, C.c_void_p(dHout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def ransac_homography_refined(self, xy1, xy2, iters, thresh_px, seed, max_iters=10, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """RANSAC-H + refinement, one synchronisation: (status, H(3x3), mask, n_inliers, best_key, HRefineInfo)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        H = np.zeros(9, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = lib().pm_ransac_homography_refined(self._h, _p(xy1), _p(xy2), n, C.byref(prm), max_iters, _p(H), _p(mask),
+                                                C.byref(ninl), C.byref(key), C.byref(info))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value, info
 
 
 class LmedsParams(C.Structure):

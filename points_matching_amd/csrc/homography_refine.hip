@@ -1,0 +1,401 @@
+// homography_refine.hip — refinement of a robust homography on its inliers in ONE launch on gfx950 (MI355X): the
+// least-squares DLT refit over all inliers (docs/SPEC.md S23) and Levenberg-Marquardt on the forward transfer error
+// (S24), the two steps cv::findHomography runs after its RANSAC loop.  The mask is not recomputed (S25).
+//
+// One workgroup of HR_P = 512 threads (8 waves).  Thread p owns partial p of S23's fixed reduction order: it walks the
+// correspondences i = p, p + 512, ... of the view straight from global memory (32 768 points are 512 KB, more than
+// LDS), skips the ones the mask rejects and keeps its partial sums in fp64 registers (45 in the widest pass).  The
+// stride-halving tree runs its three cross-wave steps through LDS, HR_CH accumulators at a time, and its six in-wave
+// steps with cross-lane moves.  Between passes, every thread reads the sums back from LDS and takes the same control
+// decisions; the Jacobi eigen-solve runs lane-parallel in wave 0, the 8 x 8 Cholesky of each LM step in thread 0.
+// Passes: sums + cost of H_in, centroid distances, normal matrix, cost of the refit, then the LM passes (one at the
+// start point, one per iteration).
+//
+// The launch keeps no per-call state, so the device form may be captured; the host forms synchronise.
+#include "homography_refine_core.hpp"
+#include "ransac_fused_kernels.hpp"
+
+namespace pm_hrefine {
+namespace {
+
+using pm_ransac::view_count1;
+using pm_ransac::view_offsets;
+using pm_ransac::view_point;
+
+// S23 tree over the threads' partials: for s = 256, ..., 1: part[p] += part[p + s] for p < s.  out[k] (LDS) = the sum,
+// visible to every thread on return.
+template <int K>
+__device__ __forceinline__ void tree(double (&acc)[K], int tid, double (*s_x)[HR_P / 2], double* out)
+{
+#pragma unroll
+    for (int c0 = 0; c0 < K; c0 += HR_CH) {
+#pragma unroll
+        for (int s = HR_P / 2; s >= 64; s >>= 1) {
+            if (tid >= s && tid < 2 * s) {
+#pragma unroll
+                for (int c = 0; c < HR_CH; ++c)
+                    if (c0 + c < K) s_x[c][tid - s] = acc[c0 + c];
+            }
+            __syncthreads();
+            if (tid < s) {
+#pragma unroll
+                for (int c = 0; c < HR_CH; ++c)
+                    if (c0 + c < K) acc[c0 + c] = acc[c0 + c] + s_x[c][tid];
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < 64) {
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1)
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = acc[k] + __shfl_down(acc[k], s, 64);
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) out[k] = acc[k];
+        }
+    }
+    __syncthreads();
+}
+
+// One pass: term(acc, x1, y1, x2, y2) over the inliers i = tid, tid + HR_P, ... < n, then the tree into out[0..K).
+template <int K, typename Term>
+__device__ __forceinline__ void pass(const pm_points_view& v, const int* offs, int n, const uint8_t* mask, int tid,
+                                     double (*s_x)[HR_P / 2], double* out, Term term)
+{
+    double acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += HR_P) {
+        if (!mask[i]) continue;
+        float2 a, b;
+        if (v.parts == 1) {
+            a = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(i));
+            b = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(i));
+        } else {
+            view_point(v, offs, i, a, b);
+        }
+        term(acc, static_cast<double>(a.x), static_cast<double>(a.y), static_cast<double>(b.x), static_cast<double>(b.y));
+    }
+    tree<K>(acc, tid, s_x, out);
+}
+
+__global__ __launch_bounds__(HR_P) void homography_refine(pm_points_view v, const uint8_t* mask, const double* H_in,
+                                                          int max_iters, double* H_out, pm_h_refine_info* info)
+{
+    __shared__ double s_x[HR_CH][HR_P / 2];
+    __shared__ double s_red[HR_LM];
+    __shared__ double s_jtjg[44];            // J^T J and J^T r at the current LM point
+    __shared__ double s_hin[9];
+    __shared__ double s_hn[9];
+    __shared__ double s_start[9];         // S24 start point
+    __shared__ double s_h[9];             // current LM point (h[8] = 1)
+    __shared__ double s_d[8];             // LM step
+    __shared__ int s_jok;                 // Jacobi / Cholesky succeeded
+    __shared__ int s_offs[PM_MAX_PARTS + 1];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    int n;
+    if (v.parts == 1) {
+        n = view_count1(v);
+    } else {
+        view_offsets(v, s_offs, tid);
+        n = 0;
+    }
+    if (tid < 9) s_hin[tid] = H_in[tid];     // read before any write: H_out may alias H_in
+    __syncthreads();
+    if (v.parts > 1) n = s_offs[v.parts];
+    double hin[9];
+    bool zero = true;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { hin[i] = s_hin[i]; zero = zero && hin[i] == 0.0; }
+    if (zero) {                              // S25 status 2: no model
+        if (tid == 0) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) H_out[i] = hin[i];
+            if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 2, 0};
+        }
+        return;
+    }
+
+    // ---- S23 pass 1: inlier count, coordinate sums, cost of H_in
+    pass<6>(v, s_offs, n, mask, tid, s_x, s_red, [&](double (&a)[6], double x1, double y1, double x2, double y2) {
+        a[0] = a[0] + 1.0;
+        a[1] = a[1] + x1; a[2] = a[2] + y1; a[3] = a[3] + x2; a[4] = a[4] + y2;
+        a[5] = a[5] + cost_term(hin, x1, y1, x2, y2);
+    });
+    const double nu = s_red[0], cost_in = s_red[5];
+    const double cx1 = s_red[1] / nu, cy1 = s_red[2] / nu, cx2 = s_red[3] / nu, cy2 = s_red[4] / nu;
+
+    // ---- S23 refit: Hartley normalisation, normal matrix, Jacobi, denormalisation
+    double href[9];
+    bool ok_ref = false;
+    if (nu >= 4.0) {
+        pass<2>(v, s_offs, n, mask, tid, s_x, s_red, [&](double (&a)[2], double x1, double y1, double x2, double y2) {
+            const double dx1 = x1 - cx1, dy1 = y1 - cy1, dx2 = x2 - cx2, dy2 = y2 - cy2;
+            a[0] = a[0] + sqrt(fma(dx1, dx1, dy1 * dy1));
+            a[1] = a[1] + sqrt(fma(dx2, dx2, dy2 * dy2));
+        });
+        const double md1 = s_red[0] / nu, md2 = s_red[1] / nu;
+        if (md1 > 0.0 && md1 < __builtin_inf() && md2 > 0.0 && md2 < __builtin_inf()) {
+            const double s1 = 1.4142135623730951 / md1, s2 = 1.4142135623730951 / md2;
+            pass<HR_NORMAL>(v, s_offs, n, mask, tid, s_x, s_red,
+                            [&](double (&a)[HR_NORMAL], double x1, double y1, double x2, double y2) {
+                                normal_term(a, (x1 - cx1) * s1, (y1 - cy1) * s1, (x2 - cx2) * s2, (y2 - cy2) * s2);
+                            });
+            if (tid < 64) {                  // wave 0
+                double hk;
+                const bool ok = jacobi_min_wave(s_red, lane, hk);
+                if (lane < 9) s_hn[lane] = hk;
+                if (lane == 0) s_jok = ok ? 1 : 0;
+            }
+            __syncthreads();
+            if (s_jok) {
+                double hn[9];
+#pragma unroll
+                for (int i = 0; i < 9; ++i) hn[i] = s_hn[i];
+                ok_ref = denormalise(hn, s1, -(s1 * cx1), -(s1 * cy1), s2, -(s2 * cx2), -(s2 * cy2), href);
+            }
+        }
+    }
+
+    // ---- S24 start point: the refit if its cost is not higher than H_in's (kept in LDS: few registers stay free
+    // next to the 45 accumulators of the LM passes)
+    double cost_start = cost_in;
+    bool from_ref = false;
+    if (ok_ref) {
+        pass<1>(v, s_offs, n, mask, tid, s_x, s_red, [&](double (&a)[1], double x1, double y1, double x2, double y2) {
+            a[0] = a[0] + cost_term(href, x1, y1, x2, y2);
+        });
+        const double cr = s_red[0];
+        if (cr <= cost_in) { cost_start = cr; from_ref = true; }
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) s_start[i] = from_ref ? href[i] : s_hin[i];
+    }
+    __syncthreads();
+
+    // ---- S24 LM: one pass per iteration at the trial point; the current point h and its J^T J, J^T r stay in LDS
+    double cur = cost_start;
+    int iters = 0;
+    bool accepted = false;
+    if (nu >= 4.0 && max_iters > 0 && fabs(s_start[8]) >= HR_MIN_H8) {
+        {
+            double h[9];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) h[i] = s_start[i] / s_start[8];
+            h[8] = 1.0;
+            pass<HR_LM>(v, s_offs, n, mask, tid, s_x, s_red,
+                        [&](double (&a)[HR_LM], double x1, double y1, double x2, double y2) { lm_term(a, h, x1, y1, x2, y2); });
+            if (tid < 44) s_jtjg[tid] = s_red[tid];
+            if (tid == 0) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) s_h[i] = h[i];
+            }
+            __syncthreads();
+        }
+        double lam = HR_LAMBDA0;
+        for (int it = 0; it < max_iters; ++it) {
+            if (tid == 0) s_jok = lm_solve(s_jtjg, lam, s_d) ? 1 : 0;
+            __syncthreads();
+            if (!s_jok) break;
+            double dmax = 0.0, hmax = 1.0;
+            double ht[9];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {        // NaN propagates into dmax and stops the loop
+                const double hi = s_h[i], di = s_d[i];
+                if (!(fabs(di) <= dmax)) dmax = fabs(di);
+                if (!(fabs(hi) <= hmax)) hmax = fabs(hi);
+                ht[i] = hi + di;
+            }
+            ht[8] = 1.0;
+            if (!(dmax > HR_STEP_TOL * hmax)) break;
+            pass<HR_LM>(v, s_offs, n, mask, tid, s_x, s_red,
+                        [&](double (&a)[HR_LM], double x1, double y1, double x2, double y2) { lm_term(a, ht, x1, y1, x2, y2); });
+            ++iters;
+            const double ct = s_red[HR_LM - 1];
+            if (ct < cur) {
+                cur = ct;
+                lam = lam / 10.0;
+                accepted = true;
+                if (tid < 44) s_jtjg[tid] = s_red[tid];
+                if (tid == 0) {
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) s_h[i] = ht[i];
+                }
+                __syncthreads();
+            } else {
+                lam = lam * 10.0;
+            }
+        }
+    }
+
+    // ---- S25 result (thread 0)
+    if (tid == 0) {
+        double out[9], h[9];
+        double cost_out = cost_start;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { out[i] = s_start[i]; h[i] = s_h[i]; }
+        if (accepted) {
+            if (scale_sign(h, out)) cost_out = cur;
+            else accepted = false;           // out untouched: the start point
+        }
+#pragma unroll
+        for (int i = 0; i < 9; ++i) H_out[i] = out[i];
+        if (info)
+            *info = pm_h_refine_info{cost_in, cost_out, static_cast<int32_t>(nu), iters, (from_ref || accepted) ? 0 : 1, 0};
+    }
+}
+
+int check_iters(int max_iters)
+{
+    PM_REQUIRE(max_iters >= 0 && max_iters <= 100, PM_E_INVALID, "max_iters must lie in [0, 100]");
+    return PM_OK;
+}
+
+// Enqueue the launch (no synchronisation, no per-call state).
+int refine_launch(pm_ctx* ctx, const pm_points_view& v, const uint8_t* d_mask, const double* d_H_in, int max_iters,
+                  double* d_H_out, pm_h_refine_info* d_info)
+{
+    pm::ScopedKernelTime t(ctx, "homography_refine");
+    hipLaunchKernelGGL(homography_refine, dim3(1), dim3(HR_P), 0, ctx->stream, v, d_mask, d_H_in, max_iters, d_H_out,
+                       d_info);
+    PM_HIP_CHECK(hipGetLastError());
+    return PM_OK;
+}
+
+}  // namespace
+}  // namespace pm_hrefine
+
+using namespace pm_hrefine;
+
+extern "C" int pm_homography_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask,
+                                        const double* d_H_in, int max_iters, double* d_H_out, pm_h_refine_info* d_info)
+{
+    PM_REQUIRE(d_mask && d_H_in && d_H_out, PM_E_INVALID, "null argument");
+    int rc = check_iters(max_iters);
+    if (rc != PM_OK) return rc;
+    rc = pm_ransac::check_view(view);
+    if (rc != PM_OK) return rc;
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    return refine_launch(ctx, *view, d_mask, d_H_in, max_iters, d_H_out, d_info);
+}
+
+extern "C" int pm_homography_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
+                                    const double H_in[9], int max_iters, double H_out[9], pm_h_refine_info* info)
+{
+    PM_REQUIRE(H_in && H_out, PM_E_INVALID, "null H");
+    double hin[9];
+    memcpy(hin, H_in, sizeof hin);           // H_out may alias H_in
+    memcpy(H_out, hin, sizeof hin);
+    if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 1, 0};
+    int rc = check_iters(max_iters);
+    if (rc != PM_OK) return rc;
+    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2 && mask)), PM_E_INVALID, "bad point or mask arrays");
+    if (n < 4) { pm::set_error("need at least 4 correspondences, got %d", n); return PM_E_TOO_FEW; }
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+
+    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
+    rc = pm::arena_reserve(ctx, 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 4 * 256);
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
+    double* dH = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 9));
+    pm_h_refine_info* dinfo = static_cast<pm_h_refine_info*>(pm::arena_take(ctx, sizeof(pm_h_refine_info)));
+    PM_REQUIRE(dxy1 && dxy2 && dmask && dH && dinfo, PM_E_NOMEM, "scratch arena too small");
+    constexpr size_t HP_INFO = 80;           // pinned layout: H (72) | pad | info (32)
+    rc = pm::pinned_reserve(ctx, HP_INFO + sizeof(pm_h_refine_info));
+    if (rc != PM_OK) return rc;
+    char* hp = static_cast<char*>(ctx->pinned);
+    memcpy(hp, hin, sizeof hin);
+    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(dmask, mask, static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(dH, hp, sizeof hin, hipMemcpyHostToDevice, ctx->stream));
+    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
+    rc = refine_launch(ctx, v, dmask, dH, max_iters, dH, dinfo);
+    if (rc != PM_OK) return rc;
+    PM_HIP_CHECK(hipMemcpyAsync(hp, dH, sizeof hin, hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hp + HP_INFO, dinfo, sizeof(pm_h_refine_info), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    pm_h_refine_info r;
+    memcpy(&r, hp + HP_INFO, sizeof r);
+    memcpy(H_out, hp, sizeof hin);
+    if (info) *info = r;
+    if (r.status == 2) {
+        pm::set_error("the input H is zero (no model)");
+        return PM_E_NO_MODEL;
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
+                                            const pm_ransac_params* p, int max_iters, double H[9], uint8_t* mask,
+                                            int* n_inliers, uint64_t* best_key, pm_h_refine_info* info)
+{
+    if (H) for (int i = 0; i < 9; ++i) H[i] = 0.0;
+    if (mask && n > 0) memset(mask, 0, static_cast<size_t>(n));
+    if (n_inliers) *n_inliers = 0;
+    if (best_key) *best_key = 0;
+    if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 2, 0};
+    int rc = pm_ransac::ransac_h_check(p);
+    if (rc != PM_OK) return rc;
+    rc = check_iters(max_iters);
+    if (rc != PM_OK) return rc;
+    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2)), PM_E_INVALID, "bad point arrays");
+    if (n < 4) { pm::set_error("need at least 4 correspondences, got %d", n); return PM_E_TOO_FEW; }
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+
+    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
+    const size_t need = 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 6 * 256 +
+                        pm_ransac::fused_scratch_bytes(ctx, p) + 2048;
+    rc = pm::arena_reserve(ctx, need);
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
+    unsigned long long* dkey = static_cast<unsigned long long*>(pm::arena_take(ctx, 8));
+    double* dH = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 9));
+    int* dninl = static_cast<int*>(pm::arena_take(ctx, sizeof(int)));
+    pm_h_refine_info* dinfo = static_cast<pm_h_refine_info*>(pm::arena_take(ctx, sizeof(pm_h_refine_info)));
+    PM_REQUIRE(dxy1 && dxy2 && dmask && dkey && dH && dninl && dinfo, PM_E_NOMEM, "scratch arena too small");
+    constexpr size_t HP_INFO = 88, HP_MASK = 128;   // pinned layout: key (8) | H (72) | count (4) | pad | info (32) | mask
+    rc = pm::pinned_reserve(ctx, HP_MASK + static_cast<size_t>(n));
+    if (rc != PM_OK) return rc;
+
+    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
+    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
+    rc = pm_ransac::ransac_h_enqueue(ctx, v, p, dkey, dH, dmask, n, dninl);
+    if (rc != PM_OK) return rc;
+    rc = refine_launch(ctx, v, dmask, dH, max_iters, dH, dinfo);
+    if (rc != PM_OK) return rc;
+    char* hp = static_cast<char*>(ctx->pinned);
+    unsigned long long* hkey = reinterpret_cast<unsigned long long*>(hp);
+    double* hH = reinterpret_cast<double*>(hp + 8);
+    int* hninl = reinterpret_cast<int*>(hp + 80);
+    uint8_t* hmask = reinterpret_cast<uint8_t*>(hp + HP_MASK);
+    PM_HIP_CHECK(hipMemcpyAsync(hkey, dkey, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hH, dH, sizeof(double) * 9, hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hninl, dninl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hp + HP_INFO, dinfo, sizeof(pm_h_refine_info), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (best_key) *best_key = *hkey;
+    if (info) memcpy(info, hp + HP_INFO, sizeof(pm_h_refine_info));
+    if (*hkey == 0ull) {
+        pm::set_error("no valid model (all hypotheses degenerate)");
+        return PM_E_NO_MODEL;
+    }
+    if (H) memcpy(H, hH, sizeof(double) * 9);
+    if (mask) memcpy(mask, hmask, static_cast<size_t>(n));
+    if (n_inliers) *n_inliers = *hninl;
+    return PM_OK;
+}

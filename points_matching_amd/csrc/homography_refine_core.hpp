@@ -1,0 +1,235 @@
+// homography_refine_core.hpp — device arithmetic of the refinement of a robust homography on its inliers (docs/SPEC.md
+// S23 least-squares DLT refit, S24 Levenberg-Marquardt on the forward transfer error, S25 result), the step
+// cv::findHomography runs after its RANSAC loop.  Built with -ffp-contract=off like every unit: the only fused
+// multiply-adds are the explicit fma() calls, so tests/homography_refine_ref.c (the CPU restatement) reproduces the bits.
+// Sums over correspondences follow S23's fixed order (HR_P partials, stride-halving tree), independent of the grid.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "pm.h"
+
+namespace pm_hrefine {
+
+constexpr int HR_P = 512;                 // S23: partials = threads of the one workgroup
+constexpr int HR_CH = 16;                 // accumulators per LDS round of the cross-wave tree steps
+constexpr int HR_NORMAL = 45;             // unique entries of the 9 x 9 normal matrix
+constexpr int HR_LM = 45;                 // 36 of J^T J, 8 of J^T r, the cost
+constexpr int HR_SWEEPS = 16;             // S23 Jacobi sweep cap
+constexpr double HR_JACOBI_SKIP = 1e-17;  // S23: rotation (p, q) skipped unless |a_pq| > HR_JACOBI_SKIP * trace(M)
+constexpr double HR_LAMBDA0 = 1e-3;       // S24 initial damping
+constexpr double HR_MIN_H8 = 1e-8;        // S24: LM needs |H[8]| >= this (H of unit norm)
+constexpr double HR_STEP_TOL = 1e-15;     // S24: stop when max|delta| <= HR_STEP_TOL * max(1, max|h|)
+
+// S24: squared forward transfer error of one correspondence under the 9 entries of h.
+__device__ __forceinline__ double cost_term(const double (&h)[9], double x, double y, double xp, double yp)
+{
+    const double u = fma(h[0], x, fma(h[1], y, h[2]));
+    const double v = fma(h[3], x, fma(h[4], y, h[5]));
+    const double w = fma(h[6], x, fma(h[7], y, h[8]));
+    const double iw = 1.0 / w;
+    const double ru = u * iw - xp, rv = v * iw - yp;
+    return fma(ru, ru, rv * rv);
+}
+
+// S23 pass 3: the two DLT rows of one normalised correspondence into the upper triangle of M (row-major, j <= k).
+__device__ __forceinline__ void normal_term(double (&acc)[HR_NORMAL], double xn, double yn, double xq, double yq)
+{
+    const double a[9] = {-xn, -yn, -1.0, 0.0, 0.0, 0.0, xq * xn, xq * yn, xq};
+    const double b[9] = {0.0, 0.0, 0.0, -xn, -yn, -1.0, yq * xn, yq * yn, yq};
+    int e = 0;
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+#pragma unroll
+        for (int k = j; k < 9; ++k, ++e) acc[e] = acc[e] + fma(a[j], a[k], b[j] * b[k]);
+}
+
+// S24 pass: J^T J (upper triangle, row-major), J^T r and the cost of one correspondence at h (h[8] = 1).
+__device__ __forceinline__ void lm_term(double (&acc)[HR_LM], const double (&h)[9], double x, double y, double xp,
+                                        double yp)
+{
+    const double u = fma(h[0], x, fma(h[1], y, h[2]));
+    const double v = fma(h[3], x, fma(h[4], y, h[5]));
+    const double w = fma(h[6], x, fma(h[7], y, h[8]));
+    const double iw = 1.0 / w;
+    const double px = u * iw, py = v * iw;
+    const double ru = px - xp, rv = py - yp;
+    const double a = x * iw, b = y * iw, mpx = -px, mpy = -py;
+    const double ju[8] = {a, b, iw, 0.0, 0.0, 0.0, mpx * a, mpx * b};
+    const double jv[8] = {0.0, 0.0, 0.0, a, b, iw, mpy * a, mpy * b};
+    int e = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int k = j; k < 8; ++k, ++e) acc[e] = acc[e] + fma(ju[j], ju[k], jv[j] * jv[k]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[36 + j] = acc[36 + j] + fma(ju[j], ru, jv[j] * rv);
+    acc[44] = acc[44] + fma(ru, ru, rv * rv);
+}
+
+// S20 step 6: unit Frobenius norm, H[8] >= 0.  false = invalid (out untouched).
+__device__ __forceinline__ bool scale_sign(const double (&in)[9], double (&out)[9])
+{
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ss = fma(in[i], in[i], ss);
+    const double nrm = sqrt(ss);
+    if (!(nrm > 0.0) || !(nrm < __builtin_inf())) return false;
+    double inv = 1.0 / nrm;
+    if (in[8] < 0.0) inv = -inv;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out[i] = in[i] * inv;
+    return true;
+}
+
+// S20 step 5 on the S23 normalisation (t = -(s * c)), then step 6.
+__device__ __forceinline__ bool denormalise(const double (&hn)[9], double s1, double t1x, double t1y, double s2,
+                                           double t2x, double t2y, double (&H)[9])
+{
+    double M[3][3], Ho[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        M[i][0] = hn[3 * i] * s1;
+        M[i][1] = hn[3 * i + 1] * s1;
+        M[i][2] = fma(hn[3 * i], t1x, fma(hn[3 * i + 1], t1y, hn[3 * i + 2]));
+    }
+    const double u2x = -t2x, u2y = -t2y;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        Ho[j] = fma(u2x, M[2][j], M[0][j]);
+        Ho[3 + j] = fma(u2y, M[2][j], M[1][j]);
+        Ho[6 + j] = s2 * M[2][j];
+    }
+    return scale_sign(Ho, H);
+}
+
+// 64-bit value of lane l (l wave-uniform): two v_readlane.
+__device__ __forceinline__ double readlane_d(double x, int l)
+{
+    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(x));
+    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b & 0xFFFFFFFFu), l));
+    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(b >> 32), l));
+    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+}
+
+// S23 step 3: eigenvector of the smallest eigenvalue of the symmetric 9 x 9 M (upper triangle m45) by cyclic Jacobi,
+// run by ONE whole wave: lane k < 9 holds row k of A and row k of V, so the updates of a rotation's columns p and q are
+// lane-local, and rows p and q are refilled from them by v_readlane (A stays exactly symmetric, as in the C
+// restatement).  Every control value is read back through v_readlane, so it is wave-uniform.  hn: lane k < 9 returns
+// component k.  false = invalid (trace not in (0, inf)).
+__device__ __forceinline__ bool jacobi_min_wave(const double* m45, int lane, double& hn)
+{
+    double A[9], V[9];
+    const int r = lane < 9 ? lane : 0;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const int a = r < j ? r : j, b = r < j ? j : r;
+        const double m = m45[a * 9 - a * (a - 1) / 2 + (b - a)];
+        A[j] = lane < 9 ? m : 0.0;
+        V[j] = lane == j ? 1.0 : 0.0;
+    }
+    double tr = 0.0;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) tr = tr + readlane_d(A[j], j);
+    if (!(tr > 0.0) || !(tr < __builtin_inf())) return false;
+    const double thr = HR_JACOBI_SKIP * tr;
+    for (int sweep = 0; sweep < HR_SWEEPS; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+#pragma unroll
+            for (int q = p + 1; q < 9; ++q) {
+                const double apq = readlane_d(A[q], p);
+                if (!(fabs(apq) > thr)) continue;
+                rotated = true;
+                const double app = readlane_d(A[p], p), aqq = readlane_d(A[q], q);
+                const double theta = (aqq - app) / (2.0 * apq);
+                double t = 1.0 / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+                if (theta < 0.0) t = -t;
+                const double c = 1.0 / sqrt(fma(t, t, 1.0));
+                const double s = t * c;
+                // columns p and q of row `lane` (rows p and q themselves: the rotated diagonal and a zero)
+                const double akp = A[p], akq = A[q];
+                double np = fma(c, akp, -(s * akq)), nq = fma(s, akp, c * akq);
+                if (lane == p) { np = fma(-t, apq, app); nq = 0.0; }
+                if (lane == q) { np = 0.0; nq = fma(t, apq, aqq); }
+                A[p] = np;
+                A[q] = nq;
+                // rows p and q: A[p][k] = A[k][p], A[q][k] = A[k][q] for k != p, q
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    if (k == p || k == q) continue;
+                    const double vp = readlane_d(A[p], k), vq = readlane_d(A[q], k);
+                    if (lane == p) A[k] = vp;
+                    if (lane == q) A[k] = vq;
+                }
+                const double vkp = V[p], vkq = V[q];
+                V[p] = fma(c, vkp, -(s * vkq));
+                V[q] = fma(s, vkp, c * vkq);
+            }
+        }
+        if (!rotated) break;
+    }
+    int mi = 0;
+    double dmin = readlane_d(A[0], 0);
+#pragma unroll
+    for (int j = 1; j < 9; ++j) {
+        const double dj = readlane_d(A[j], j);
+        if (dj < dmin) { dmin = dj; mi = j; }
+    }
+    double vm = V[0];
+#pragma unroll
+    for (int j = 1; j < 9; ++j)
+        if (mi == j) vm = V[j];
+    hn = vm;
+    return true;
+}
+
+// S24: (J^T J + lam * diag(J^T J)) d = -g by an 8 x 8 Cholesky in a fixed order.  jtjg: 36 upper-triangle entries of
+// J^T J (row-major) then the 8 of g = J^T r; d: 8 doubles (LDS).  false = not positive definite.  Not inlined: one
+// thread runs it between two passes, and inlined into the LM loop it pushes the kernel past 256 VGPRs.
+__device__ __attribute__((noinline)) bool lm_solve(const double* jtjg, double lam, double* d)
+{
+    // A[i][j] (i >= j) is read from the packed upper triangle as needed: jtjg[j*8 - j*(j-1)/2 + (i - j)]
+    double L[8][8], y[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const double ajj = jtjg[j * 8 - j * (j - 1) / 2];
+        double dd = ajj + lam * ajj;
+#pragma unroll
+        for (int k = 0; k < j; ++k) dd = fma(-L[j][k], L[j][k], dd);
+        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
+        L[j][j] = sqrt(dd);
+#pragma unroll
+        for (int i = j + 1; i < 8; ++i) {
+            double v = jtjg[j * 8 - j * (j - 1) / 2 + (i - j)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
+            L[i][j] = v / L[j][j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        double v = -jtjg[36 + i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v = fma(-L[i][k], y[k], v);
+        y[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 8; ++k) v = fma(-L[k][i], d[k], v);
+        d[i] = v / L[i][i];
+    }
+    return true;
+}
+
+}  // namespace pm_hrefine
+
+namespace pm_ransac {
+// Host side of the RANSAC-H launch (ransac_h_fused.hip), for pm_ransac_homography_refined: the argument check and the
+// enqueue itself (no synchronisation; the arena must hold fused_scratch_bytes() more, as for pm_ransac_homography).
+int ransac_h_check(const pm_ransac_params* p);
+int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
+                     double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
+}  // namespace pm_ransac

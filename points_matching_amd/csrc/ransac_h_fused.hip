@@ -11,6 +11,7 @@
 //   * each workgroup writes its best key (S22) and fp64 model to its slot and draws a ticket; the last one picks the
 //     winner, publishes key / H / count and writes the mask.
 #include "homography_core.hpp"
+#include "homography_refine_core.hpp"
 #include "ransac_fused_kernels.hpp"
 
 namespace pm_ransac {
@@ -362,6 +363,14 @@ int host_run_h(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_
 }
 
 }  // namespace
+
+// for pm_ransac_homography_refined (homography_refine.hip): RANSAC-H and the refinement on one stream, one synchronisation
+int ransac_h_check(const pm_ransac_params* p) { return check_params_h(p); }
+int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
+                     double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl)
+{
+    return h_launch(ctx, v, p, d_key, d_H, d_mask, mask_len, d_ninl);
+}
 }  // namespace pm_ransac
 
 using namespace pm_ransac;
