@@ -2,15 +2,19 @@
 // 4-point DLT, S21 division-free reprojection test).  The counterpart of cv::findHomography(pts1, pts2, RANSAC, thr),
 // the sibling of the cv::findFundamentalMat call at main.cpp:95-98.  Built with -ffp-contract=off like the RANSAC-F
 // units: the only fused multiply-adds are the explicit fma()/fmaf() calls, so tests/homography_ref.c (the CPU
-// restatement) reproduces the same bits.  The 9 x 8 Householder QR is a copy of S7 step 3 (ransac_core.hpp solve8), kept
-// separate so that the F kernels' generated code cannot change.
+// restatement) reproduces the same bits.  The Hartley normalisation, the 9 x 8 Householder QR and the scale/sign step are
+// S7's (ransac_core.hpp), shared with the 8-point solve.
 #pragma once
 #include "ransac_core.hpp"
 
 namespace pm_homog {
 
 using pm_ransac::f32x2;
+using pm_ransac::hartley;
+using pm_ransac::householder_null9x8;
+using pm_ransac::householder_qr9x8;
 using pm_ransac::mix64;
+using pm_ransac::scale_sign;
 
 // S20: |cross| of a normalised triple at or below this is collinear (normalised points sit at mean distance sqrt(2)
 // from their centroid, so the bound is ~3.5e-5 of a typical triangle's doubled area)
@@ -49,29 +53,6 @@ __device__ __forceinline__ void sample4(uint64_t seed, uint64_t h, int n, int (&
     }
 }
 
-// SPEC S20 step 1: Hartley normalisation of 4 points (S7 step 1 with * 0.25).
-__device__ __forceinline__ bool hartley4(const double (&px)[4], const double (&py)[4], double (&nx)[4], double (&ny)[4],
-                                         double& s, double& tx, double& ty)
-{
-    double cx = px[0], cy = py[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) { cx = cx + px[i]; cy = cy + py[i]; }
-    cx = cx * 0.25; cy = cy * 0.25;
-    double md = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double dx = px[i] - cx, dy = py[i] - cy;
-        md = md + sqrt(fma(dx, dx, dy * dy));
-    }
-    md = md * 0.25;
-    if (!(md > 0.0) || !(md < __builtin_inf())) return false;
-    s = 1.4142135623730951 / md;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { nx[i] = (px[i] - cx) * s; ny[i] = (py[i] - cy) * s; }
-    tx = -(s * cx); ty = -(s * cy);
-    return true;
-}
-
 // SPEC S20 step 2: doubled signed area of the normalised triple (a, b, c), unfused.
 __device__ __forceinline__ double cross3(const double (&x)[4], const double (&y)[4], int a, int b, int c)
 {
@@ -94,74 +75,11 @@ __device__ __forceinline__ bool sample_ok(const double (&ax)[4], const double (&
     return same[0] == same[1] && same[0] == same[2] && same[0] == same[3];
 }
 
-// SPEC S7 step 3 (copied, see the file comment): null vector f of the 9 x 8 matrix B by Householder QR.
-__device__ __forceinline__ void householder_null9x8(double (&B)[9][8], double (&f)[9])
+// SPEC S20 steps 5-6: H ~ (s2 T2^-1) Hn T1, where s2 T2^-1 = [[1, 0, -t2x], [0, 1, -t2y], [0, 0, s2]], then unit norm
+// and sign.  false = invalid (H untouched).
+__device__ __forceinline__ bool denormalise(const double (&hn)[9], double s1, double t1x, double t1y, double s2,
+                                           double t2x, double t2y, double (&H)[9])
 {
-    double beta[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        double sigma = 0.0;
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) sigma = fma(B[i][j], B[i][j], sigma);
-        const double alpha = B[j][j];
-        const double nrm = sqrt(fma(alpha, alpha, sigma));
-        if (!(nrm > 0.0)) { beta[j] = 0.0; continue; }
-        const double v0 = alpha + (alpha >= 0.0 ? nrm : -nrm);
-        const double vtv = fma(v0, v0, sigma);
-        beta[j] = 2.0 / vtv;
-        B[j][j] = v0;
-#pragma unroll
-        for (int c = j + 1; c < 8; ++c) {
-            double dot = v0 * B[j][c];
-#pragma unroll
-            for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], B[i][c], dot);
-            const double w = beta[j] * dot;
-            B[j][c] = fma(-w, v0, B[j][c]);
-#pragma unroll
-            for (int i = j + 1; i < 9; ++i) B[i][c] = fma(-w, B[i][j], B[i][c]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = 0.0;
-    f[8] = 1.0;
-#pragma unroll
-    for (int j = 7; j >= 0; --j) {
-        if (beta[j] == 0.0) continue;
-        double dot = B[j][j] * f[j];
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], f[i], dot);
-        const double w = beta[j] * dot;
-        f[j] = fma(-w, B[j][j], f[j]);
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) f[i] = fma(-w, B[i][j], f[i]);
-    }
-}
-
-// SPEC S20: normalised 4-point DLT.  Returns false for an invalid sample (H is then 0).
-__device__ __forceinline__ bool solve4(const double (&x1)[4], const double (&y1)[4], const double (&x2)[4],
-                                       const double (&y2)[4], double (&H)[9])
-{
-#pragma unroll
-    for (int i = 0; i < 9; ++i) H[i] = 0.0;
-    double ax[4], ay[4], bx[4], by[4], s1, t1x, t1y, s2, t2x, t2y;
-    if (!hartley4(x1, y1, ax, ay, s1, t1x, t1y)) return false;
-    if (!hartley4(x2, y2, bx, by, s2, t2x, t2y)) return false;
-    if (!sample_ok(ax, ay, bx, by)) return false;
-    // B = A^T (9 x 8): columns 2c and 2c+1 are the two constraint rows of correspondence c
-    double B[9][8];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int k = 2 * c, l = 2 * c + 1;
-        B[0][k] = -ax[c];        B[1][k] = -ay[c];        B[2][k] = -1.0;
-        B[3][k] = 0.0;           B[4][k] = 0.0;           B[5][k] = 0.0;
-        B[6][k] = bx[c] * ax[c]; B[7][k] = bx[c] * ay[c]; B[8][k] = bx[c];
-        B[0][l] = 0.0;           B[1][l] = 0.0;           B[2][l] = 0.0;
-        B[3][l] = -ax[c];        B[4][l] = -ay[c];        B[5][l] = -1.0;
-        B[6][l] = by[c] * ax[c]; B[7][l] = by[c] * ay[c]; B[8][l] = by[c];
-    }
-    double hn[9];
-    householder_null9x8(B, hn);
-    // denormalise: H ~ (s2 T2^-1) Hn T1, where s2 T2^-1 = [[1, 0, -t2x], [0, 1, -t2y], [0, 0, s2]]
     double M[3][3], Ho[9];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -176,16 +94,35 @@ __device__ __forceinline__ bool solve4(const double (&x1)[4], const double (&y1)
         Ho[3 + j] = fma(u2y, M[2][j], M[1][j]);
         Ho[6 + j] = s2 * M[2][j];
     }
-    double ss = 0.0;
+    return scale_sign(Ho, H);
+}
+
+// SPEC S20: normalised 4-point DLT.  Returns false for an invalid sample (H is then 0).
+__device__ __forceinline__ bool solve4(const double (&x1)[4], const double (&y1)[4], const double (&x2)[4],
+                                       const double (&y2)[4], double (&H)[9])
+{
 #pragma unroll
-    for (int i = 0; i < 9; ++i) ss = fma(Ho[i], Ho[i], ss);
-    const double nrm = sqrt(ss);
-    if (!(nrm > 0.0) || !(nrm < __builtin_inf())) return false;
-    double inv = 1.0 / nrm;
-    if (Ho[8] < 0.0) inv = -inv;
+    for (int i = 0; i < 9; ++i) H[i] = 0.0;
+    double ax[4], ay[4], bx[4], by[4], s1, t1x, t1y, s2, t2x, t2y;
+    if (!hartley(x1, y1, ax, ay, s1, t1x, t1y)) return false;
+    if (!hartley(x2, y2, bx, by, s2, t2x, t2y)) return false;
+    if (!sample_ok(ax, ay, bx, by)) return false;
+    // B = A^T (9 x 8): columns 2c and 2c+1 are the two constraint rows of correspondence c
+    double B[9][8];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) H[i] = Ho[i] * inv;
-    return true;
+    for (int c = 0; c < 4; ++c) {
+        const int k = 2 * c, l = 2 * c + 1;
+        B[0][k] = -ax[c];        B[1][k] = -ay[c];        B[2][k] = -1.0;
+        B[3][k] = 0.0;           B[4][k] = 0.0;           B[5][k] = 0.0;
+        B[6][k] = bx[c] * ax[c]; B[7][k] = bx[c] * ay[c]; B[8][k] = bx[c];
+        B[0][l] = 0.0;           B[1][l] = 0.0;           B[2][l] = 0.0;
+        B[3][l] = -ax[c];        B[4][l] = -ay[c];        B[5][l] = -1.0;
+        B[6][l] = by[c] * ax[c]; B[7][l] = by[c] * ay[c]; B[8][l] = by[c];
+    }
+    double beta[8], hn[9];
+    householder_qr9x8(B, beta);
+    householder_null9x8(B, beta, hn);
+    return denormalise(hn, s1, t1x, t1y, s2, t2x, t2y, H);
 }
 
 // SPEC S21: fp32 one-way reprojection test of one correspondence against h = H32.  w == 0 and NaN are outliers.

@@ -12,12 +12,15 @@
 // start point, one per iteration).
 //
 // The launch keeps no per-call state, so the device form may be captured; the host forms synchronise.
+#include "homography_core.hpp"
 #include "homography_refine_core.hpp"
 #include "ransac_fused_kernels.hpp"
 
 namespace pm_hrefine {
 namespace {
 
+using pm_homog::denormalise;
+using pm_ransac::scale_sign;
 using pm_ransac::view_count1;
 using pm_ransac::view_offsets;
 using pm_ransac::view_point;

@@ -66,42 +66,6 @@ __device__ __forceinline__ void lm_term(double (&acc)[HR_LM], const double (&h)[
     acc[44] = acc[44] + fma(ru, ru, rv * rv);
 }
 
-// S20 step 6: unit Frobenius norm, H[8] >= 0.  false = invalid (out untouched).
-__device__ __forceinline__ bool scale_sign(const double (&in)[9], double (&out)[9])
-{
-    double ss = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ss = fma(in[i], in[i], ss);
-    const double nrm = sqrt(ss);
-    if (!(nrm > 0.0) || !(nrm < __builtin_inf())) return false;
-    double inv = 1.0 / nrm;
-    if (in[8] < 0.0) inv = -inv;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) out[i] = in[i] * inv;
-    return true;
-}
-
-// S20 step 5 on the S23 normalisation (t = -(s * c)), then step 6.
-__device__ __forceinline__ bool denormalise(const double (&hn)[9], double s1, double t1x, double t1y, double s2,
-                                           double t2x, double t2y, double (&H)[9])
-{
-    double M[3][3], Ho[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        M[i][0] = hn[3 * i] * s1;
-        M[i][1] = hn[3 * i + 1] * s1;
-        M[i][2] = fma(hn[3 * i], t1x, fma(hn[3 * i + 1], t1y, hn[3 * i + 2]));
-    }
-    const double u2x = -t2x, u2y = -t2y;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        Ho[j] = fma(u2x, M[2][j], M[0][j]);
-        Ho[3 + j] = fma(u2y, M[2][j], M[1][j]);
-        Ho[6 + j] = s2 * M[2][j];
-    }
-    return scale_sign(Ho, H);
-}
-
 // 64-bit value of lane l (l wave-uniform): two v_readlane.
 __device__ __forceinline__ double readlane_d(double x, int l)
 {
@@ -225,11 +189,3 @@ __device__ __attribute__((noinline)) bool lm_solve(const double* jtjg, double la
 }
 
 }  // namespace pm_hrefine
-
-namespace pm_ransac {
-// Host side of the RANSAC-H launch (ransac_h_fused.hip), for pm_ransac_homography_refined: the argument check and the
-// enqueue itself (no synchronisation; the arena must hold fused_scratch_bytes() more, as for pm_ransac_homography).
-int ransac_h_check(const pm_ransac_params* p);
-int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
-                     double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
-}  // namespace pm_ransac

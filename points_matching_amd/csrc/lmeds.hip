@@ -16,19 +16,15 @@
 #include <cfloat>
 #include <cmath>
 
-#include "pm_common.hpp"
+#include "ransac_core.hpp"
 
 namespace {
 
 constexpr int LM_MAX_N = 32768;          // residual keys of one model live in LDS (128 KB)
 constexpr double LM_INF = __builtin_inf();
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
+using pm_ransac::hartley;
+using pm_ransac::mix64;
 
 // SPEC S13: 7 distinct indices in [0, n) as a pure function of (seed, h, n).
 __device__ __forceinline__ void sample7(uint64_t seed, uint64_t h, int n, int (&idx)[7])
@@ -63,28 +59,6 @@ __device__ __forceinline__ void sample7(uint64_t seed, uint64_t h, int n, int (&
     }
 }
 
-__device__ __forceinline__ bool hartley7(const double (&px)[7], const double (&py)[7], double (&nx)[7],
-                                         double (&ny)[7], double& s, double& tx, double& ty)
-{
-    double cx = px[0], cy = py[0];
-#pragma unroll
-    for (int i = 1; i < 7; ++i) { cx = cx + px[i]; cy = cy + py[i]; }
-    cx = cx / 7.0; cy = cy / 7.0;
-    double md = 0.0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        const double dx = px[i] - cx, dy = py[i] - cy;
-        md = md + sqrt(fma(dx, dx, dy * dy));
-    }
-    md = md / 7.0;
-    if (!(md > 0.0) || !(md < LM_INF)) return false;
-    s = 1.4142135623730951 / md;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) { nx[i] = (px[i] - cx) * s; ny[i] = (py[i] - cy) * s; }
-    tx = -(s * cx); ty = -(s * cy);
-    return true;
-}
-
 __device__ __forceinline__ double det3(double r00, double r01, double r02, double r10, double r11, double r12,
                                        double r20, double r21, double r22)
 {
@@ -108,8 +82,8 @@ __device__ __forceinline__ void solve7(const double (&x1)[7], const double (&y1)
         for (int i = 0; i < 9; ++i) F[r][i] = 0.0;
     }
     double ax[7], ay[7], bx[7], by[7], s1, t1x, t1y, s2, t2x, t2y;
-    if (!hartley7(x1, y1, ax, ay, s1, t1x, t1y)) return;
-    if (!hartley7(x2, y2, bx, by, s2, t2x, t2y)) return;
+    if (!hartley(x1, y1, ax, ay, s1, t1x, t1y)) return;
+    if (!hartley(x2, y2, bx, by, s2, t2x, t2y)) return;
     double B[9][7], beta[7];
 #pragma unroll
     for (int c = 0; c < 7; ++c) {

@@ -1,6 +1,7 @@
 // ransac_core.hpp — device functions shared by the RANSAC-F translation units (ransac.hip: hypothesis-per-lane
 // kernels for large correspondence sets and the sharded legacy entry points; ransac_fused.hip: the one-launch
-// solve + score + pick + mask kernel).  Every operation is written in the order docs/SPEC.md fixes (S6 sampler,
+// solve + score + pick + mask kernel); the fp64 normalisation, QR and scale/sign steps also serve RANSAC-H
+// (homography_core.hpp) and LMedS (lmeds.hip).  Every operation is written in the order docs/SPEC.md fixes (S6 sampler,
 // S7 normalised 8-point solve, S8 inlier test); both TUs are built with -ffp-contract=off, so the only fused
 // multiply-adds are the explicit fma()/fmaf() calls and the CPU restatement reproduces the same bits.
 // Replaces the arithmetic behind cv::findFundamentalMat (main.cpp:95-98) with the estimator BASELINE.json names.
@@ -87,26 +88,92 @@ __device__ __forceinline__ void sample8(uint64_t seed, uint64_t h, int n, int (&
     }
 }
 
-// SPEC S7, Hartley normalisation of 8 points: centroid to the origin, mean distance sqrt(2).
-__device__ __forceinline__ bool hartley8(const double (&px)[8], const double (&py)[8], double (&nx)[8],
-                                         double (&ny)[8], double& s, double& tx, double& ty)
+// SPEC S7 step 1 (and S14 step 1, S20 step 1): Hartley normalisation of N points, centroid to the origin, mean distance
+// sqrt(2).  The means divide by N (for N = 4 and 8 the same bits as a multiply by 1/N).
+template <int N>
+__device__ __forceinline__ bool hartley(const double (&px)[N], const double (&py)[N], double (&nx)[N], double (&ny)[N],
+                                        double& s, double& tx, double& ty)
 {
     double cx = px[0], cy = py[0];
 #pragma unroll
-    for (int i = 1; i < 8; ++i) { cx = cx + px[i]; cy = cy + py[i]; }
-    cx = cx * 0.125; cy = cy * 0.125;
+    for (int i = 1; i < N; ++i) { cx = cx + px[i]; cy = cy + py[i]; }
+    cx = cx / N; cy = cy / N;
     double md = 0.0;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < N; ++i) {
         const double dx = px[i] - cx, dy = py[i] - cy;
         md = md + sqrt(fma(dx, dx, dy * dy));
     }
-    md = md * 0.125;
+    md = md / N;
     if (!(md > 0.0) || !(md < __builtin_inf())) return false;
     s = 1.4142135623730951 / md;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { nx[i] = (px[i] - cx) * s; ny[i] = (py[i] - cy) * s; }
+    for (int i = 0; i < N; ++i) { nx[i] = (px[i] - cx) * s; ny[i] = (py[i] - cy) * s; }
     tx = -(s * cx); ty = -(s * cy);
+    return true;
+}
+
+// SPEC S7 step 3 (and S20 step 4), first half: Householder QR of the 9 x 8 matrix B; reflector j stays in column j
+// (v0 on the diagonal), beta[j] = 0 for a skipped column.  Two functions with beta owned by the caller, not one: with
+// beta local to a single QR + null-vector function the F solver kernels came out 10 VGPRs larger.
+__device__ __forceinline__ void householder_qr9x8(double (&B)[9][8], double (&beta)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        double sigma = 0.0;
+#pragma unroll
+        for (int i = j + 1; i < 9; ++i) sigma = fma(B[i][j], B[i][j], sigma);
+        const double alpha = B[j][j];
+        const double nrm = sqrt(fma(alpha, alpha, sigma));
+        if (!(nrm > 0.0)) { beta[j] = 0.0; continue; }
+        const double v0 = alpha + (alpha >= 0.0 ? nrm : -nrm);
+        const double vtv = fma(v0, v0, sigma);
+        beta[j] = 2.0 / vtv;
+        B[j][j] = v0;
+#pragma unroll
+        for (int c = j + 1; c < 8; ++c) {
+            double dot = v0 * B[j][c];
+#pragma unroll
+            for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], B[i][c], dot);
+            const double w = beta[j] * dot;
+            B[j][c] = fma(-w, v0, B[j][c]);
+#pragma unroll
+            for (int i = j + 1; i < 9; ++i) B[i][c] = fma(-w, B[i][j], B[i][c]);
+        }
+    }
+}
+
+// ... second half: the null vector f = H0 H1 ... H7 e8 of the factored B.
+__device__ __forceinline__ void householder_null9x8(const double (&B)[9][8], const double (&beta)[8], double (&f)[9])
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = 0.0;
+    f[8] = 1.0;
+#pragma unroll
+    for (int j = 7; j >= 0; --j) {
+        if (beta[j] == 0.0) continue;
+        double dot = B[j][j] * f[j];
+#pragma unroll
+        for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], f[i], dot);
+        const double w = beta[j] * dot;
+        f[j] = fma(-w, B[j][j], f[j]);
+#pragma unroll
+        for (int i = j + 1; i < 9; ++i) f[i] = fma(-w, B[i][j], f[i]);
+    }
+}
+
+// SPEC S7 step 6 (and S20 step 6): unit Frobenius norm, m[8] >= 0.  false = invalid (out untouched).
+__device__ __forceinline__ bool scale_sign(const double (&in)[9], double (&out)[9])
+{
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ss = fma(in[i], in[i], ss);
+    const double nrm = sqrt(ss);
+    if (!(nrm > 0.0) || !(nrm < __builtin_inf())) return false;
+    double inv = 1.0 / nrm;
+    if (in[8] < 0.0) inv = -inv;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) out[i] = in[i] * inv;
     return true;
 }
 
@@ -144,56 +211,22 @@ __device__ __forceinline__ bool solve8(const double (&x1)[8], const double (&y1)
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i] = 0.0;
     double ax[8], ay[8], bx[8], by[8], s1, t1x, t1y, s2, t2x, t2y;
-    if (!hartley8(x1, y1, ax, ay, s1, t1x, t1y)) return false;
-    if (!hartley8(x2, y2, bx, by, s2, t2x, t2y)) return false;
+    if (!hartley(x1, y1, ax, ay, s1, t1x, t1y)) return false;
+    if (!hartley(x2, y2, bx, by, s2, t2x, t2y)) return false;
 
     DIAG::solve(1);
     // B = A^T (9 x 8): column c is the epipolar constraint row of correspondence c
-    double B[9][8], beta[8];
+    double B[9][8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         B[0][c] = bx[c] * ax[c]; B[1][c] = bx[c] * ay[c]; B[2][c] = bx[c];
         B[3][c] = by[c] * ax[c]; B[4][c] = by[c] * ay[c]; B[5][c] = by[c];
         B[6][c] = ax[c];         B[7][c] = ay[c];         B[8][c] = 1.0;
     }
-    // Householder QR of B; reflector j stays in column j (v0 on the diagonal)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        double sigma = 0.0;
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) sigma = fma(B[i][j], B[i][j], sigma);
-        const double alpha = B[j][j];
-        const double nrm = sqrt(fma(alpha, alpha, sigma));
-        if (!(nrm > 0.0)) { beta[j] = 0.0; continue; }
-        const double v0 = alpha + (alpha >= 0.0 ? nrm : -nrm);
-        const double vtv = fma(v0, v0, sigma);
-        beta[j] = 2.0 / vtv;
-        B[j][j] = v0;
-#pragma unroll
-        for (int c = j + 1; c < 8; ++c) {
-            double dot = v0 * B[j][c];
-#pragma unroll
-            for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], B[i][c], dot);
-            const double w = beta[j] * dot;
-            B[j][c] = fma(-w, v0, B[j][c]);
-#pragma unroll
-            for (int i = j + 1; i < 9; ++i) B[i][c] = fma(-w, B[i][j], B[i][c]);
-        }
-    }
+    double beta[8], f[9];
+    householder_qr9x8(B, beta);
     DIAG::solve(2);
-    // null vector f = H0 H1 ... H7 e8
-    double f[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0};
-#pragma unroll
-    for (int j = 7; j >= 0; --j) {
-        if (beta[j] == 0.0) continue;
-        double dot = B[j][j] * f[j];
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) dot = fma(B[i][j], f[i], dot);
-        const double w = beta[j] * dot;
-        f[j] = fma(-w, B[j][j], f[j]);
-#pragma unroll
-        for (int i = j + 1; i < 9; ++i) f[i] = fma(-w, B[i][j], f[i]);
-    }
+    householder_null9x8(B, beta, f);
     DIAG::solve(3);
     // rank 2: one-sided Jacobi on the columns of G, six fixed sweeps, then drop the smallest column
     double G[3][3], V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
@@ -244,16 +277,7 @@ __device__ __forceinline__ bool solve8(const double (&x1)[8], const double (&y1)
         Fo[3 + j] = s2 * M[1][j];
         Fo[6 + j] = fma(t2x, M[0][j], fma(t2y, M[1][j], M[2][j]));
     }
-    double ss = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) ss = fma(Fo[i], Fo[i], ss);
-    const double nrm = sqrt(ss);
-    if (!(nrm > 0.0) || !(nrm < __builtin_inf())) return false;
-    double inv = 1.0 / nrm;
-    if (Fo[8] < 0.0) inv = -inv;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F[i] = Fo[i] * inv;
-    return true;
+    return scale_sign(Fo, F);
 }
 
 __device__ __forceinline__ bool hyp_model(const float* __restrict__ xy1, const float* __restrict__ xy2, int n,

@@ -20,10 +20,12 @@
 // The correspondences may be given as `parts` padded blocks with device-side counts (the all-gathered survivors
 // of a query-row-sharded matcher): the view is resolved while loading, no concatenation pass exists.
 //
-// Everything here is templated on a diagnostics policy (ransac_core.hpp: NoDiag).  Three translation units include this
-// header: csrc/ransac_fused.hip (the product launch: NoDiag, nothing else instantiated), csrc/ransac_shard.hip (finish
-// kernel + the sharded C-ABI entry points; it shares the view helpers) and tools/ablation/ransac_fused_stamps.hip (a
-// diagnostic launch with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).
+// Everything here is templated on a diagnostics policy (ransac_core.hpp: NoDiag); the LDS form below is also templated on
+// a model policy (FModel here, HModel in csrc/ransac_h_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
+// (the product launch: NoDiag, nothing else instantiated) and tools/ablation/ransac_fused_stamps.hip (a diagnostic launch
+// with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).  csrc/ransac_h_fused.hip
+// instantiates the LDS form for the homography; csrc/ransac_shard.hip (finish kernel + the sharded C-ABI entry points)
+// and csrc/homography_refine.hip share the view helpers.
 #pragma once
 #include "ransac_core.hpp"
 #include "ransac_internal.hpp"
@@ -192,6 +194,36 @@ __device__ __forceinline__ void inlier_pk_model(const ModelS& m, f32x2 x, f32x2 
         ib = (n2[1] <= r2[1]) && (n2[1] <= r1[1]);
     }
 }
+
+// Model policy of the LDS one-launch kernel (ransac_fused_lds): the fundamental matrix with error KIND (SPEC S6-S8).
+// The homography policy, HModel, lives in ransac_h_fused.hip.  A policy supplies
+//   MIN_PTS             the minimal sample size (fewer correspondences: no valid model);
+//   solve<DIAG>         the sample and fp64 solve of hypothesis h by one lane;
+//   inlier_pk           the packed test of two correspondences, model in SGPR pairs (score phase);
+//   inlier_x2           the same test, model in VGPRs (mask phase);
+//   SHARD_OUT           whether the run may end in a shard record (out.shard) or a result block (out.fo).  Without
+//                       them the tail carries no tests of either (measured: ~0.4 us at 512-2275 correspondences).
+template <int KIND>
+struct FModel {
+    static constexpr int MIN_PTS = 8;
+    static constexpr bool SHARD_OUT = true;
+    template <typename DIAG>
+    static __device__ __forceinline__ bool solve(const pm_points_view& v, const int* __restrict__ offs, int n, uint64_t seed,
+                                                 uint64_t h, double (&F)[9])
+    {
+        return hyp_model_view<DIAG>(v, offs, n, seed, h, F);
+    }
+    static __device__ __forceinline__ void inlier_pk(const ModelS& m, f32x2 x, f32x2 y, f32x2 xp, f32x2 yp, float thr2, bool& ia,
+                                                     bool& ib)
+    {
+        inlier_pk_model<KIND>(m, x, y, xp, yp, thr2, ia, ib);
+    }
+    static __device__ __forceinline__ void inlier_x2(const float (&f)[9], f32x2 x, f32x2 y, f32x2 xp, f32x2 yp, float thr2,
+                                                     bool& ia, bool& ib)
+    {
+        inlier32_x2_flags<KIND>(f, x, y, xp, yp, thr2, ia, ib);
+    }
+};
 
 // One tile against this team's share of the `hcount` models of the workgroup, KM register slots in use (compile-time: no per-slot
 // branches).  The model of hypothesis s+1 is requested from LDS before hypothesis s is scored; the ten verdict masks
@@ -479,7 +511,7 @@ constexpr int RL_MAX_SLOTS = 64;             // slots per LDS tile: 128 KiB dyna
 
 // NH hypotheses of one wave (ids s0, s0 + RL_WAVES, ...) over the slots of the LDS tile in ONE pass: each operand read serves NH
 // models (the LDS port, 4 x 512 B per wave and slot, would otherwise be ~3/4 as busy as the VALU and the two contend).
-template <int KIND, int NH>
+template <typename MODEL, int NH>
 __device__ __forceinline__ void score_lds(const float (*s_mdl)[12], int* s_cnt, const f32x2* pp, int kslots, int s0, float thr2, int lane)
 {
     ModelS ms[NH];
@@ -497,7 +529,7 @@ __device__ __forceinline__ void score_lds(const float (*s_mdl)[12], int* s_cnt, 
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
             bool ia, ib;
-            inlier_pk_model<KIND>(ms[h], x, y, xp, yp, thr2, ia, ib);
+            MODEL::inlier_pk(ms[h], x, y, xp, yp, thr2, ia, ib);
             c[h] += __popcll(__ballot(ia)) + __popcll(__ballot(ib));
         }
     }
@@ -507,7 +539,7 @@ __device__ __forceinline__ void score_lds(const float (*s_mdl)[12], int* s_cnt, 
     }
 }
 
-template <int KIND, typename DIAG>
+template <typename MODEL, typename DIAG>
 __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v, uint64_t seed, int64_t hyp_begin, int nh, int hb,
                                                                float thr2, int tile_slots, RfSlot* __restrict__ slots,
                                                                int* __restrict__ ticket, RfOut out)
@@ -562,7 +594,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         return k < 0 ? 0 : (k > tile_slots ? tile_slots : k);
     };
 
-    // ---- solve (threads < hcount: SPEC S6, S7) || tile 0 -> LDS (the other waves)
+    // ---- solve (threads < hcount: SPEC S6, S7 / S19, S20) || tile 0 -> LDS (the other waves)
     const int h0 = static_cast<int>(blockIdx.x) * hb;
     const int hcount = nh - h0 < hb ? nh - h0 : hb;
     const int solver_waves = (hcount + 63) / 64;                            // 1 (or 2 beyond 64 ids per workgroup)
@@ -573,7 +605,8 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
             bool ok = false;
 #pragma unroll
             for (int i = 0; i < 9; ++i) F[i] = 0.0;
-            if (n >= 8) ok = hyp_model_view<DIAG>(v, s_offs, n, seed, static_cast<uint64_t>(hyp_begin + h0 + tid), F);
+            if (n >= MODEL::MIN_PTS)
+                ok = MODEL::template solve<DIAG>(v, s_offs, n, seed, static_cast<uint64_t>(hyp_begin + h0 + tid), F);
 #pragma unroll
             for (int i = 0; i < 9; ++i) { s_mdl[tid][i] = static_cast<float>(F[i]); s_m64[tid][i] = F[i]; }
             s_mdl[tid][9] = ok ? 1.f : 0.f;
@@ -598,16 +631,16 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         }
         for (int s = wave; s < hcount; s += 4 * RL_WAVES) {
             const int left = (hcount - s + RL_WAVES - 1) / RL_WAVES;       // hypotheses of this wave from s on
-            if (left >= 4) score_lds<KIND, 4>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else if (left == 3) score_lds<KIND, 3>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else if (left == 2) score_lds<KIND, 2>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else score_lds<KIND, 1>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+            if (left >= 4) score_lds<MODEL, 4>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+            else if (left == 3) score_lds<MODEL, 3>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+            else if (left == 2) score_lds<MODEL, 2>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+            else score_lds<MODEL, 1>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
         }
     }
     DIAG::phase(5);
     __syncthreads();
 
-    // ---- the workgroup's best key (SPEC S9: most inliers, then lowest id) and its slot
+    // ---- the workgroup's best key (SPEC S9 / S22: most inliers, then lowest id) and its slot
     unsigned long long key = 0ull;
     if (tid < hcount && s_mdl[tid][9] != 0.f)
         key = (static_cast<unsigned long long>(static_cast<uint32_t>(s_cnt[tid])) << 32) |
@@ -649,7 +682,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         }
     }
     const unsigned long long kwin = wg_max_u64<RL_WAVES>(kb, s_wk, tid);
-    const bool ok = kwin != 0ull && n >= 8;
+    const bool ok = kwin != 0ull && n >= MODEL::MIN_PTS;
     if (tid < 9) s_F64[tid] = 0.0;
     __syncthreads();
     if (ok && kb == kwin) {                                  // exactly one thread: keys of distinct ids differ
@@ -658,18 +691,18 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
     }
     __syncthreads();
     DIAG::phase(7);
-    if (out.shard) {
+    if (MODEL::SHARD_OUT && out.shard) {
         if (tid < 9) out.rec->F[tid] = s_F64[tid];
         if (tid == 9) out.rec->key = ok ? kwin : 0ull;
         return;
     }
     if (tid < 9) {
         if (out.F) out.F[tid] = s_F64[tid];
-        if (out.fo) { out.fo->F[tid] = s_F64[tid]; out.fo->F32[tid] = static_cast<float>(s_F64[tid]); }
+        if (MODEL::SHARD_OUT && out.fo) { out.fo->F[tid] = s_F64[tid]; out.fo->F32[tid] = static_cast<float>(s_F64[tid]); }
     }
     if (tid == 9) {
         *out.key = ok ? kwin : 0ull;
-        if (out.fo) out.fo->valid = ok ? 1 : 0;
+        if (MODEL::SHARD_OUT && out.fo) out.fo->valid = ok ? 1 : 0;
     }
     float fw[9];
 #pragma unroll
@@ -685,7 +718,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         for (int slot = wave; slot < kslots; slot += RL_WAVES) {
             const f32x2* pp = s_pts + static_cast<size_t>(slot) * 256 + lane;
             bool ia, ib;
-            inlier32_x2_flags<KIND>(fw, pp[0], pp[64], pp[128], pp[192], thr2, ia, ib);
+            MODEL::inlier_x2(fw, pp[0], pp[64], pp[128], pp[192], thr2, ia, ib);
             ia = ia && ok; ib = ib && ok;
             const int i0 = t * tile_pts + 2 * (64 * slot + lane);
             if (i0 < out.mask_len) out.mask[i0] = ia ? 1 : 0;
@@ -702,7 +735,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
 #pragma unroll
         for (int w = 0; w < RL_WAVES; ++w) tot += s_wc[w];
         if (out.n_inliers) *out.n_inliers = tot;
-        if (out.fo) out.fo->n_inliers = tot;
+        if (MODEL::SHARD_OUT && out.fo) out.fo->n_inliers = tot;
     }
     DIAG::phase(8);
     DIAG::phase(9);
@@ -724,6 +757,30 @@ int sync_words(pm_ctx* ctx, int** out)
         PM_HIP_CHECK(hipMemsetAsync(ctx->sync_words, 0, 256, ctx->stream));
     }
     *out = ctx->sync_words;
+    return PM_OK;
+}
+
+// Enqueue the LDS form (ransac_fused_lds) for MODEL: tile sizing, the dynamic-LDS attribute (once per instantiation and
+// device) and the launch.  The caller carves the nwg slots, fills `out` and times the launch.
+template <typename MODEL, typename DIAG>
+int fused_lds_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int nwg, int hb, RfSlot* slots,
+                     int* ticket, const RfOut& out)
+{
+    const long long cap_total = static_cast<long long>(v.parts) * v.cap;
+    const long long need = (cap_total + RL_SLOT_PTS - 1) / RL_SLOT_PTS;
+    const int tile_slots = static_cast<int>(need < 1 ? 1 : (need > RL_MAX_SLOTS ? RL_MAX_SLOTS : need));
+    const size_t lds = static_cast<size_t>(tile_slots) * 4 * 64 * sizeof(f32x2);
+    static bool attr_done_dev[PM_MAX_DEVICES] = {};
+    if (!attr_done_dev[ctx->device]) {
+        PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ransac_fused_lds<MODEL, DIAG>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         RL_MAX_SLOTS * 4 * 64 * static_cast<int>(sizeof(f32x2))));
+        attr_done_dev[ctx->device] = true;
+    }
+    const float thr2 = p->thresh_px * p->thresh_px;
+    hipLaunchKernelGGL((ransac_fused_lds<MODEL, DIAG>), dim3(nwg), dim3(RL_THREADS), lds, ctx->stream, v, p->seed, p->hyp_begin,
+                       static_cast<int>(p->hyp_end - p->hyp_begin), hb, thr2, tile_slots, slots, ticket, out);
+    PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
 }
 
@@ -757,26 +814,8 @@ int fused_launch_t(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params*
     // PM_OPT_RANSAC_FORM: 1 = correspondences in registers, two teams (round 2), 2 = correspondences in LDS, one wave per
     // hypothesis (round 3, the default)
     if (ctx->opts[PM_OPT_RANSAC_FORM] != 1) {
-        long long need = (cap_total + RL_SLOT_PTS - 1) / RL_SLOT_PTS;
-        const int tile_slots = static_cast<int>(need < 1 ? 1 : (need > RL_MAX_SLOTS ? RL_MAX_SLOTS : need));
-        const size_t lds = static_cast<size_t>(tile_slots) * 4 * 64 * sizeof(f32x2);
-        static bool attr_done_dev[PM_MAX_DEVICES] = {};
-        if (!attr_done_dev[ctx->device]) {
-            const int lmax = RL_MAX_SLOTS * 4 * 64 * static_cast<int>(sizeof(f32x2));
-            PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ransac_fused_lds<PM_ERR_SAMPSON, DIAG>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lmax));
-            PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ransac_fused_lds<PM_ERR_SYM_EPIPOLAR, DIAG>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, lmax));
-            attr_done_dev[ctx->device] = true;
-        }
-        if (p->error_kind == PM_ERR_SAMPSON)
-            hipLaunchKernelGGL((ransac_fused_lds<PM_ERR_SAMPSON, DIAG>), dim3(nwg), dim3(RL_THREADS), lds, ctx->stream, v, p->seed,
-                               p->hyp_begin, static_cast<int>(nh), hb, thr2, tile_slots, slots, sync, out);
-        else
-            hipLaunchKernelGGL((ransac_fused_lds<PM_ERR_SYM_EPIPOLAR, DIAG>), dim3(nwg), dim3(RL_THREADS), lds, ctx->stream, v, p->seed,
-                               p->hyp_begin, static_cast<int>(nh), hb, thr2, tile_slots, slots, sync, out);
-        PM_HIP_CHECK(hipGetLastError());
-        return PM_OK;
+        if (p->error_kind == PM_ERR_SAMPSON) return fused_lds_launch<FModel<PM_ERR_SAMPSON>, DIAG>(ctx, v, p, nwg, hb, slots, sync, out);
+        return fused_lds_launch<FModel<PM_ERR_SYM_EPIPOLAR>, DIAG>(ctx, v, p, nwg, hb, slots, sync, out);
     }
     // 2*RF_PPT2 points per thread: a 2560-point tile (config C3 fits one); small capacities take the 2-slot build
 #define PM_RF(KIND_, PPT2_)                                                                                              \

@@ -1,5 +1,6 @@
 // ransac_internal.hpp — entry points of ransac_fused.hip used by the C-ABI functions in ransac.hip (host-pointer
-// and device-resident single-shard runs) and by the multi-GPU driver (mgpu.cpp).
+// and device-resident single-shard runs) and by the multi-GPU driver (mgpu.cpp), and of ransac_h_fused.hip used by
+// homography_refine.hip.
 #pragma once
 #include "ransac_core.hpp"
 
@@ -10,5 +11,11 @@ int fused_hb(const pm_ctx* ctx, long long nh);
 size_t fused_scratch_bytes(const pm_ctx* ctx, const pm_ransac_params* p);
 int fused_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int shard, pm_ransac_record* d_rec,
                  unsigned long long* d_key, double* d_F, uint8_t* d_mask, int mask_len, int* d_ninl, FinalOut** fo_out);
+
+// Host side of the RANSAC-H launch (ransac_h_fused.hip), for pm_ransac_homography_refined: the argument check and the
+// enqueue itself (no synchronisation; the arena must hold fused_scratch_bytes() more, as for pm_ransac_homography).
+int ransac_h_check(const pm_ransac_params* p);
+int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
+                     double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
 
 }  // namespace pm_ransac
