@@ -125,7 +125,10 @@ __device__ __forceinline__ bool solve4(const double (&x1)[4], const double (&y1)
     return denormalise(hn, s1, t1x, t1y, s2, t2x, t2y, H);
 }
 
-// SPEC S21: fp32 one-way reprojection test of one correspondence against h = H32.  w == 0 and NaN are outliers.
+// SPEC S21: fp32 one-way reprojection test of one correspondence against h = H32.  Outliers: NaN, and a right side
+// thr2 * w^2 that is 0 (w == 0) or +inf (a huge coordinate overflows both sides, and inf <= inf would hold).
+// 0 < rhs < inf is one v_cmp_class (positive subnormal or normal), as cheap as the w != 0 it replaces.
+constexpr int CLASS_POS_FINITE = 0x180;
 __device__ __forceinline__ bool inlier_h32(const float (&h)[9], float x, float y, float xp, float yp, float thr2)
 {
     const float u = fmaf(h[0], x, fmaf(h[1], y, h[2]));
@@ -133,7 +136,8 @@ __device__ __forceinline__ bool inlier_h32(const float (&h)[9], float x, float y
     const float w = fmaf(h[6], x, fmaf(h[7], y, h[8]));
     const float du = fmaf(-xp, w, u);
     const float dv = fmaf(-yp, w, v);
-    return (fmaf(du, du, dv * dv) <= thr2 * (w * w)) && (w != 0.f);
+    const float rhs = thr2 * (w * w);
+    return (fmaf(du, du, dv * dv) <= rhs) && __builtin_amdgcn_classf(rhs, CLASS_POS_FINITE);
 }
 
 // SPEC S21 on two correspondences: the packed-f32 form of inlier_h32 (IEEE per component, same bits).
@@ -149,8 +153,8 @@ __device__ __forceinline__ void inlier_h32_x2(const float (&h)[9], f32x2 x, f32x
     const f32x2 du = __builtin_elementwise_fma(-xp, w, u);
     const f32x2 dv = __builtin_elementwise_fma(-yp, w, v);
     const f32x2 lhs = __builtin_elementwise_fma(du, du, dv * dv);
-    ia = (lhs[0] <= rhs[0]) && (w[0] != 0.f);
-    ib = (lhs[1] <= rhs[1]) && (w[1] != 0.f);
+    ia = (lhs[0] <= rhs[0]) && __builtin_amdgcn_classf(rhs[0], CLASS_POS_FINITE);
+    ib = (lhs[1] <= rhs[1]) && __builtin_amdgcn_classf(rhs[1], CLASS_POS_FINITE);
 }
 
 }  // namespace pm_homog

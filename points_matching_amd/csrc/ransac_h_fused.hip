@@ -56,8 +56,8 @@ struct HModel {
         const f32x2 dv = __builtin_elementwise_fma(-yp, w, v);
         const f32x2 lhs = __builtin_elementwise_fma(du, du, dv * dv);
         const f32x2 rhs = f32x2{thr2, thr2} * (w * w);
-        ia = (lhs[0] <= rhs[0]) && (w[0] != 0.f);
-        ib = (lhs[1] <= rhs[1]) && (w[1] != 0.f);
+        ia = (lhs[0] <= rhs[0]) && __builtin_amdgcn_classf(rhs[0], CLASS_POS_FINITE);
+        ib = (lhs[1] <= rhs[1]) && __builtin_amdgcn_classf(rhs[1], CLASS_POS_FINITE);
     }
 
     static __device__ __forceinline__ void inlier_x2(const float (&h)[9], f32x2 x, f32x2 y, f32x2 xp, f32x2 yp, float thr2,

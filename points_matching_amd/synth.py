@@ -225,3 +225,53 @@ def planar_view(n, seed=0xC5, outlier_frac=0.3, noise_px=0.5, width=993, height=
         inl[bad] = False
         x2[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl
+
+
+def planar_view_wide(n, seed=0, width=4000, height=3000, angle=None, persp=0.8, pp_offset=(0.0, 0.0), noise_px=0.5,
+                     outlier_frac=0.3, w_min=0.05):
+    """planar_view at hard geometry: images up to 16000 px wide, any rotation, strong perspective.
+
+    Built about the principal point c1 = image centre + pp_offset: x2 - c2 ~ A (x1 - c1), A = [[s R, t], [g, h, 1]] with
+    R a rotation by `angle` radians (None: uniform in [-pi, pi)), s in [0.7, 1.4], |t| up to width / 20 and the
+    perspective row (g, h) of random direction scaled so that |g dx + h dy| reaches `persp` at the farthest image
+    corner: the true w = 1 + g dx + h dy spans about [1 - persp, 1 + persp] over image 1 (0.8: 0.2 to 1.8, a 9x
+    change of scale).  Pairs whose true w is at or below `w_min` (behind or at the vanishing line) are redrawn.  Image-2
+    points may lie far outside the image; outliers are uniform over the bounding box of the true image-2 points.
+
+    Returns xy1, xy2 (n x 2 float32 pixels), H_gt (3x3 float64, x2 ~ H x1, unit Frobenius norm, H[2,2] > 0) and the
+    boolean ground-truth inlier flags, as planar_view does.
+    """
+    rng = np.random.default_rng([seed, 0x4818])
+    a = rng.uniform(-np.pi, np.pi) if angle is None else float(angle)
+    sc = rng.uniform(0.7, 1.4)
+    c1 = np.array([width / 2.0 + pp_offset[0], height / 2.0 + pp_offset[1]])
+    c2 = np.array([width / 2.0, height / 2.0])
+    corners = np.array([[0, 0], [width, 0], [0, height], [width, height]], np.float64) - c1
+    d = rng.normal(size=2)
+    d /= np.linalg.norm(d)
+    g = d * (persp / np.abs(corners @ d).max())
+    A = np.array([[sc * np.cos(a), -sc * np.sin(a), rng.uniform(-width / 20.0, width / 20.0)],
+                  [sc * np.sin(a), sc * np.cos(a), rng.uniform(-width / 20.0, width / 20.0)],
+                  [g[0], g[1], 1.0]])
+    C1 = np.array([[1.0, 0, -c1[0]], [0, 1.0, -c1[1]], [0, 0, 1.0]])
+    C2 = np.array([[1.0, 0, c2[0]], [0, 1.0, c2[1]], [0, 0, 1.0]])
+    H = C2 @ A @ C1
+    x1 = np.zeros((0, 2))
+    while x1.shape[0] < n:
+        c = rng.uniform([0, 0], [width, height], (2 * n + 16, 2))
+        x1 = np.concatenate([x1, c[(c - c1) @ g + 1.0 > w_min]])
+    x1 = x1[:n]
+    p = np.column_stack([x1, np.ones(n)]) @ H.T
+    x2 = p[:, :2] / p[:, 2:3]
+    H = H / np.linalg.norm(H)
+    if H[2, 2] < 0:
+        H = -H
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform(x2[inl].min(axis=0), x2[inl].max(axis=0), (n_out, 2))
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl

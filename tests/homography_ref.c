@@ -157,7 +157,8 @@ int hr_inlier(const float h[9], float x, float y, float xp, float yp, float thr2
     const float w = fmaf(h[6], x, fmaf(h[7], y, h[8]));
     const float du = fmaf(-xp, w, u);
     const float dv = fmaf(-yp, w, v);
-    return (fmaf(du, du, dv * dv) <= thr2 * (w * w)) && (w != 0.f);
+    const float rhs = thr2 * (w * w);
+    return (fmaf(du, du, dv * dv) <= rhs) && (rhs > 0.f) && (rhs < INFINITY);
 }
 
 /* S21 over all n with the f32 rounding of H; mask may be NULL; returns the inlier count */
