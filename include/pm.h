@@ -69,7 +69,7 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
  * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
- * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine". */
+ * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -424,6 +424,56 @@ int pm_homography_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint
 int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
                                  int max_iters, double H[9], uint8_t* mask, int* n_inliers, uint64_t* best_key,
                                  pm_h_refine_info* info);
+
+/* ---- robust 2D affine and similarity (cv::estimateAffine2D / cv::estimateAffinePartial2D with RANSAC: the
+ * alignment models of document scans, aerial mosaics and video stabilisation, where the perspective part of an H is
+ * noise) — docs/SPEC.md S26-S30.  One family, the model chosen by `model`:
+ *   PM_AFFINE_FULL     6 DOF, x2 = A [x1 y1 1]^T with A = [a0 a1 a2; a3 a4 a5], 3-point samples (estimateAffine2D);
+ *   PM_AFFINE_PARTIAL  4 DOF, A = [a -b tx; b a ty] (rotation, uniform scale, translation), 2-point samples
+ *                      (estimateAffinePartial2D).
+ * pm_ransac_params as for the homography: error_kind = PM_ERR_REPROJ only, ids [hyp_begin, hyp_end) non-empty.  Every
+ * hypothesis h: sample MIN_PTS = 3 (full) or 2 (partial) correspondences on a stream of the model's own (S26), solve
+ * the minimal system in fp64 (S27; a full sample is invalid when its 3 points are collinear in either image, a partial
+ * one when its 2 points coincide in either image), score ALL n correspondences with ||x2 - A x1||^2 <= thresh_px^2 in
+ * fp32 (S28), count inliers.  Winner: most inliers, ties -> lowest h (S29).  A: 6 doubles, 2 x 3 row-major (OpenCV's
+ * layout).  pm_affine_refine* then refit A on the inliers by closed-form least squares (S30), pm_estimate_affine does
+ * both.  Graph capture: as the homography calls (no per-call state; the host forms synchronise). */
+enum { PM_AFFINE_FULL = 0, PM_AFFINE_PARTIAL = 1 };
+/* Host in, host out (mirrors pm_ransac_homography).  mask (n bytes), n_inliers, best_key may be NULL.
+ * Statuses: PM_E_INVALID (model not PM_AFFINE_*, null params or points, bad range, error_kind != PM_ERR_REPROJ, null
+ * ctx), n < MIN_PTS -> PM_E_TOO_FEW, all hypotheses invalid -> PM_E_NO_MODEL with A = 0, mask = 0 (*best_key = 0). */
+int pm_ransac_affine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
+                     double A[6], uint8_t* mask, int* n_inliers, uint64_t* best_key);
+/* A, mask and inlier count of ONE hypothesis id (0 <= hyp < 2^32; p's hypothesis range is ignored): the same launch
+ * over [hyp, hyp + 1).  An invalid sample -> PM_E_NO_MODEL with A = 0, mask = 0. */
+int pm_ransac_affine_from_hyp(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n,
+                              const pm_ransac_params* p, int64_t hyp, double A[6], uint8_t* mask, int* n_inliers);
+/* Whole run on the device over a correspondence view, as pm_ransac_homography_run_dev: chains after
+ * pm_filter_ratio_gather_dev / pm_bf_knn_l2_*_ratio_dev with no host round trip.  Writes *d_best_key, d_A (6
+ * doubles), d_mask[0..mask_len) (zero beyond n) and *d_n_inliers; n < MIN_PTS or no valid model leaves key 0, A = 0,
+ * mask = 0, count 0.  All four output pointers are required. */
+int pm_ransac_affine_run_dev(pm_ctx* ctx, int model, const pm_points_view* view, const pm_ransac_params* p,
+                             uint64_t* d_best_key, double* d_A, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers);
+/* Least-squares refit of A on the correspondences with mask[i] != 0 (what estimateAffine2D's Levenberg-Marquardt
+ * refinement converges to [recalled]: the costs are quadratic, so the minimiser of sum ||x2 - A x1||^2 is closed-form;
+ * S30).  Sums in S23's fixed order; the refit is kept only if its cost is not higher than A_in's, so
+ * cost_out <= cost_in.  The mask is not recomputed.  Info: pm_h_refine_info with iters = 0; status 0 = refitted,
+ * 1 = kept A_in (fewer than MIN_PTS inliers, degenerate normal system or no gain; A_out = A_in bit for bit), 2 = A_in
+ * is zero (no model).  Host in, host out; A_out may alias A_in; info may be NULL.
+ * Statuses: PM_E_INVALID (bad model, null arrays, null ctx), n < MIN_PTS -> PM_E_TOO_FEW (A_out = A_in),
+ * A_in zero -> PM_E_NO_MODEL (status 2).  One launch of one workgroup. */
+int pm_affine_refine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const uint8_t* mask,
+                     const double A_in[6], double A_out[6], pm_h_refine_info* info);
+/* Device form over a view (count read on the device): chains after pm_ransac_affine_run_dev with no host round trip.
+ * d_A_out may equal d_A_in; d_info may be NULL; data outcomes are reported in *d_info only. */
+int pm_affine_refine_dev(pm_ctx* ctx, int model, const pm_points_view* view, const uint8_t* d_mask, const double* d_A_in,
+                         double* d_A_out, pm_h_refine_info* d_info);
+/* Convenience: cv::estimateAffine2D / estimateAffinePartial2D in one call — pm_ransac_affine, then (refine != 0) the
+ * refit, one synchronisation.  mask/n_inliers/best_key as the RANSAC call (the RANSAC mask).  info (may be NULL): the
+ * refit's; with refine == 0 it is zero but for status (1, or 2 without a model).  Statuses as pm_ransac_affine. */
+int pm_estimate_affine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
+                       int refine, double A[6], uint8_t* mask, int* n_inliers, uint64_t* best_key,
+                       pm_h_refine_info* info);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

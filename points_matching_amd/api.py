@@ -22,7 +22,9 @@ PM_KNN_HINT_U8 = 8
 PM_KNN_HINT_UNIT_NORM = 16
 PM_ERR_SAMPSON = 0
 PM_ERR_SYM_EPIPOLAR = 1
-PM_ERR_REPROJ = 2          # robust homography (pm_ransac_homography*)
+PM_ERR_REPROJ = 2          # robust homography and affine (pm_ransac_homography*, pm_ransac_affine*)
+PM_AFFINE_FULL = 0         # 6 DOF (cv::estimateAffine2D)
+PM_AFFINE_PARTIAL = 1      # 4 DOF: rotation, uniform scale, translation (cv::estimateAffinePartial2D)
 PM_OK, PM_E_INVALID, PM_E_TOO_FEW, PM_E_NO_MODEL, PM_E_HIP, PM_E_NOMEM, PM_E_UNSUPPORTED = \
     0, -1, -2, -3, -4, -5, -6
 
@@ -50,6 +52,8 @@ EXPORTS = [
     "pm_epipolar_residuals", "pm_f_scale_f33", "pm_epilines", "pm_epiline_endpoints",
     "pm_ransac_homography", "pm_ransac_homography_run_dev", "pm_ransac_homography_from_hyp",
     "pm_homography_refine", "pm_homography_refine_dev", "pm_ransac_homography_refined",
+    "pm_ransac_affine", "pm_ransac_affine_from_hyp", "pm_ransac_affine_run_dev", "pm_affine_refine", "pm_affine_refine_dev",
+    "pm_estimate_affine",
 ]
 
 
@@ -510,6 +514,85 @@ class Context:
             _check(rc)
         return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value, info
 
+
+    # -- robust 2D affine / similarity (cv::estimateAffine2D / estimateAffinePartial2D, SPEC S26-S30) -------------------
+    # model: PM_AFFINE_FULL (6 DOF) or PM_AFFINE_PARTIAL (4 DOF).  A is returned as a 2 x 3 float64 array.
+    def ransac_affine(self, xy1, xy2, iters, thresh_px, seed, model=PM_AFFINE_FULL, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """Hypotheses [hyp_begin, iters).  Returns (status, A(2x3), mask, n_inliers, best_key); raises on anything other
+        than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        A = np.zeros(6, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        rc = lib().pm_ransac_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), _p(A), _p(mask), C.byref(ninl),
+                                    C.byref(key))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, A.reshape(2, 3), mask[:n], ninl.value, key.value
+
+    def ransac_affine_from_hyp(self, xy1, xy2, hyp, thresh_px, seed, model=PM_AFFINE_FULL, kind=PM_ERR_REPROJ):
+        """A, mask and count of one hypothesis id: (status, A(2x3), mask, n_inliers)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(0, 0, seed, thresh_px, kind)
+        A = np.zeros(6, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl = C.c_int()
+        rc = lib().pm_ransac_affine_from_hyp(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp), _p(A),
+                                             _p(mask), C.byref(ninl))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, A.reshape(2, 3), mask[:n], ninl.value
+
+    def ransac_affine_run_dev(self, view, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dA_ptr, dmask_ptr, mask_len,
+                              dninl_ptr, model=PM_AFFINE_FULL, kind=PM_ERR_REPROJ):
+        """Device-resident run over a PointsView (count read on the device); outputs are device pointers (A: 6 doubles)."""
+        prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)
+        _check(lib().pm_ransac_affine_run_dev(self._h, model, C.byref(view), C.byref(prm), C.c_void_p(dkey_ptr),
+                                              C.c_void_p(dA_ptr), C.c_void_p(dmask_ptr), mask_len, C.c_void_p(dninl_ptr)))
+
+    def affine_refine(self, xy1, xy2, mask, A_in, model=PM_AFFINE_FULL):
+        """Least-squares refit on the inliers: (status, A(2x3), HRefineInfo); raises on anything other than PM_OK /
+        PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n or xy2.shape[0] != n:
+            raise ValueError("xy1, xy2 and mask must have the same length")
+        Ain = np.ascontiguousarray(A_in, np.float64).reshape(6)
+        A = np.zeros(6, np.float64)
+        info = HRefineInfo()
+        rc = lib().pm_affine_refine(self._h, model, _p(xy1), _p(xy2), n, _p(mask), _p(Ain), _p(A), C.byref(info))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, A.reshape(2, 3), info
+
+    def affine_refine_dev(self, view, dmask_ptr, dAin_ptr, dAout_ptr, dinfo_ptr=None, model=PM_AFFINE_FULL):
+        """Device form over a PointsView; dinfo_ptr (32 bytes, H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_affine_refine_dev(self._h, model, C.byref(view), C.c_void_p(dmask_ptr), C.c_void_p(dAin_ptr),
+                                          C.c_void_p(dAout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def estimate_affine(self, xy1, xy2, iters, thresh_px, seed, model=PM_AFFINE_FULL, refine=True, hyp_begin=0,
+                        kind=PM_ERR_REPROJ):
+        """RANSAC-A + (refine) refit, one synchronisation: (status, A(2x3), mask, n_inliers, best_key, HRefineInfo)."""
+        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+        n = xy1.shape[0]
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        A = np.zeros(6, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = lib().pm_estimate_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), 1 if refine else 0, _p(A),
+                                      _p(mask), C.byref(ninl), C.byref(key), C.byref(info))
+        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+            _check(rc)
+        return rc, A.reshape(2, 3), mask[:n], ninl.value, key.value, info
 
 class LmedsParams(C.Structure):
     _fields_ = [("hyp_begin", C.c_int64), ("hyp_end", C.c_int64), ("seed", C.c_uint64)]

@@ -17,12 +17,13 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
-           "ransac_h_fused.hip", "homography_refine.hip",
+           "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
-         "homography_refine.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "homography_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "affine_refine.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

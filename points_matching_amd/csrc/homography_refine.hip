@@ -15,6 +15,7 @@
 #include "homography_core.hpp"
 #include "homography_refine_core.hpp"
 #include "ransac_fused_kernels.hpp"
+#include "refine_reduce.hpp"
 
 namespace pm_hrefine {
 namespace {
@@ -23,65 +24,6 @@ using pm_homog::denormalise;
 using pm_ransac::scale_sign;
 using pm_ransac::view_count1;
 using pm_ransac::view_offsets;
-using pm_ransac::view_point;
-
-// S23 tree over the threads' partials: for s = 256, ..., 1: part[p] += part[p + s] for p < s.  out[k] (LDS) = the sum,
-// visible to every thread on return.
-template <int K>
-__device__ __forceinline__ void tree(double (&acc)[K], int tid, double (*s_x)[HR_P / 2], double* out)
-{
-#pragma unroll
-    for (int c0 = 0; c0 < K; c0 += HR_CH) {
-#pragma unroll
-        for (int s = HR_P / 2; s >= 64; s >>= 1) {
-            if (tid >= s && tid < 2 * s) {
-#pragma unroll
-                for (int c = 0; c < HR_CH; ++c)
-                    if (c0 + c < K) s_x[c][tid - s] = acc[c0 + c];
-            }
-            __syncthreads();
-            if (tid < s) {
-#pragma unroll
-                for (int c = 0; c < HR_CH; ++c)
-                    if (c0 + c < K) acc[c0 + c] = acc[c0 + c] + s_x[c][tid];
-            }
-            __syncthreads();
-        }
-    }
-    if (tid < 64) {
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1)
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc[k] = acc[k] + __shfl_down(acc[k], s, 64);
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) out[k] = acc[k];
-        }
-    }
-    __syncthreads();
-}
-
-// One pass: term(acc, x1, y1, x2, y2) over the inliers i = tid, tid + HR_P, ... < n, then the tree into out[0..K).
-template <int K, typename Term>
-__device__ __forceinline__ void pass(const pm_points_view& v, const int* offs, int n, const uint8_t* mask, int tid,
-                                     double (*s_x)[HR_P / 2], double* out, Term term)
-{
-    double acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += HR_P) {
-        if (!mask[i]) continue;
-        float2 a, b;
-        if (v.parts == 1) {
-            a = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(i));
-            b = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(i));
-        } else {
-            view_point(v, offs, i, a, b);
-        }
-        term(acc, static_cast<double>(a.x), static_cast<double>(a.y), static_cast<double>(b.x), static_cast<double>(b.y));
-    }
-    tree<K>(acc, tid, s_x, out);
-}
 
 __global__ __launch_bounds__(HR_P) void homography_refine(pm_points_view v, const uint8_t* mask, const double* H_in,
                                                           int max_iters, double* H_out, pm_h_refine_info* info)

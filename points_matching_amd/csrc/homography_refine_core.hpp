@@ -7,11 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "pm.h"
+#include "refine_reduce.hpp"
 
 namespace pm_hrefine {
 
-constexpr int HR_P = 512;                 // S23: partials = threads of the one workgroup
-constexpr int HR_CH = 16;                 // accumulators per LDS round of the cross-wave tree steps
 constexpr int HR_NORMAL = 45;             // unique entries of the 9 x 9 normal matrix
 constexpr int HR_LM = 45;                 // 36 of J^T J, 8 of J^T r, the cost
 constexpr int HR_SWEEPS = 16;             // S23 Jacobi sweep cap

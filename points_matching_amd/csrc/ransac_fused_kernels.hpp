@@ -21,7 +21,7 @@
 // of a query-row-sharded matcher): the view is resolved while loading, no concatenation pass exists.
 //
 // Everything here is templated on a diagnostics policy (ransac_core.hpp: NoDiag); the LDS form below is also templated on
-// a model policy (FModel here, HModel in csrc/ransac_h_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
+// a model policy (FModel here, HModel in csrc/ransac_h_fused.hip, AModel in csrc/ransac_a_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
 // (the product launch: NoDiag, nothing else instantiated) and tools/ablation/ransac_fused_stamps.hip (a diagnostic launch
 // with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).  csrc/ransac_h_fused.hip
 // instantiates the LDS form for the homography; csrc/ransac_shard.hip (finish kernel + the sharded C-ABI entry points)
@@ -196,17 +196,20 @@ __device__ __forceinline__ void inlier_pk_model(const ModelS& m, f32x2 x, f32x2 
 }
 
 // Model policy of the LDS one-launch kernel (ransac_fused_lds): the fundamental matrix with error KIND (SPEC S6-S8).
-// The homography policy, HModel, lives in ransac_h_fused.hip.  A policy supplies
+// The homography policy, HModel, lives in ransac_h_fused.hip, the affine ones, AModel, in ransac_a_fused.hip.  A policy
+// supplies
 //   MIN_PTS             the minimal sample size (fewer correspondences: no valid model);
 //   solve<DIAG>         the sample and fp64 solve of hypothesis h by one lane;
 //   inlier_pk           the packed test of two correspondences, model in SGPR pairs (score phase);
 //   inlier_x2           the same test, model in VGPRs (mask phase);
 //   SHARD_OUT           whether the run may end in a shard record (out.shard) or a result block (out.fo).  Without
-//                       them the tail carries no tests of either (measured: ~0.4 us at 512-2275 correspondences).
+//                       them the tail carries no tests of either (measured: ~0.4 us at 512-2275 correspondences);
+//   OUT_WORDS           the doubles of the published model out.F (9; the 2 x 3 affine models of ransac_a_fused.hip: 6).
 template <int KIND>
 struct FModel {
     static constexpr int MIN_PTS = 8;
     static constexpr bool SHARD_OUT = true;
+    static constexpr int OUT_WORDS = 9;
     template <typename DIAG>
     static __device__ __forceinline__ bool solve(const pm_points_view& v, const int* __restrict__ offs, int n, uint64_t seed,
                                                  uint64_t h, double (&F)[9])
@@ -697,7 +700,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         return;
     }
     if (tid < 9) {
-        if (out.F) out.F[tid] = s_F64[tid];
+        if (out.F && (MODEL::OUT_WORDS == 9 || tid < MODEL::OUT_WORDS)) out.F[tid] = s_F64[tid];
         if (MODEL::SHARD_OUT && out.fo) { out.fo->F[tid] = s_F64[tid]; out.fo->F32[tid] = static_cast<float>(s_F64[tid]); }
     }
     if (tid == 9) {

@@ -25,6 +25,7 @@ constexpr int RH_SYNC_WORD = 8;       // arrival ticket in ctx->sync_words (RANS
 struct HModel {
     static constexpr int MIN_PTS = 4;
     static constexpr bool SHARD_OUT = false;               // key, H, mask and count only
+    static constexpr int OUT_WORDS = 9;
 
     // SPEC S19, S20: sample and solve hypothesis h.
     template <typename DIAG>

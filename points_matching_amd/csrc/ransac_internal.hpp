@@ -1,6 +1,6 @@
 // ransac_internal.hpp — entry points of ransac_fused.hip used by the C-ABI functions in ransac.hip (host-pointer
-// and device-resident single-shard runs) and by the multi-GPU driver (mgpu.cpp), and of ransac_h_fused.hip used by
-// homography_refine.hip.
+// and device-resident single-shard runs) and by the multi-GPU driver (mgpu.cpp), of ransac_h_fused.hip used by
+// homography_refine.hip, and of the affine pair ransac_a_fused.hip / affine_refine.hip used by each other.
 #pragma once
 #include "ransac_core.hpp"
 
@@ -17,5 +17,13 @@ int fused_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p
 int ransac_h_check(const pm_ransac_params* p);
 int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
                      double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
+
+// The affine family (ransac_a_fused.hip, affine_refine.hip): the model check and sample size every affine entry point
+// uses (ransac_a_fused.hip), and the enqueue of the refit (affine_refine.hip; no synchronisation, no per-call state),
+// which pm_estimate_affine runs after RANSAC-A on the same stream.
+int ransac_a_check_model(int model);
+int ransac_a_min_pts(int model);
+int affine_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_A_in,
+                          double* d_A_out, pm_h_refine_info* d_info);
 
 }  // namespace pm_ransac

@@ -227,6 +227,38 @@ def planar_view(n, seed=0xC5, outlier_frac=0.3, noise_px=0.5, width=993, height=
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl
 
 
+def affine_view(n, seed=0xA5, outlier_frac=0.3, noise_px=0.5, partial=False, width=993, height=660):
+    """Correspondences of a 2D affine scene (a document scan, an aerial mosaic tile, a stabilised video frame): image-2
+    points are image-1 points mapped by a known affine map about the image centre, plus N(0, noise_px) in both images;
+    `outlier_frac` of the pairs get uniform-random image-2 positions.  The map is a rotation up to 10 degrees, scale
+    0.85-1.15 and a shift up to 40 px; unless `partial`, also anisotropic scale (0.9-1.1 per axis) and shear up to 0.1,
+    so that only the full 6-DOF model explains it.  `partial`: a similarity (rotation, uniform scale, translation).
+
+    Returns xy1, xy2 (n x 2 float32 pixels), A_gt (2 x 3 float64, x2 = A [x1 y1 1]^T) and the boolean ground-truth inlier
+    flags.
+    """
+    rng = np.random.default_rng([seed, 0xAFF1])
+    a = rng.uniform(-0.175, 0.175)
+    sc = rng.uniform(0.85, 1.15)
+    R = sc * np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+    if not partial:
+        R = R @ np.array([[rng.uniform(0.9, 1.1), rng.uniform(-0.1, 0.1)], [0.0, rng.uniform(0.9, 1.1)]])
+    c = np.array([width / 2.0, height / 2.0])
+    t = c + rng.uniform(-40, 40, 2) - R @ c
+    A = np.column_stack([R, t])
+    x1 = rng.uniform([0, 0], [width, height], (n, 2))
+    x2 = x1 @ R.T + t
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), A, inl
+
+
 def planar_view_wide(n, seed=0, width=4000, height=3000, angle=None, persp=0.8, pp_offset=(0.0, 0.0), noise_px=0.5,
                      outlier_frac=0.3, w_min=0.05):
     """planar_view at hard geometry: images up to 16000 px wide, any rotation, strong perspective.
