@@ -523,6 +523,8 @@ class Context:
         xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
         xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
         n = xy1.shape[0]
+        if xy2.shape[0] != n:
+            raise ValueError("xy1 and xy2 must have the same length")
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
@@ -538,6 +540,8 @@ class Context:
         xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
         xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
         n = xy1.shape[0]
+        if xy2.shape[0] != n:
+            raise ValueError("xy1 and xy2 must have the same length")
         prm = RansacParams(0, 0, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
@@ -583,6 +587,8 @@ class Context:
         xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
         xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
         n = xy1.shape[0]
+        if xy2.shape[0] != n:
+            raise ValueError("xy1 and xy2 must have the same length")
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)

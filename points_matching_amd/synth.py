@@ -307,3 +307,50 @@ def planar_view_wide(n, seed=0, width=4000, height=3000, angle=None, persp=0.8, 
         inl[bad] = False
         x2[bad] = rng.uniform(x2[inl].min(axis=0), x2[inl].max(axis=0), (n_out, 2))
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl
+
+
+def affine_view_wide(n, seed=0, width=4000, height=3000, angle=None, scale=None, aniso=None, shear=None, reflect=False,
+                     offset=(0.0, 0.0), noise_px=0.5, outlier_frac=0.3, partial=False):
+    """affine_view at hard geometry: images up to 16000 px wide, any rotation, scale 0.25-4, far from the origin.
+
+    x2 - c2 = M (x1 - c1) + t, with c1 = c2 = image centre + `offset` (mosaic or tile coordinates: 1e4-1e5 px puts
+    every coordinate far from the origin), |t| up to width / 20 and M = s R(angle) for `partial`.  Otherwise
+    M = s R(angle) diag(sqrt(k), 1 / sqrt(k)) [[1, shear], [0, 1]] R(beta) diag(1, -1 if reflect else 1): anisotropy
+    k (singular-value ratio about k for small shear), shear and a reflection.  None draws: angle and beta uniform in
+    [-pi, pi), s log-uniform in [0.25, 4], k uniform in [1, 3], shear uniform in [-0.3, 0.3].  Both images get
+    N(0, noise_px); `outlier_frac` of the pairs get image-2 points uniform over the bounding box of the true ones.
+
+    Returns xy1, xy2 (n x 2 float32 pixels), A_gt (2 x 3 float64, x2 = A [x1 y1 1]^T) and the boolean ground-truth inlier
+    flags, as affine_view does.
+    """
+    if partial and (reflect or (aniso not in (None, 1.0)) or (shear not in (None, 0.0))):
+        raise ValueError("a similarity has no anisotropy, shear or reflection")
+    rng = np.random.default_rng([seed, 0xAFF2])
+    a = rng.uniform(-np.pi, np.pi) if angle is None else float(angle)
+    s = float(np.exp(rng.uniform(np.log(0.25), np.log(4.0)))) if scale is None else float(scale)
+
+    def rot(t):
+        return np.array([[np.cos(t), -np.sin(t)], [np.sin(t), np.cos(t)]])
+
+    M = s * rot(a)
+    if not partial:
+        k = rng.uniform(1.0, 3.0) if aniso is None else float(aniso)
+        sh = rng.uniform(-0.3, 0.3) if shear is None else float(shear)
+        beta = rng.uniform(-np.pi, np.pi)
+        M = M @ np.diag([np.sqrt(k), 1.0 / np.sqrt(k)]) @ np.array([[1.0, sh], [0.0, 1.0]]) @ rot(beta)
+        if reflect:
+            M = M @ np.diag([1.0, -1.0])
+    c = np.array([width / 2.0 + offset[0], height / 2.0 + offset[1]])
+    t = c + rng.uniform(-width / 20.0, width / 20.0, 2) - M @ c
+    A = np.column_stack([M, t])
+    x1 = rng.uniform([offset[0], offset[1]], [offset[0] + width, offset[1] + height], (n, 2))
+    x2 = x1 @ M.T + t
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform(x2[inl].min(axis=0), x2[inl].max(axis=0), (n_out, 2))
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), A, inl
