@@ -137,6 +137,22 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _pair(xy1, xy2):
+    """Correspondences as contiguous float32 (n, 2) arrays, and n; raises ValueError unless both have n rows."""
+    xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
+    xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
+    if xy2.shape[0] != xy1.shape[0]:
+        raise ValueError("xy1 and xy2 must have the same length")
+    return xy1, xy2, xy1.shape[0]
+
+
+def _outcome(rc):
+    """rc when it is a data outcome (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW); raises PmError on anything else."""
+    if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
+        _check(rc)
+    return rc
+
+
 def ransac_key(inliers, hyp):
     return (int(inliers) << 32) | (0xFFFFFFFF - int(hyp))
 
@@ -439,32 +455,24 @@ class Context:
     def ransac_homography(self, xy1, xy2, iters, thresh_px, seed, hyp_begin=0, kind=PM_ERR_REPROJ):
         """Hypotheses [hyp_begin, iters).  Returns (status, H(3x3), mask, n_inliers, best_key); raises on anything other
         than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         H = np.zeros(9, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl, key = C.c_int(), C.c_uint64()
-        rc = lib().pm_ransac_homography(self._h, _p(xy1), _p(xy2), n, C.byref(prm), _p(H), _p(mask),
-                                        C.byref(ninl), C.byref(key))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_ransac_homography(self._h, _p(xy1), _p(xy2), n, C.byref(prm), _p(H), _p(mask),
+                                                 C.byref(ninl), C.byref(key)))
         return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value
 
     def ransac_homography_from_hyp(self, xy1, xy2, hyp, thresh_px, seed, kind=PM_ERR_REPROJ):
         """H, mask and count of one hypothesis id: (status, H(3x3), mask, n_inliers)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(0, 0, seed, thresh_px, kind)
         H = np.zeros(9, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl = C.c_int()
-        rc = lib().pm_ransac_homography_from_hyp(self._h, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp),
-                                                 _p(H), _p(mask), C.byref(ninl))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_ransac_homography_from_hyp(self._h, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp),
+                                                          _p(H), _p(mask), C.byref(ninl)))
         return rc, H.reshape(3, 3), mask[:n], ninl.value
 
     def ransac_homography_run_dev(self, view, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dH_ptr, dmask_ptr, mask_len,
@@ -478,19 +486,15 @@ class Context:
     # -- refinement of the robust H on its inliers (DLT refit + LM, SPEC S23-S25) ------------------------------------
     def homography_refine(self, xy1, xy2, mask, H_in, max_iters=10):
         """Returns (status, H(3x3), HRefineInfo); raises on anything other than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
+        xy1, xy2, n = _pair(xy1, xy2)
         mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        if mask.shape[0] != n or xy2.shape[0] != n:
+        if mask.shape[0] != n:
             raise ValueError("xy1, xy2 and mask must have the same length")
         Hin = np.ascontiguousarray(H_in, np.float64).reshape(9)
         H = np.zeros(9, np.float64)
         info = HRefineInfo()
-        rc = lib().pm_homography_refine(self._h, _p(xy1), _p(xy2), n, _p(mask), _p(Hin), max_iters, _p(H),
-                                        C.byref(info))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_homography_refine(self._h, _p(xy1), _p(xy2), n, _p(mask), _p(Hin), max_iters, _p(H),
+                                                 C.byref(info)))
         return rc, H.reshape(3, 3), info
 
     def homography_refine_dev(self, view, dmask_ptr, dHin_ptr, max_iters, dHout_ptr, dinfo_ptr=None):
@@ -500,18 +504,14 @@ class Context:
 
     def ransac_homography_refined(self, xy1, xy2, iters, thresh_px, seed, max_iters=10, hyp_begin=0, kind=PM_ERR_REPROJ):
         """RANSAC-H + refinement, one synchronisation: (status, H(3x3), mask, n_inliers, best_key, HRefineInfo)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         H = np.zeros(9, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl, key = C.c_int(), C.c_uint64()
         info = HRefineInfo()
-        rc = lib().pm_ransac_homography_refined(self._h, _p(xy1), _p(xy2), n, C.byref(prm), max_iters, _p(H), _p(mask),
-                                                C.byref(ninl), C.byref(key), C.byref(info))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_ransac_homography_refined(self._h, _p(xy1), _p(xy2), n, C.byref(prm), max_iters, _p(H),
+                                                         _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
         return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value, info
 
 
@@ -520,36 +520,24 @@ class Context:
     def ransac_affine(self, xy1, xy2, iters, thresh_px, seed, model=PM_AFFINE_FULL, hyp_begin=0, kind=PM_ERR_REPROJ):
         """Hypotheses [hyp_begin, iters).  Returns (status, A(2x3), mask, n_inliers, best_key); raises on anything other
         than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
-        if xy2.shape[0] != n:
-            raise ValueError("xy1 and xy2 must have the same length")
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl, key = C.c_int(), C.c_uint64()
-        rc = lib().pm_ransac_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), _p(A), _p(mask), C.byref(ninl),
-                                    C.byref(key))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_ransac_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), _p(A), _p(mask),
+                                             C.byref(ninl), C.byref(key)))
         return rc, A.reshape(2, 3), mask[:n], ninl.value, key.value
 
     def ransac_affine_from_hyp(self, xy1, xy2, hyp, thresh_px, seed, model=PM_AFFINE_FULL, kind=PM_ERR_REPROJ):
         """A, mask and count of one hypothesis id: (status, A(2x3), mask, n_inliers)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
-        if xy2.shape[0] != n:
-            raise ValueError("xy1 and xy2 must have the same length")
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(0, 0, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl = C.c_int()
-        rc = lib().pm_ransac_affine_from_hyp(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp), _p(A),
-                                             _p(mask), C.byref(ninl))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_ransac_affine_from_hyp(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), C.c_int64(hyp),
+                                                      _p(A), _p(mask), C.byref(ninl)))
         return rc, A.reshape(2, 3), mask[:n], ninl.value
 
     def ransac_affine_run_dev(self, view, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dA_ptr, dmask_ptr, mask_len,
@@ -562,18 +550,15 @@ class Context:
     def affine_refine(self, xy1, xy2, mask, A_in, model=PM_AFFINE_FULL):
         """Least-squares refit on the inliers: (status, A(2x3), HRefineInfo); raises on anything other than PM_OK /
         PM_E_NO_MODEL / PM_E_TOO_FEW."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
+        xy1, xy2, n = _pair(xy1, xy2)
         mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
-        if mask.shape[0] != n or xy2.shape[0] != n:
+        if mask.shape[0] != n:
             raise ValueError("xy1, xy2 and mask must have the same length")
         Ain = np.ascontiguousarray(A_in, np.float64).reshape(6)
         A = np.zeros(6, np.float64)
         info = HRefineInfo()
-        rc = lib().pm_affine_refine(self._h, model, _p(xy1), _p(xy2), n, _p(mask), _p(Ain), _p(A), C.byref(info))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_affine_refine(self._h, model, _p(xy1), _p(xy2), n, _p(mask), _p(Ain), _p(A),
+                                             C.byref(info)))
         return rc, A.reshape(2, 3), info
 
     def affine_refine_dev(self, view, dmask_ptr, dAin_ptr, dAout_ptr, dinfo_ptr=None, model=PM_AFFINE_FULL):
@@ -584,20 +569,14 @@ class Context:
     def estimate_affine(self, xy1, xy2, iters, thresh_px, seed, model=PM_AFFINE_FULL, refine=True, hyp_begin=0,
                         kind=PM_ERR_REPROJ):
         """RANSAC-A + (refine) refit, one synchronisation: (status, A(2x3), mask, n_inliers, best_key, HRefineInfo)."""
-        xy1 = np.ascontiguousarray(xy1, np.float32).reshape(-1, 2)
-        xy2 = np.ascontiguousarray(xy2, np.float32).reshape(-1, 2)
-        n = xy1.shape[0]
-        if xy2.shape[0] != n:
-            raise ValueError("xy1 and xy2 must have the same length")
+        xy1, xy2, n = _pair(xy1, xy2)
         prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
         A = np.zeros(6, np.float64)
         mask = np.zeros(max(n, 1), np.uint8)
         ninl, key = C.c_int(), C.c_uint64()
         info = HRefineInfo()
-        rc = lib().pm_estimate_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), 1 if refine else 0, _p(A),
-                                      _p(mask), C.byref(ninl), C.byref(key), C.byref(info))
-        if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_TOO_FEW):
-            _check(rc)
+        rc = _outcome(lib().pm_estimate_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), 1 if refine else 0,
+                                               _p(A), _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
         return rc, A.reshape(2, 3), mask[:n], ninl.value, key.value, info
 
 class LmedsParams(C.Structure):

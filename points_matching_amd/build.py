@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
-           "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
+           "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip", "planar_estimators.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],

@@ -8,7 +8,8 @@
 //   1. count, coordinate sums and the cost of A_in (6 sums);
 //   2. the centred second moments (7 sums full, 3 partial), then the 2 x 2 cofactor solve in every thread;
 //   3. the cost of the refit, which is kept only if it is not higher than A_in's.
-// The launch keeps no per-call state, so the device form may be captured; the host forms synchronise.
+// The launch keeps no per-call state, so the device form may be captured; the host forms (planar_estimators.cpp)
+// synchronise.
 #include "affine_core.hpp"
 #include "ransac_fused_kernels.hpp"
 #include "refine_reduce.hpp"
@@ -133,94 +134,18 @@ __global__ __launch_bounds__(HR_P) void affine_refine(pm_points_view v, const ui
     }
 }
 
-// Enqueue the launch (no synchronisation, no per-call state).
-int refine_launch(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_A_in,
-                  double* d_A_out, pm_h_refine_info* d_info)
+}  // namespace
+}  // namespace pm_arefine
+
+int pm_ransac::affine_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask,
+                                     const double* d_A_in, double* d_A_out, pm_h_refine_info* d_info)
 {
+    using namespace pm_arefine;
     pm::ScopedKernelTime t(ctx, "affine_refine");
     if (model == PM_AFFINE_FULL)
         hipLaunchKernelGGL(affine_refine<FULL>, dim3(1), dim3(HR_P), 0, ctx->stream, v, d_mask, d_A_in, d_A_out, d_info);
     else
         hipLaunchKernelGGL(affine_refine<PARTIAL>, dim3(1), dim3(HR_P), 0, ctx->stream, v, d_mask, d_A_in, d_A_out, d_info);
     PM_HIP_CHECK(hipGetLastError());
-    return PM_OK;
-}
-
-}  // namespace
-}  // namespace pm_arefine
-
-namespace pm_ransac {
-// for pm_estimate_affine (ransac_a_fused.hip): the refit after RANSAC-A on the same stream
-int affine_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_A_in,
-                          double* d_A_out, pm_h_refine_info* d_info)
-{
-    return pm_arefine::refine_launch(ctx, model, v, d_mask, d_A_in, d_A_out, d_info);
-}
-}  // namespace pm_ransac
-
-using namespace pm_arefine;
-
-extern "C" int pm_affine_refine_dev(pm_ctx* ctx, int model, const pm_points_view* view, const uint8_t* d_mask,
-                                    const double* d_A_in, double* d_A_out, pm_h_refine_info* d_info)
-{
-    PM_REQUIRE(d_mask && d_A_in && d_A_out, PM_E_INVALID, "null argument");
-    int rc = pm_ransac::ransac_a_check_model(model);
-    if (rc != PM_OK) return rc;
-    rc = pm_ransac::check_view(view);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return refine_launch(ctx, model, *view, d_mask, d_A_in, d_A_out, d_info);
-}
-
-extern "C" int pm_affine_refine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const uint8_t* mask,
-                                const double A_in[6], double A_out[6], pm_h_refine_info* info)
-{
-    PM_REQUIRE(A_in && A_out, PM_E_INVALID, "null A");
-    double ain[6];
-    memcpy(ain, A_in, sizeof ain);           // A_out may alias A_in
-    memcpy(A_out, ain, sizeof ain);
-    if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 1, 0};
-    int rc = pm_ransac::ransac_a_check_model(model);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2 && mask)), PM_E_INVALID, "bad point or mask arrays");
-    const int mp = pm_ransac::ransac_a_min_pts(model);
-    if (n < mp) { pm::set_error("need at least %d correspondences, got %d", mp, n); return PM_E_TOO_FEW; }
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
-    rc = pm::arena_reserve(ctx, 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 4 * 256);
-    if (rc != PM_OK) return rc;
-    pm::arena_reset(ctx);
-    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
-    double* dA = static_cast<double*>(pm::arena_take(ctx, sizeof ain));
-    pm_h_refine_info* dinfo = static_cast<pm_h_refine_info*>(pm::arena_take(ctx, sizeof(pm_h_refine_info)));
-    PM_REQUIRE(dxy1 && dxy2 && dmask && dA && dinfo, PM_E_NOMEM, "scratch arena too small");
-    constexpr size_t HP_INFO = 64;           // pinned layout: A (48) | pad | info (32)
-    rc = pm::pinned_reserve(ctx, HP_INFO + sizeof(pm_h_refine_info));
-    if (rc != PM_OK) return rc;
-    char* hp = static_cast<char*>(ctx->pinned);
-    memcpy(hp, ain, sizeof ain);
-    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dmask, mask, static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dA, hp, sizeof ain, hipMemcpyHostToDevice, ctx->stream));
-    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
-    rc = refine_launch(ctx, model, v, dmask, dA, dA, dinfo);
-    if (rc != PM_OK) return rc;
-    PM_HIP_CHECK(hipMemcpyAsync(hp, dA, sizeof ain, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hp + HP_INFO, dinfo, sizeof(pm_h_refine_info), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    pm_h_refine_info r;
-    memcpy(&r, hp + HP_INFO, sizeof r);
-    memcpy(A_out, hp, sizeof ain);
-    if (info) *info = r;
-    if (r.status == 2) {
-        pm::set_error("the input A is zero (no model)");
-        return PM_E_NO_MODEL;
-    }
     return PM_OK;
 }

@@ -11,7 +11,8 @@
 // Passes: sums + cost of H_in, centroid distances, normal matrix, cost of the refit, then the LM passes (one at the
 // start point, one per iteration).
 //
-// The launch keeps no per-call state, so the device form may be captured; the host forms synchronise.
+// The launch keeps no per-call state, so the device form may be captured; the host forms (planar_estimators.cpp)
+// synchronise.
 #include "homography_core.hpp"
 #include "homography_refine_core.hpp"
 #include "ransac_fused_kernels.hpp"
@@ -193,154 +194,15 @@ __global__ __launch_bounds__(HR_P) void homography_refine(pm_points_view v, cons
     }
 }
 
-int check_iters(int max_iters)
-{
-    PM_REQUIRE(max_iters >= 0 && max_iters <= 100, PM_E_INVALID, "max_iters must lie in [0, 100]");
-    return PM_OK;
-}
-
-// Enqueue the launch (no synchronisation, no per-call state).
-int refine_launch(pm_ctx* ctx, const pm_points_view& v, const uint8_t* d_mask, const double* d_H_in, int max_iters,
-                  double* d_H_out, pm_h_refine_info* d_info)
-{
-    pm::ScopedKernelTime t(ctx, "homography_refine");
-    hipLaunchKernelGGL(homography_refine, dim3(1), dim3(HR_P), 0, ctx->stream, v, d_mask, d_H_in, max_iters, d_H_out,
-                       d_info);
-    PM_HIP_CHECK(hipGetLastError());
-    return PM_OK;
-}
-
 }  // namespace
 }  // namespace pm_hrefine
 
-using namespace pm_hrefine;
-
-extern "C" int pm_homography_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask,
-                                        const double* d_H_in, int max_iters, double* d_H_out, pm_h_refine_info* d_info)
+int pm_ransac::homography_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const uint8_t* d_mask, const double* d_H_in,
+                                         int max_iters, double* d_H_out, pm_h_refine_info* d_info)
 {
-    PM_REQUIRE(d_mask && d_H_in && d_H_out, PM_E_INVALID, "null argument");
-    int rc = check_iters(max_iters);
-    if (rc != PM_OK) return rc;
-    rc = pm_ransac::check_view(view);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return refine_launch(ctx, *view, d_mask, d_H_in, max_iters, d_H_out, d_info);
-}
-
-extern "C" int pm_homography_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
-                                    const double H_in[9], int max_iters, double H_out[9], pm_h_refine_info* info)
-{
-    PM_REQUIRE(H_in && H_out, PM_E_INVALID, "null H");
-    double hin[9];
-    memcpy(hin, H_in, sizeof hin);           // H_out may alias H_in
-    memcpy(H_out, hin, sizeof hin);
-    if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 1, 0};
-    int rc = check_iters(max_iters);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2 && mask)), PM_E_INVALID, "bad point or mask arrays");
-    if (n < 4) { pm::set_error("need at least 4 correspondences, got %d", n); return PM_E_TOO_FEW; }
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
-    rc = pm::arena_reserve(ctx, 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 4 * 256);
-    if (rc != PM_OK) return rc;
-    pm::arena_reset(ctx);
-    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
-    double* dH = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 9));
-    pm_h_refine_info* dinfo = static_cast<pm_h_refine_info*>(pm::arena_take(ctx, sizeof(pm_h_refine_info)));
-    PM_REQUIRE(dxy1 && dxy2 && dmask && dH && dinfo, PM_E_NOMEM, "scratch arena too small");
-    constexpr size_t HP_INFO = 80;           // pinned layout: H (72) | pad | info (32)
-    rc = pm::pinned_reserve(ctx, HP_INFO + sizeof(pm_h_refine_info));
-    if (rc != PM_OK) return rc;
-    char* hp = static_cast<char*>(ctx->pinned);
-    memcpy(hp, hin, sizeof hin);
-    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dmask, mask, static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dH, hp, sizeof hin, hipMemcpyHostToDevice, ctx->stream));
-    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
-    rc = refine_launch(ctx, v, dmask, dH, max_iters, dH, dinfo);
-    if (rc != PM_OK) return rc;
-    PM_HIP_CHECK(hipMemcpyAsync(hp, dH, sizeof hin, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hp + HP_INFO, dinfo, sizeof(pm_h_refine_info), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    pm_h_refine_info r;
-    memcpy(&r, hp + HP_INFO, sizeof r);
-    memcpy(H_out, hp, sizeof hin);
-    if (info) *info = r;
-    if (r.status == 2) {
-        pm::set_error("the input H is zero (no model)");
-        return PM_E_NO_MODEL;
-    }
-    return PM_OK;
-}
-
-extern "C" int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
-                                            const pm_ransac_params* p, int max_iters, double H[9], uint8_t* mask,
-                                            int* n_inliers, uint64_t* best_key, pm_h_refine_info* info)
-{
-    if (H) for (int i = 0; i < 9; ++i) H[i] = 0.0;
-    if (mask && n > 0) memset(mask, 0, static_cast<size_t>(n));
-    if (n_inliers) *n_inliers = 0;
-    if (best_key) *best_key = 0;
-    if (info) *info = pm_h_refine_info{0.0, 0.0, 0, 0, 2, 0};
-    int rc = pm_ransac::ransac_h_check(p);
-    if (rc != PM_OK) return rc;
-    rc = check_iters(max_iters);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2)), PM_E_INVALID, "bad point arrays");
-    if (n < 4) { pm::set_error("need at least 4 correspondences, got %d", n); return PM_E_TOO_FEW; }
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
-    const size_t need = 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 6 * 256 +
-                        pm_ransac::fused_scratch_bytes(ctx, p) + 2048;
-    rc = pm::arena_reserve(ctx, need);
-    if (rc != PM_OK) return rc;
-    pm::arena_reset(ctx);
-    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
-    unsigned long long* dkey = static_cast<unsigned long long*>(pm::arena_take(ctx, 8));
-    double* dH = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 9));
-    int* dninl = static_cast<int*>(pm::arena_take(ctx, sizeof(int)));
-    pm_h_refine_info* dinfo = static_cast<pm_h_refine_info*>(pm::arena_take(ctx, sizeof(pm_h_refine_info)));
-    PM_REQUIRE(dxy1 && dxy2 && dmask && dkey && dH && dninl && dinfo, PM_E_NOMEM, "scratch arena too small");
-    constexpr size_t HP_INFO = 88, HP_MASK = 128;   // pinned layout: key (8) | H (72) | count (4) | pad | info (32) | mask
-    rc = pm::pinned_reserve(ctx, HP_MASK + static_cast<size_t>(n));
-    if (rc != PM_OK) return rc;
-
-    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
-    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
-    rc = pm_ransac::ransac_h_enqueue(ctx, v, p, dkey, dH, dmask, n, dninl);
-    if (rc != PM_OK) return rc;
-    rc = refine_launch(ctx, v, dmask, dH, max_iters, dH, dinfo);
-    if (rc != PM_OK) return rc;
-    char* hp = static_cast<char*>(ctx->pinned);
-    unsigned long long* hkey = reinterpret_cast<unsigned long long*>(hp);
-    double* hH = reinterpret_cast<double*>(hp + 8);
-    int* hninl = reinterpret_cast<int*>(hp + 80);
-    uint8_t* hmask = reinterpret_cast<uint8_t*>(hp + HP_MASK);
-    PM_HIP_CHECK(hipMemcpyAsync(hkey, dkey, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hH, dH, sizeof(double) * 9, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hninl, dninl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hp + HP_INFO, dinfo, sizeof(pm_h_refine_info), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (best_key) *best_key = *hkey;
-    if (info) memcpy(info, hp + HP_INFO, sizeof(pm_h_refine_info));
-    if (*hkey == 0ull) {
-        pm::set_error("no valid model (all hypotheses degenerate)");
-        return PM_E_NO_MODEL;
-    }
-    if (H) memcpy(H, hH, sizeof(double) * 9);
-    if (mask) memcpy(mask, hmask, static_cast<size_t>(n));
-    if (n_inliers) *n_inliers = *hninl;
+    using namespace pm_hrefine;
+    pm::ScopedKernelTime t(ctx, "homography_refine");
+    hipLaunchKernelGGL(homography_refine, dim3(1), dim3(HR_P), 0, ctx->stream, v, d_mask, d_H_in, max_iters, d_H_out, d_info);
+    PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
 }

@@ -24,8 +24,9 @@
 // a model policy (FModel here, HModel in csrc/ransac_h_fused.hip, AModel in csrc/ransac_a_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
 // (the product launch: NoDiag, nothing else instantiated) and tools/ablation/ransac_fused_stamps.hip (a diagnostic launch
 // with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).  csrc/ransac_h_fused.hip
-// instantiates the LDS form for the homography; csrc/ransac_shard.hip (finish kernel + the sharded C-ABI entry points)
-// and csrc/homography_refine.hip share the view helpers.
+// and csrc/ransac_a_fused.hip instantiate the LDS form (fused_lds_enqueue) for the homography and the affine models;
+// csrc/ransac_shard.hip (finish kernel + the sharded C-ABI entry points) and csrc/homography_refine.hip share the view
+// helpers.
 #pragma once
 #include "ransac_core.hpp"
 #include "ransac_internal.hpp"
@@ -744,15 +745,6 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
     DIAG::phase(9);
 }
 
-int check_view(const pm_points_view* v)
-{
-    PM_REQUIRE(v != nullptr && v->xy1 && v->xy2, PM_E_INVALID, "null correspondence view");
-    PM_REQUIRE(v->parts >= 1 && v->parts <= PM_MAX_PARTS && v->cap >= 1, PM_E_INVALID, "need 1 <= parts <= 64, cap >= 1");
-    PM_REQUIRE(v->parts == 1 || (v->pitch_xy >= 2LL * v->cap), PM_E_INVALID, "pitch_xy smaller than a part");
-    PM_REQUIRE(static_cast<long long>(v->parts) * v->cap <= 0x7FFFFFFFLL, PM_E_INVALID, "view too large");
-    return PM_OK;
-}
-
 int sync_words(pm_ctx* ctx, int** out)
 {
     if (!ctx->sync_words) {
@@ -785,6 +777,27 @@ int fused_lds_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_param
                        static_cast<int>(p->hyp_end - p->hyp_begin), hb, thr2, tile_slots, slots, ticket, out);
     PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
+}
+
+// Enqueue the LDS form for a model policy with a local result (key, model, mask[mask_len], count), timed as `timer`,
+// arrival ticket sync_words[sync_word]: the launch of RANSAC-H and RANSAC-A.  The arena must already be reserved for
+// fused_scratch_bytes(); the workgroup slots are carved here.
+template <typename MODEL>
+int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int sync_word, const char* timer,
+                      unsigned long long* d_key, double* d_model, uint8_t* d_mask, int mask_len, int* d_ninl)
+{
+    const long long nh = p->hyp_end - p->hyp_begin;
+    const int hb = fused_hb(ctx, nh);
+    const int nwg = static_cast<int>((nh + hb - 1) / hb);
+    RfSlot* slots = static_cast<RfSlot*>(pm::arena_take(ctx, sizeof(RfSlot) * static_cast<size_t>(nwg)));
+    PM_REQUIRE(slots, PM_E_NOMEM, "scratch arena too small");
+    int* sync = nullptr;
+    int rc = sync_words(ctx, &sync);
+    if (rc != PM_OK) return rc;
+    RfOut out{};
+    out.key = d_key; out.F = d_model; out.mask = d_mask; out.mask_len = mask_len; out.n_inliers = d_ninl;
+    pm::ScopedKernelTime t(ctx, timer);
+    return fused_lds_launch<MODEL, NoDiag>(ctx, v, p, nwg, hb, slots, sync + sync_word, out);
 }
 
 // Enqueue the one-launch run.  The arena must already be reserved for fused_scratch_bytes(); it is carved here.

@@ -68,140 +68,12 @@ struct HModel {
     }
 };
 
-int check_params_h(const pm_ransac_params* p)
-{
-    PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
-    PM_REQUIRE(p->hyp_begin >= 0 && p->hyp_end > p->hyp_begin && p->hyp_end <= 0x100000000LL, PM_E_INVALID,
-               "hypothesis ids must satisfy 0 <= begin < end <= 2^32");
-    PM_REQUIRE(p->hyp_end - p->hyp_begin <= 0x7FFFFFFFLL, PM_E_INVALID,
-               "a single launch takes at most 2^31 - 1 hypothesis ids: split the range");
-    PM_REQUIRE(p->error_kind == PM_ERR_REPROJ, PM_E_INVALID, "error_kind must be PM_ERR_REPROJ");
-    return PM_OK;
-}
-
-// Enqueue the one-launch run.  The arena must already be reserved for fused_scratch_bytes(); it is carved here.
-int h_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key, double* d_H,
-             uint8_t* d_mask, int mask_len, int* d_ninl)
-{
-    const long long nh = p->hyp_end - p->hyp_begin;
-    const int hb = fused_hb(ctx, nh);
-    const int nwg = static_cast<int>((nh + hb - 1) / hb);
-    RfSlot* slots = static_cast<RfSlot*>(pm::arena_take(ctx, sizeof(RfSlot) * static_cast<size_t>(nwg)));
-    PM_REQUIRE(slots, PM_E_NOMEM, "scratch arena too small");
-    int* sync = nullptr;
-    int rc = sync_words(ctx, &sync);
-    if (rc != PM_OK) return rc;
-    RfOut out{};
-    out.key = d_key; out.F = d_H; out.mask = d_mask; out.mask_len = mask_len; out.n_inliers = d_ninl;
-    pm::ScopedKernelTime t(ctx, "ransac_h_fused");
-    return fused_lds_launch<HModel, NoDiag>(ctx, v, p, nwg, hb, slots, sync + RH_SYNC_WORD, out);
-}
-
-// Host-pointer driver of pm_ransac_homography (range) and pm_ransac_homography_from_hyp (the range [hyp, hyp + 1)).
-int host_run_h(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p, double H[9],
-               uint8_t* mask, int* n_inliers, uint64_t* best_key)
-{
-    if (H) for (int i = 0; i < 9; ++i) H[i] = 0.0;
-    if (mask && n > 0) memset(mask, 0, static_cast<size_t>(n));
-    if (n_inliers) *n_inliers = 0;
-    if (best_key) *best_key = 0;
-    int rc = check_params_h(p);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2)), PM_E_INVALID, "bad point arrays");
-    if (n < 4) { pm::set_error("need at least 4 correspondences, got %d", n); return PM_E_TOO_FEW; }
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-
-    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
-    const size_t need = 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + 3 * 256 +
-                        fused_scratch_bytes(ctx, p) + 2048;
-    rc = pm::arena_reserve(ctx, need);
-    if (rc != PM_OK) return rc;
-    pm::arena_reset(ctx);
-    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
-    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
-    unsigned long long* dkey = static_cast<unsigned long long*>(pm::arena_take(ctx, 8));
-    double* dH = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 9));
-    int* dninl = static_cast<int*>(pm::arena_take(ctx, sizeof(int)));
-    PM_REQUIRE(dxy1 && dxy2 && dmask && dkey && dH && dninl, PM_E_NOMEM, "scratch arena too small");
-    constexpr size_t HP_MASK = 96;                           // pinned layout: key (8) | H (72) | count (4) | pad | mask
-    rc = pm::pinned_reserve(ctx, HP_MASK + static_cast<size_t>(n));
-    if (rc != PM_OK) return rc;
-
-    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
-    const pm_points_view v{dxy1, dxy2, nullptr, 1, n, 0, 1, 0};
-    rc = h_launch(ctx, v, p, dkey, dH, dmask, n, dninl);
-    if (rc != PM_OK) return rc;
-    char* hp = static_cast<char*>(ctx->pinned);
-    unsigned long long* hkey = reinterpret_cast<unsigned long long*>(hp);
-    double* hH = reinterpret_cast<double*>(hp + 8);
-    int* hninl = reinterpret_cast<int*>(hp + 80);
-    uint8_t* hmask = reinterpret_cast<uint8_t*>(hp + HP_MASK);
-    PM_HIP_CHECK(hipMemcpyAsync(hkey, dkey, 8, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hH, dH, sizeof(double) * 9, hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hninl, dninl, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (best_key) *best_key = *hkey;
-    if (*hkey == 0ull) {
-        pm::set_error("no valid model (all hypotheses degenerate)");
-        return PM_E_NO_MODEL;
-    }
-    if (H) memcpy(H, hH, sizeof(double) * 9);
-    if (mask) memcpy(mask, hmask, static_cast<size_t>(n));
-    if (n_inliers) *n_inliers = *hninl;
-    return PM_OK;
-}
-
 }  // namespace
 
-// for pm_ransac_homography_refined (homography_refine.hip): RANSAC-H and the refinement on one stream, one synchronisation
-int ransac_h_check(const pm_ransac_params* p) { return check_params_h(p); }
 int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
                      double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
-    return h_launch(ctx, v, p, d_key, d_H, d_mask, mask_len, d_ninl);
+    return fused_lds_enqueue<HModel>(ctx, v, p, RH_SYNC_WORD, "ransac_h_fused", d_key, d_H, d_mask, mask_len, d_ninl);
 }
+
 }  // namespace pm_ransac
-
-using namespace pm_ransac;
-
-extern "C" int pm_ransac_homography(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
-                                    double H[9], uint8_t* mask, int* n_inliers, uint64_t* best_key)
-{
-    return host_run_h(ctx, xy1, xy2, n, p, H, mask, n_inliers, best_key);
-}
-
-extern "C" int pm_ransac_homography_from_hyp(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
-                                             const pm_ransac_params* p, int64_t hyp, double H[9], uint8_t* mask,
-                                             int* n_inliers)
-{
-    if (H) for (int i = 0; i < 9; ++i) H[i] = 0.0;
-    if (n_inliers) *n_inliers = 0;
-    PM_REQUIRE(hyp >= 0 && hyp < 0x100000000LL, PM_E_INVALID, "hypothesis id must satisfy 0 <= hyp < 2^32");
-    PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
-    pm_ransac_params q = *p;
-    q.hyp_begin = hyp;
-    q.hyp_end = hyp + 1;
-    return host_run_h(ctx, xy1, xy2, n, &q, H, mask, n_inliers, nullptr);
-}
-
-extern "C" int pm_ransac_homography_run_dev(pm_ctx* ctx, const pm_points_view* view, const pm_ransac_params* p,
-                                            uint64_t* d_best_key, double* d_H, uint8_t* d_mask, int mask_len,
-                                            int32_t* d_n_inliers)
-{
-    PM_REQUIRE(d_best_key && d_H && d_mask && d_n_inliers, PM_E_INVALID, "null argument");
-    PM_REQUIRE(mask_len >= 0, PM_E_INVALID, "mask_len must be >= 0");
-    int rc = check_params_h(p);
-    if (rc != PM_OK) return rc;
-    rc = check_view(view);
-    if (rc != PM_OK) return rc;
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_HIP_CHECK(hipSetDevice(ctx->device));
-    rc = pm::arena_reserve(ctx, fused_scratch_bytes(ctx, p) + 1024);
-    if (rc != PM_OK) return rc;
-    pm::arena_reset(ctx);
-    return h_launch(ctx, *view, p, reinterpret_cast<unsigned long long*>(d_best_key), d_H, d_mask, mask_len, d_n_inliers);
-}

@@ -1,6 +1,8 @@
-// ransac_internal.hpp — entry points of ransac_fused.hip used by the C-ABI functions in ransac.hip (host-pointer
-// and device-resident single-shard runs) and by the multi-GPU driver (mgpu.cpp), of ransac_h_fused.hip used by
-// homography_refine.hip, and of the affine pair ransac_a_fused.hip / affine_refine.hip used by each other.
+// ransac_internal.hpp — host functions shared across translation units: the entry points of ransac_fused.hip used by
+// the C-ABI functions in ransac.hip (host-pointer and device-resident single-shard runs) and by the multi-GPU driver
+// (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue each of the planar estimators'
+// kernel files (ransac_h_fused.hip, ransac_a_fused.hip, homography_refine.hip, affine_refine.hip), which
+// planar_estimators.cpp drives.
 #pragma once
 #include "ransac_core.hpp"
 
@@ -12,17 +14,24 @@ size_t fused_scratch_bytes(const pm_ctx* ctx, const pm_ransac_params* p);
 int fused_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int shard, pm_ransac_record* d_rec,
                  unsigned long long* d_key, double* d_F, uint8_t* d_mask, int mask_len, int* d_ninl, FinalOut** fo_out);
 
-// Host side of the RANSAC-H launch (ransac_h_fused.hip), for pm_ransac_homography_refined: the argument check and the
-// enqueue itself (no synchronisation; the arena must hold fused_scratch_bytes() more, as for pm_ransac_homography).
-int ransac_h_check(const pm_ransac_params* p);
+inline int check_view(const pm_points_view* v)
+{
+    PM_REQUIRE(v != nullptr && v->xy1 && v->xy2, PM_E_INVALID, "null correspondence view");
+    PM_REQUIRE(v->parts >= 1 && v->parts <= PM_MAX_PARTS && v->cap >= 1, PM_E_INVALID, "need 1 <= parts <= 64, cap >= 1");
+    PM_REQUIRE(v->parts == 1 || (v->pitch_xy >= 2LL * v->cap), PM_E_INVALID, "pitch_xy smaller than a part");
+    PM_REQUIRE(static_cast<long long>(v->parts) * v->cap <= 0x7FFFFFFFLL, PM_E_INVALID, "view too large");
+    return PM_OK;
+}
+
+// The planar estimators' launches, each enqueued on ctx->stream with no synchronisation and no argument check.  The
+// RANSAC pair carves its workgroup slots from the arena, which must hold fused_scratch_bytes() more; model is
+// PM_AFFINE_FULL or PM_AFFINE_PARTIAL.
 int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
                      double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
-
-// The affine family (ransac_a_fused.hip, affine_refine.hip): the model check and sample size every affine entry point
-// uses (ransac_a_fused.hip), and the enqueue of the refit (affine_refine.hip; no synchronisation, no per-call state),
-// which pm_estimate_affine runs after RANSAC-A on the same stream.
-int ransac_a_check_model(int model);
-int ransac_a_min_pts(int model);
+int ransac_a_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
+                     double* d_A, uint8_t* d_mask, int mask_len, int* d_ninl);
+int homography_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const uint8_t* d_mask, const double* d_H_in,
+                              int max_iters, double* d_H_out, pm_h_refine_info* d_info);
 int affine_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_A_in,
                           double* d_A_out, pm_h_refine_info* d_info);
 

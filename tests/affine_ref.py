@@ -1,46 +1,31 @@
 """ctypes loader of tests/affine_ref.c, the plain-C restatement of docs/SPEC.md S26-S30 (robust 2D affine and
-similarity estimation, least-squares refit on the inliers).  Built on first use with the host C compiler into a
-temporary directory; shared by test_affine_cpu.py and test_affine_gpu.py.  model: 0 = full, 1 = partial."""
+similarity estimation, least-squares refit on the inliers).  Built on first use by cref.py; shared by
+test_affine_cpu.py and test_affine_gpu.py.  model: 0 = full, 1 = partial."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "affine_ref.c")
+import cref
+from cref import ptr as _p
+
 _lib = None
-_tmp = None
 
 
 def lib():
-    global _lib, _tmp
+    global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
-        assert cc, "no host C compiler"
-        _tmp = tempfile.TemporaryDirectory(prefix="affine_ref_")
-        so = os.path.join(_tmp.name, "libaffine_ref.so")
-        r = subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        L = C.CDLL(so)
-        L.ar_run.restype = C.c_uint64
-        L.ar_run.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_float,
-                             C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ar_sample.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
-        L.ar_solve.argtypes = [C.c_int] + [C.c_void_p] * 5
-        L.ar_model.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
-        L.ar_inlier.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]
-        L.ar_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
-        L.ar_refine.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_void_p]
-        _lib = L
+        _lib = cref.load("affine_ref", {
+            "ar_run": [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_float,
+                       C.c_void_p, C.c_void_p, C.c_void_p],
+            "ar_sample": [C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p],
+            "ar_solve": [C.c_int] + [C.c_void_p] * 5,
+            "ar_model": [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p],
+            "ar_inlier": [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float],
+            "ar_score": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p],
+            "ar_refine": [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_void_p],
+        }, {"ar_run": C.c_uint64})
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _f32(xy):

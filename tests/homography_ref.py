@@ -1,43 +1,27 @@
 """ctypes loader of tests/homography_ref.c, the plain-C restatement of docs/SPEC.md S19-S22 (robust homography).
-Built on first use with the host C compiler into a temporary directory; shared by test_homography_cpu.py and
-test_homography_gpu.py."""
+Built on first use by cref.py; shared by test_homography_cpu.py and test_homography_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "homography_ref.c")
+import cref
+from cref import ptr as _p
+
 _lib = None
-_tmp = None
 
 
 def lib():
-    global _lib, _tmp
+    global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
-        assert cc, "no host C compiler"
-        _tmp = tempfile.TemporaryDirectory(prefix="homography_ref_")
-        so = os.path.join(_tmp.name, "libhomography_ref.so")
-        r = subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        L = C.CDLL(so)
-        L.hr_run.restype = C.c_uint64
-        L.hr_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_float, C.c_void_p,
-                             C.c_void_p, C.c_void_p]
-        L.hr_sample4.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
-        L.hr_solve4.argtypes = [C.c_void_p] * 5
-        L.hr_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
-        L.hr_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]
-        _lib = L
+        _lib = cref.load("homography_ref", {
+            "hr_run": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_float, C.c_void_p,
+                       C.c_void_p, C.c_void_p],
+            "hr_sample4": [C.c_uint64, C.c_uint64, C.c_int, C.c_void_p],
+            "hr_solve4": [C.c_void_p] * 5,
+            "hr_model": [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p],
+            "hr_score": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p],
+        }, {"hr_run": C.c_uint64})
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _f32(xy):

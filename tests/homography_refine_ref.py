@@ -1,17 +1,14 @@
 """ctypes loader of tests/homography_refine_ref.c, the plain-C restatement of docs/SPEC.md S23-S25 (refinement of the
-robust homography on its inliers).  Built on first use with the host C compiler into a temporary directory, as
-homography_ref.py builds its library; shared by test_homography_refine_cpu.py and test_homography_refine_gpu.py."""
+robust homography on its inliers).  Built on first use by cref.py; shared by test_homography_refine_cpu.py and
+test_homography_refine_gpu.py."""
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "homography_refine_ref.c")
+import cref
+from cref import ptr as _p
+
 _lib = None
-_tmp = None
 
 
 class Info(C.Structure):
@@ -24,27 +21,14 @@ class Info(C.Structure):
 
 
 def lib():
-    global _lib, _tmp
+    global _lib
     if _lib is None:
-        cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
-        assert cc, "no host C compiler"
-        _tmp = tempfile.TemporaryDirectory(prefix="homography_refine_ref_")
-        so = os.path.join(_tmp.name, "libhomography_refine_ref.so")
-        r = subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        L = C.CDLL(so)
-        L.hrr_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                 C.c_void_p]
-        L.hrr_refit.argtypes = [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
-        L.hrr_cost.argtypes = [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
-        L.hrr_cost.restype = C.c_double
-        _lib = L
+        _lib = cref.load("homography_refine_ref", {
+            "hrr_refine": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+            "hrr_refit": [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2,
+            "hrr_cost": [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2,
+        }, {"hrr_cost": C.c_double})
     return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _args(xy1, xy2, mask):

@@ -225,3 +225,17 @@ def test_planar_view_is_consistent():
     p = np.column_stack([xy1[inl], np.ones(inl.sum())]) @ H.T
     assert np.abs(p[:, :2] / p[:, 2:3] - xy2[inl]).max() < 1e-3
     assert np.linalg.cond(H) < 1e7
+
+
+def test_homography_wrappers_reject_mismatched_lengths_without_a_device():
+    """The Python wrappers check the row counts before any call into the library (a shorter xy2 would be read past)."""
+    ctx = api.Context.__new__(api.Context)            # no device: the check must come first
+    ctx._h = C.c_void_p()
+    xy1, xy2 = np.zeros((10, 2), np.float32), np.zeros((9, 2), np.float32)
+    for call in (lambda: ctx.ransac_homography(xy1, xy2, 10, 2.0, 1),
+                 lambda: ctx.ransac_homography_from_hyp(xy1, xy2, 0, 2.0, 1),
+                 lambda: ctx.ransac_homography_refined(xy1, xy2, 10, 2.0, 1),
+                 lambda: ctx.ransac_homography(xy2, xy1, 10, 2.0, 1),
+                 lambda: ctx.homography_refine(xy1, xy2, np.ones(10, np.uint8), np.eye(3))):
+        with pytest.raises(ValueError):
+            call()
