@@ -69,7 +69,8 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
  * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
- * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine". */
+ * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
+ * "essential_solve", "ransac_e_fused", "recover_pose". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -474,6 +475,52 @@ int pm_affine_refine_dev(pm_ctx* ctx, int model, const pm_points_view* view, con
 int pm_estimate_affine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
                        int refine, double A[6], uint8_t* mask, int* n_inliers, uint64_t* best_key,
                        pm_h_refine_info* info);
+
+/* ---- calibrated relative pose (cv::findEssentialMat with RANSAC + cv::recoverPose: visual odometry, SfM front ends,
+ * stereo rigs) — docs/SPEC.md S31-S35.  One pinhole camera shared by both views; no distortion.  K is invalid unless
+ * fx, fy > 0, all four values are finite and the normalised threshold thresh_px / ((fx + fy) / 2) is finite and > 0 in
+ * fp32.  Correspondences are normalised as xn = (x - cx) / fx, yn = (y - cy) / fy (fp64, rounded to fp32).
+ * RANSAC-E: pm_ransac_params with error_kind = PM_ERR_SAMPSON; sample h in [hyp_begin, hyp_end) draws 5
+ * correspondences (S32) and the 5-point solve (S33) gives up to 10 candidates, model ids 10h + j; every candidate is
+ * scored with the Sampson test on the normalised points (S34).  Winner: most inliers, ties -> lowest id; the key is
+ * (inliers << 32) | (0xFFFFFFFF - id), so 10 * hyp_end <= 2^32 (and 10 * (hyp_end - hyp_begin) <= 2^31 - 1).
+ * E: 9 doubles row-major, x2n^T E x1n = 0 on normalised coordinates, unit Frobenius norm, its first entry of largest
+ * magnitude positive.  Pose (S35): R (9 doubles, row-major) and t (3 doubles, unit norm) with x2 ~ R x1 + t; the pose
+ * mask is the input mask AND the cheirality of the chosen candidate (depths in (0, dist) in both cameras; OpenCV's
+ * default dist is 50).  Statuses: PM_E_INVALID (bad K, null params / points / outputs, bad range, error_kind,
+ * dist not > 0), n < 5 -> PM_E_TOO_FEW, no valid candidate -> PM_E_NO_MODEL with E = 0, mask = 0.  Graph capture: as
+ * the homography calls (no per-call state; the host forms synchronise). */
+typedef struct pm_camera { double fx, fy, cx, cy; } pm_camera;
+/* Host in, host out.  mask (n bytes), n_inliers, best_key may be NULL. */
+int pm_ransac_essential(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                        const pm_ransac_params* p, double E[9], uint8_t* mask, int* n_inliers, uint64_t* best_key);
+/* All candidates of ONE sample id (0 <= hyp, 10 * hyp + 10 <= 2^32; p's range is ignored): E[10 * 9] (slot j = the
+ * j-th real root of S33, zero when unused), counts[j] = its inlier count (-1: unused slot), *n_models = valid slots.
+ * No valid candidate -> PM_E_NO_MODEL. */
+int pm_ransac_essential_from_hyp(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                                 const pm_ransac_params* p, int64_t hyp, double E[90], int32_t counts[10], int* n_models);
+/* Whole run on the device over a correspondence view (counts read on the device): chains after
+ * pm_filter_ratio_gather_dev / pm_bf_knn_l2_*_ratio_dev with no host round trip.  Writes *d_best_key, d_E (9 doubles),
+ * d_mask[0..mask_len) (zero beyond n) and *d_n_inliers; n < 5 or no valid model leaves key 0, E = 0, mask = 0. */
+int pm_ransac_essential_run_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K, const pm_ransac_params* p,
+                                uint64_t* d_best_key, double* d_E, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers);
+/* cv::recoverPose: decompose E, triangulate the correspondences with mask_in[i] != 0 (mask_in NULL: all) against the
+ * four candidates, keep the one most points pass.  mask_out (n bytes, may alias mask_in), n_good may be NULL; points4
+ * (may be NULL): 4 floats per correspondence, the chosen candidate's homogeneous point (cv::triangulatePoints, n x 4).
+ * E that does not decompose (rank < 2, not finite) -> PM_E_NO_MODEL with R = 0, t = 0, mask 0. */
+int pm_recover_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K, const double E[9],
+                    const uint8_t* mask_in, double dist, double R[9], double t[3], uint8_t* mask_out, int* n_good,
+                    float* points4);
+/* Device form over a view: d_mask_in may be NULL, d_points4 may be NULL; d_mask_out holds parts * cap bytes (zero beyond
+ * n), d_points4 4 * parts * cap floats (written below n).  One launch of one workgroup; a bad E gives R = 0, t = 0. */
+int pm_recover_pose_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K, const double* d_E,
+                        const uint8_t* d_mask_in, double dist, double* d_R, double* d_t, uint8_t* d_mask_out,
+                        int32_t* d_n_good, float* d_points4);
+/* Both in one call, one synchronisation: RANSAC-E, then pose recovery on its inliers.  mask: the pose mask (n bytes,
+ * may be NULL); n_inliers: RANSAC's count; n_good: the pose's.  Statuses as pm_ransac_essential. */
+int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                     const pm_ransac_params* p, double dist, double E[9], double R[9], double t[3], uint8_t* mask,
+                     int* n_inliers, int* n_good, uint64_t* best_key);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

@@ -54,6 +54,8 @@ EXPORTS = [
     "pm_homography_refine", "pm_homography_refine_dev", "pm_ransac_homography_refined",
     "pm_ransac_affine", "pm_ransac_affine_from_hyp", "pm_ransac_affine_run_dev", "pm_affine_refine", "pm_affine_refine_dev",
     "pm_estimate_affine",
+    "pm_ransac_essential", "pm_ransac_essential_from_hyp", "pm_ransac_essential_run_dev", "pm_recover_pose",
+    "pm_recover_pose_dev", "pm_estimate_pose",
 ]
 
 
@@ -72,6 +74,21 @@ class PointsView(C.Structure):
     """pm_points_view: `parts` padded blocks of correspondences with device-side counts (include/pm.h)."""
     _fields_ = [("xy1", C.c_void_p), ("xy2", C.c_void_p), ("counts", C.c_void_p), ("parts", C.c_int32),
                 ("cap", C.c_int32), ("pitch_xy", C.c_int64), ("pitch_cnt", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Camera(C.Structure):
+    """pm_camera: one pinhole camera shared by both views (fx, fy, cx, cy; no distortion)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+def _camera(K):
+    """A Camera from a Camera, (fx, fy, cx, cy) or a 3 x 3 intrinsic matrix."""
+    if isinstance(K, Camera):
+        return K
+    k = np.asarray(K, np.float64)
+    if k.shape == (3, 3):
+        return Camera(k[0, 0], k[1, 1], k[0, 2], k[1, 2])
+    return Camera(*[float(v) for v in k.reshape(4)])
 
 
 class HRefineInfo(C.Structure):
@@ -578,6 +595,76 @@ class Context:
         rc = _outcome(lib().pm_estimate_affine(self._h, model, _p(xy1), _p(xy2), n, C.byref(prm), 1 if refine else 0,
                                                _p(A), _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
         return rc, A.reshape(2, 3), mask[:n], ninl.value, key.value, info
+
+    # -- calibrated relative pose (cv::findEssentialMat + cv::recoverPose, SPEC S31-S35) ---------------------------------
+    # K: a Camera, (fx, fy, cx, cy) or a 3 x 3 intrinsic matrix.  E and R are returned as 3 x 3 float64 arrays.
+    def ransac_essential(self, xy1, xy2, K, iters, thresh_px, seed, hyp_begin=0, kind=PM_ERR_SAMPSON):
+        """Samples [hyp_begin, iters).  Returns (status, E(3x3), mask, n_inliers, best_key); raises on anything other than
+        PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        E = np.zeros(9, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        rc = _outcome(lib().pm_ransac_essential(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), C.byref(prm), _p(E),
+                                                _p(mask), C.byref(ninl), C.byref(key)))
+        return rc, E.reshape(3, 3), mask[:n], ninl.value, key.value
+
+    def ransac_essential_from_hyp(self, xy1, xy2, K, hyp, thresh_px, seed, kind=PM_ERR_SAMPSON):
+        """All candidates of one sample id: (status, E(10x3x3), counts(10; -1 = unused slot), n_models)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        prm = RansacParams(0, 0, seed, thresh_px, kind)
+        E = np.zeros(90, np.float64)
+        counts = np.zeros(10, np.int32)
+        nm = C.c_int()
+        rc = _outcome(lib().pm_ransac_essential_from_hyp(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), C.byref(prm),
+                                                         C.c_int64(hyp), _p(E), _p(counts), C.byref(nm)))
+        return rc, E.reshape(10, 3, 3), counts, nm.value
+
+    def ransac_essential_run_dev(self, view, K, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dE_ptr, dmask_ptr, mask_len,
+                                 dninl_ptr, kind=PM_ERR_SAMPSON):
+        """Device-resident run over a PointsView (count read on the device); outputs are device pointers (E: 9 doubles)."""
+        prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)
+        _check(lib().pm_ransac_essential_run_dev(self._h, C.byref(view), C.byref(_camera(K)), C.byref(prm),
+                                                 C.c_void_p(dkey_ptr), C.c_void_p(dE_ptr), C.c_void_p(dmask_ptr), mask_len,
+                                                 C.c_void_p(dninl_ptr)))
+
+    def recover_pose(self, xy1, xy2, K, E, mask=None, dist=50.0, points=False):
+        """Pose from E on the masked correspondences: (status, R(3x3), t(3), pose mask, n_good, points n x 4 or None)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        Ein = np.ascontiguousarray(E, np.float64).reshape(9)
+        mi = None
+        if mask is not None:
+            mi = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+            if mi.shape[0] != n:
+                raise ValueError("xy1, xy2 and mask must have the same length")
+        R, t = np.zeros(9, np.float64), np.zeros(3, np.float64)
+        mo = np.zeros(max(n, 1), np.uint8)
+        pts = np.zeros((max(n, 1), 4), np.float32) if points else None
+        ng = C.c_int()
+        rc = _outcome(lib().pm_recover_pose(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), _p(Ein), _p(mi),
+                                            C.c_double(dist), _p(R), _p(t), _p(mo), C.byref(ng), _p(pts)))
+        return rc, R.reshape(3, 3), t, mo[:n], ng.value, (pts[:n] if points else None)
+
+    def recover_pose_dev(self, view, K, dE_ptr, dmask_in_ptr, dR_ptr, dt_ptr, dmask_out_ptr, dngood_ptr, dpoints_ptr=None,
+                         dist=50.0):
+        """Device form over a PointsView; dmask_in_ptr and dpoints_ptr may be None."""
+        _check(lib().pm_recover_pose_dev(self._h, C.byref(view), C.byref(_camera(K)), C.c_void_p(dE_ptr),
+                                         C.c_void_p(dmask_in_ptr), C.c_double(dist), C.c_void_p(dR_ptr), C.c_void_p(dt_ptr),
+                                         C.c_void_p(dmask_out_ptr), C.c_void_p(dngood_ptr), C.c_void_p(dpoints_ptr)))
+
+    def estimate_pose(self, xy1, xy2, K, iters, thresh_px, seed, dist=50.0, hyp_begin=0, kind=PM_ERR_SAMPSON):
+        """RANSAC-E + pose recovery, one synchronisation: (status, E, R, t, pose mask, n_inliers, n_good, best_key)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        E, R, t = np.zeros(9, np.float64), np.zeros(9, np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, ng, key = C.c_int(), C.c_int(), C.c_uint64()
+        rc = _outcome(lib().pm_estimate_pose(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), C.byref(prm),
+                                             C.c_double(dist), _p(E), _p(R), _p(t), _p(mask), C.byref(ninl), C.byref(ng),
+                                             C.byref(key)))
+        return rc, E.reshape(3, 3), R.reshape(3, 3), t, mask[:n], ninl.value, ng.value, key.value
+
 
 class LmedsParams(C.Structure):
     _fields_ = [("hyp_begin", C.c_int64), ("hyp_end", C.c_int64), ("seed", C.c_uint64)]

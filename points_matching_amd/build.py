@@ -17,13 +17,18 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
-           "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip", "planar_estimators.cpp",
+           "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
+           "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "planar_estimators.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
          "homography_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
-         "affine_refine.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "affine_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # lane-serial fp64 5-point solver (its 10 x 20 elimination matrix lives in scratch) and the one-workgroup pose
+         # recovery: report their registers, scratch and spills
+         "essential_solve.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "recover_pose.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -3,6 +3,8 @@
 // (RANSAC-A, ransac_a_fused.hip, refitted by affine_refine.hip).  Those files hold the kernels and one enqueue each;
 // here are the argument checks, the staging of host arrays and one driver for every host-pointer form: upload, RANSAC
 // and / or the refit on one stream, one readback into pinned memory, one synchronisation.
+#include <cmath>
+
 #include "affine_core.hpp"
 #include "ransac_internal.hpp"
 
@@ -231,6 +233,232 @@ int refine_dev(pm_ctx* ctx, const Family& f, const pm_points_view* view, const u
     return enqueue_refine(ctx, f, *view, d_mask, d_in, d_out, d_info);
 }
 
+// ---- calibrated relative pose (RANSAC-E and pose recovery) ------------------------------------------------------------
+// S31: K and the normalised threshold (fp32), checked before anything else of the family
+int check_camera(const pm_camera* K, float thresh_px, float* thr_n)
+{
+    PM_REQUIRE(K != nullptr, PM_E_INVALID, "K is null");
+    const bool fin = std::isfinite(K->fx) && std::isfinite(K->fy) && std::isfinite(K->cx) && std::isfinite(K->cy);
+    PM_REQUIRE(fin && K->fx > 0.0 && K->fy > 0.0, PM_E_INVALID, "K needs finite values and fx, fy > 0");
+    const float t = static_cast<float>(static_cast<double>(thresh_px) / (0.5 * (K->fx + K->fy)));
+    PM_REQUIRE(t > 0.0f && std::isfinite(t), PM_E_INVALID, "the normalised threshold must be finite and > 0");
+    *thr_n = t;
+    return PM_OK;
+}
+
+int check_e_params(const pm_ransac_params* p)
+{
+    PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
+    PM_REQUIRE(p->hyp_begin >= 0 && p->hyp_end > p->hyp_begin && p->hyp_end <= 0x100000000LL / 10, PM_E_INVALID,
+               "sample ids must satisfy 0 <= begin < end and 10 * end <= 2^32 (model ids 10h + j)");
+    PM_REQUIRE(10 * (p->hyp_end - p->hyp_begin) <= 0x7FFFFFFFLL, PM_E_INVALID,
+               "a single launch takes at most (2^31 - 1) / 10 samples: split the range");
+    PM_REQUIRE(p->error_kind == PM_ERR_SAMPSON, PM_E_INVALID, "error_kind must be PM_ERR_SAMPSON");
+    return PM_OK;
+}
+
+// The scorer's parameters: model ids [10 begin, 10 end), the normalised threshold
+pm_ransac_params model_ids(const pm_ransac_params* p, float thr_n)
+{
+    pm_ransac_params q = *p;
+    q.hyp_begin = 10 * p->hyp_begin;
+    q.hyp_end = 10 * p->hyp_end;
+    q.thresh_px = thr_n;
+    return q;
+}
+
+// Arena bytes of a RANSAC-E run over a view of cap_total points: normalised copy, count, candidates, scorer slots
+size_t e_scratch_bytes(const pm_ctx* ctx, long long cap_total, const pm_ransac_params* p, float thr_n)
+{
+    const pm_ransac_params q = model_ids(p, thr_n);
+    const size_t nh = static_cast<size_t>(p->hyp_end - p->hyp_begin);
+    return 2 * pm::align_up(sizeof(float) * 2 * static_cast<size_t>(cap_total), 256) + 256 +
+           pm::align_up(sizeof(double) * 100 * nh, 256) + fused_scratch_bytes(ctx, &q) + 1024;
+}
+
+// Solve + score on ctx->stream (the arena reserved for e_scratch_bytes; carved here).  With d_cand_out the scoring
+// launch is left to the caller: *d_cand_out and *vn_out receive the candidate buffer and the normalised view.
+int enqueue_essential(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const pm_ransac_params* p, float thr_n,
+                      unsigned long long* d_key, double* d_E, uint8_t* d_mask, int mask_len, int* d_ninl,
+                      double** d_cand_out = nullptr, pm_points_view* vn_out = nullptr)
+{
+    const long long cap_total = static_cast<long long>(v.parts) * v.cap;
+    const size_t nh = static_cast<size_t>(p->hyp_end - p->hyp_begin);
+    float* xyn = static_cast<float*>(pm::arena_take(ctx, sizeof(float) * 4 * static_cast<size_t>(cap_total)));
+    int* dn = static_cast<int*>(pm::arena_take(ctx, sizeof(int)));
+    double* cand = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 100 * nh));
+    PM_REQUIRE(xyn && dn && cand, PM_E_NOMEM, "scratch arena too small");
+    int rc = essential_solve_enqueue(ctx, v, K, p, xyn, dn, cand);
+    if (rc != PM_OK) return rc;
+    const pm_points_view vn{xyn, xyn + 2 * cap_total, dn, 1, static_cast<int32_t>(cap_total), 0, 1, 0};
+    if (d_cand_out) {
+        *d_cand_out = cand;
+        *vn_out = vn;
+        return PM_OK;
+    }
+    const pm_ransac_params q = model_ids(p, thr_n);
+    return ransac_e_enqueue(ctx, vn, &q, cand, d_key, d_E, d_mask, mask_len, d_ninl);
+}
+
+// The small results of a host-pointer call of the family (mask and points follow the pinned block)
+struct EResults {
+    unsigned long long key;
+    double E[9];
+    int32_t count;
+    int32_t n_good;
+    double R[9];
+    double t[3];
+    unsigned long long keys[10];
+    double cand[100];
+};
+
+enum EStep { E_RANSAC = 1, E_POSE = 2, E_CANDIDATES = 4 };
+
+struct EHostOut {
+    double* E;                  // E_RANSAC: 9; E_CANDIDATES: 90
+    uint8_t* mask;              // n bytes
+    int* n_inliers;
+    uint64_t* best_key;
+    double* R;
+    double* t;
+    int* n_good;
+    float* points4;             // 4 n
+    int32_t* counts;            // E_CANDIDATES: 10
+    int* n_models;
+};
+
+// Driver of every host-pointer form of the family: RANSAC-E (or the candidates of one sample), pose recovery (of
+// RANSAC's winner on its mask, or of E_in on mask_in), one readback, one synchronisation.  Outputs are zeroed before
+// the first check.
+int run_e_host(pm_ctx* ctx, int steps, const float* xy1, const float* xy2, int n, const pm_camera* K,
+               const pm_ransac_params* p, const double* E_in, const uint8_t* mask_in, double dist, const EHostOut& out)
+{
+    const bool ransac = steps & (E_RANSAC | E_CANDIDATES), pose = steps & E_POSE, cands = steps & E_CANDIDATES;
+    if (out.E) memset(out.E, 0, sizeof(double) * (cands ? 90 : 9));
+    if (out.mask && n > 0) memset(out.mask, 0, static_cast<size_t>(n));
+    if (out.n_inliers) *out.n_inliers = 0;
+    if (out.best_key) *out.best_key = 0;
+    if (out.R) memset(out.R, 0, sizeof(double) * 9);
+    if (out.t) memset(out.t, 0, sizeof(double) * 3);
+    if (out.n_good) *out.n_good = 0;
+    if (out.points4 && n > 0) memset(out.points4, 0, sizeof(float) * 4 * static_cast<size_t>(n));
+    if (out.counts) for (int j = 0; j < 10; ++j) out.counts[j] = -1;
+    if (out.n_models) *out.n_models = 0;
+    float thr_n = 1.0f;
+    int rc = PM_OK;
+    if (ransac) {
+        rc = check_e_params(p);
+        if (rc != PM_OK) return rc;
+    }
+    rc = check_camera(K, ransac ? p->thresh_px : 1.0f, &thr_n);
+    if (rc != PM_OK) return rc;
+    if (!ransac) {
+        PM_REQUIRE(E_in != nullptr, PM_E_INVALID, "null E");
+    }
+    if (pose) PM_REQUIRE(dist > 0.0, PM_E_INVALID, "dist must be > 0");
+    if (cands) PM_REQUIRE(out.E && out.counts, PM_E_INVALID, "null E or counts");
+    PM_REQUIRE(n >= 0 && (n == 0 || (xy1 && xy2)), PM_E_INVALID, "bad point arrays");
+    if (n < 5) {
+        pm::set_error("need at least 5 correspondences, got %d", n);
+        return PM_E_TOO_FEW;
+    }
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+
+    const size_t xyb = sizeof(float) * 2 * static_cast<size_t>(n);
+    const size_t pts = out.points4 ? sizeof(float) * 4 * static_cast<size_t>(n) : 0;
+    rc = pm::arena_reserve(ctx, 2 * pm::align_up(xyb, 256) + pm::align_up(static_cast<size_t>(n), 256) + pm::align_up(pts, 256) +
+                                    pm::align_up(sizeof(EResults), 256) + (ransac ? e_scratch_bytes(ctx, n, p, thr_n) : 0) + (cands ? 10 * 1024 : 0) + 1024);
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    float* dxy1 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    float* dxy2 = static_cast<float*>(pm::arena_take(ctx, xyb));
+    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
+    float* dpts = pts ? static_cast<float*>(pm::arena_take(ctx, pts)) : nullptr;
+    EResults* dres = static_cast<EResults*>(pm::arena_take(ctx, sizeof(EResults)));
+    PM_REQUIRE(dxy1 && dxy2 && dmask && dres && (dpts || !pts), PM_E_NOMEM, "scratch arena too small");
+    rc = pm::pinned_reserve(ctx, sizeof(EResults) + static_cast<size_t>(n) + pts);
+    if (rc != PM_OK) return rc;
+    EResults* hres = static_cast<EResults*>(ctx->pinned);
+    uint8_t* hmask = reinterpret_cast<uint8_t*>(hres + 1);
+    float* hpts = reinterpret_cast<float*>(hmask + n);
+
+    PM_HIP_CHECK(hipMemcpyAsync(dxy1, xy1, xyb, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(dxy2, xy2, xyb, hipMemcpyHostToDevice, ctx->stream));
+    if (!ransac) {
+        memcpy(hres->E, E_in, sizeof(double) * 9);
+        PM_HIP_CHECK(hipMemcpyAsync(dres->E, hres->E, sizeof(double) * 9, hipMemcpyHostToDevice, ctx->stream));
+        if (mask_in) PM_HIP_CHECK(hipMemcpyAsync(dmask, mask_in, static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const pm_points_view v = one_part_view(dxy1, dxy2, n);
+    if (cands) {
+        double* dcand = nullptr;
+        pm_points_view vn{};
+        rc = enqueue_essential(ctx, v, *K, p, thr_n, nullptr, nullptr, nullptr, 0, nullptr, &dcand, &vn);
+        if (rc != PM_OK) return rc;
+        // each candidate alone: model ids [10 hyp + j, 10 hyp + j + 1); its key holds its count
+        for (int j = 0; j < 10; ++j) {
+            pm_ransac_params q = model_ids(p, thr_n);
+            q.hyp_begin += j;
+            q.hyp_end = q.hyp_begin + 1;
+            rc = ransac_e_enqueue(ctx, vn, &q, dcand + 10 * j, &dres->keys[j], nullptr, dmask, 0, nullptr);
+            if (rc != PM_OK) return rc;
+        }
+        PM_HIP_CHECK(hipMemcpyAsync(dres->cand, dcand, sizeof(double) * 100, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (ransac && !cands) {
+        rc = enqueue_essential(ctx, v, *K, p, thr_n, &dres->key, dres->E, dmask, n, &dres->count);
+        if (rc != PM_OK) return rc;
+    }
+    if (pose) {
+        rc = recover_pose_enqueue(ctx, v, *K, dres->E, (ransac || mask_in) ? dmask : nullptr, dist, dres->R, dres->t, dmask, n,
+                                  &dres->n_good, dpts);
+        if (rc != PM_OK) return rc;
+    }
+    PM_HIP_CHECK(hipMemcpyAsync(hres, dres, sizeof(EResults), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
+    if (pts) PM_HIP_CHECK(hipMemcpyAsync(hpts, dpts, pts, hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+
+    if (cands) {
+        int nm = 0;
+        for (int j = 0; j < 10; ++j) {
+            if (hres->cand[10 * j + 9] == 0.0) continue;
+            memcpy(out.E + 9 * j, hres->cand + 10 * j, sizeof(double) * 9);
+            out.counts[j] = static_cast<int32_t>(hres->keys[j] >> 32);
+            ++nm;
+        }
+        if (out.n_models) *out.n_models = nm;
+        if (nm == 0) {
+            pm::set_error("no valid candidate (degenerate sample)");
+            return PM_E_NO_MODEL;
+        }
+        return PM_OK;
+    }
+    if (ransac) {
+        if (out.best_key) *out.best_key = hres->key;
+        if (hres->key == 0ull) {
+            pm::set_error("no valid model (all samples degenerate)");
+            return PM_E_NO_MODEL;
+        }
+        if (out.E) memcpy(out.E, hres->E, sizeof(double) * 9);
+        if (out.n_inliers) *out.n_inliers = hres->count;
+    }
+    if (pose) {
+        const bool ok = hres->t[0] != 0.0 || hres->t[1] != 0.0 || hres->t[2] != 0.0;
+        if (!ok) {
+            pm::set_error("E does not decompose (rank < 2 or not finite)");
+            return PM_E_NO_MODEL;
+        }
+        if (out.R) memcpy(out.R, hres->R, sizeof(double) * 9);
+        if (out.t) memcpy(out.t, hres->t, sizeof(double) * 3);
+        if (out.n_good) *out.n_good = hres->n_good;
+        if (out.points4) memcpy(out.points4, hpts, pts);
+    }
+    if (out.mask) memcpy(out.mask, hmask, static_cast<size_t>(n));
+    return PM_OK;
+}
+
 }  // namespace
 }  // namespace pm_ransac
 
@@ -321,4 +549,83 @@ extern "C" int pm_estimate_affine(pm_ctx* ctx, int model, const float* xy1, cons
 {
     return run_host(ctx, affine(model), refine ? RANSAC | REFIT : RANSAC, xy1, xy2, n, p, nullptr, nullptr,
                     HostOut{A, mask, n_inliers, best_key, info});
+}
+
+// ---- calibrated relative pose
+extern "C" int pm_ransac_essential(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                                   const pm_ransac_params* p, double E[9], uint8_t* mask, int* n_inliers, uint64_t* best_key)
+{
+    EHostOut o{};
+    o.E = E; o.mask = mask; o.n_inliers = n_inliers; o.best_key = best_key;
+    return run_e_host(ctx, E_RANSAC, xy1, xy2, n, K, p, nullptr, nullptr, 0.0, o);
+}
+
+extern "C" int pm_ransac_essential_from_hyp(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                                            const pm_ransac_params* p, int64_t hyp, double E[90], int32_t counts[10],
+                                            int* n_models)
+{
+    EHostOut o{};
+    o.E = E; o.counts = counts; o.n_models = n_models;
+    if (E) memset(E, 0, sizeof(double) * 90);
+    if (counts) for (int j = 0; j < 10; ++j) counts[j] = -1;
+    if (n_models) *n_models = 0;
+    PM_REQUIRE(hyp >= 0 && hyp < 0x100000000LL / 10, PM_E_INVALID, "sample id must satisfy 0 <= hyp and 10 * hyp + 10 <= 2^32");
+    PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
+    pm_ransac_params q = *p;
+    q.hyp_begin = hyp;
+    q.hyp_end = hyp + 1;
+    return run_e_host(ctx, E_CANDIDATES, xy1, xy2, n, K, &q, nullptr, nullptr, 0.0, o);
+}
+
+extern "C" int pm_ransac_essential_run_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K,
+                                           const pm_ransac_params* p, uint64_t* d_best_key, double* d_E, uint8_t* d_mask,
+                                           int mask_len, int32_t* d_n_inliers)
+{
+    PM_REQUIRE(d_best_key && d_E && d_mask && d_n_inliers, PM_E_INVALID, "null argument");
+    PM_REQUIRE(mask_len >= 0, PM_E_INVALID, "mask_len must be >= 0");
+    int rc = check_e_params(p);
+    if (rc != PM_OK) return rc;
+    float thr_n = 1.0f;
+    rc = check_camera(K, p->thresh_px, &thr_n);
+    if (rc != PM_OK) return rc;
+    rc = dev_prologue(ctx, view, nullptr);
+    if (rc != PM_OK) return rc;
+    rc = pm::arena_reserve(ctx, e_scratch_bytes(ctx, static_cast<long long>(view->parts) * view->cap, p, thr_n));
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    return enqueue_essential(ctx, *view, *K, p, thr_n, reinterpret_cast<unsigned long long*>(d_best_key), d_E, d_mask, mask_len,
+                             d_n_inliers);
+}
+
+extern "C" int pm_recover_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K, const double E[9],
+                               const uint8_t* mask_in, double dist, double R[9], double t[3], uint8_t* mask_out, int* n_good,
+                               float* points4)
+{
+    EHostOut o{};
+    o.mask = mask_out; o.R = R; o.t = t; o.n_good = n_good; o.points4 = points4;
+    return run_e_host(ctx, E_POSE, xy1, xy2, n, K, nullptr, E, mask_in, dist, o);
+}
+
+extern "C" int pm_recover_pose_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K, const double* d_E,
+                                   const uint8_t* d_mask_in, double dist, double* d_R, double* d_t, uint8_t* d_mask_out,
+                                   int32_t* d_n_good, float* d_points4)
+{
+    PM_REQUIRE(d_E && d_R && d_t && d_mask_out && d_n_good, PM_E_INVALID, "null argument");
+    float thr_n = 1.0f;
+    int rc = check_camera(K, 1.0f, &thr_n);
+    if (rc != PM_OK) return rc;
+    PM_REQUIRE(dist > 0.0, PM_E_INVALID, "dist must be > 0");
+    rc = dev_prologue(ctx, view, nullptr);
+    if (rc != PM_OK) return rc;
+    return recover_pose_enqueue(ctx, *view, *K, d_E, d_mask_in, dist, d_R, d_t, d_mask_out, view->parts * view->cap, d_n_good,
+                                d_points4);
+}
+
+extern "C" int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                                const pm_ransac_params* p, double dist, double E[9], double R[9], double t[3], uint8_t* mask,
+                                int* n_inliers, int* n_good, uint64_t* best_key)
+{
+    EHostOut o{};
+    o.E = E; o.mask = mask; o.n_inliers = n_inliers; o.best_key = best_key; o.R = R; o.t = t; o.n_good = n_good;
+    return run_e_host(ctx, E_RANSAC | E_POSE, xy1, xy2, n, K, p, nullptr, nullptr, dist, o);
 }

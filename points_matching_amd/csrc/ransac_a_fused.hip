@@ -26,6 +26,7 @@ struct AModel {
     static constexpr int MIN_PTS = Traits<MODEL>::MIN_PTS;
     static constexpr bool SHARD_OUT = false;               // key, A, mask and count only
     static constexpr int OUT_WORDS = 6;
+    static constexpr bool CANDIDATES = false;
 
     // SPEC S26, S27: sample and solve hypothesis h.
     template <typename DIAG>

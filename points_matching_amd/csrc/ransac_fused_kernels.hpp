@@ -21,7 +21,8 @@
 // of a query-row-sharded matcher): the view is resolved while loading, no concatenation pass exists.
 //
 // Everything here is templated on a diagnostics policy (ransac_core.hpp: NoDiag); the LDS form below is also templated on
-// a model policy (FModel here, HModel in csrc/ransac_h_fused.hip, AModel in csrc/ransac_a_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
+// a model policy (FModel here, HModel in csrc/ransac_h_fused.hip, AModel in csrc/ransac_a_fused.hip, EModel in
+// csrc/ransac_e_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
 // (the product launch: NoDiag, nothing else instantiated) and tools/ablation/ransac_fused_stamps.hip (a diagnostic launch
 // with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).  csrc/ransac_h_fused.hip
 // and csrc/ransac_a_fused.hip instantiate the LDS form (fused_lds_enqueue) for the homography and the affine models;
@@ -57,7 +58,10 @@ struct RfOut {
     int mask_len;                 // local: bytes of `mask` (zero beyond n)
     int* n_inliers;               // local, may be null
     FinalOut* fo;                 // local, may be null (host entry point reads it back)
-    pm_ransac_record* rec;        // shard
+    union {
+        pm_ransac_record* rec;    // shard
+        const double* cand;       // CANDIDATES policies (never SHARD_OUT): the solved models, 10 doubles (9 + valid flag)
+    };                            // per id from hyp_begin.  A union keeps the kernel arguments of F, H and A as they were
 };
 
 // ---- correspondence view -------------------------------------------------------------------------------------
@@ -205,12 +209,16 @@ __device__ __forceinline__ void inlier_pk_model(const ModelS& m, f32x2 x, f32x2 
 //   inlier_x2           the same test, model in VGPRs (mask phase);
 //   SHARD_OUT           whether the run may end in a shard record (out.shard) or a result block (out.fo).  Without
 //                       them the tail carries no tests of either (measured: ~0.4 us at 512-2275 correspondences);
-//   OUT_WORDS           the doubles of the published model out.F (9; the 2 x 3 affine models of ransac_a_fused.hip: 6).
+//   OUT_WORDS           the doubles of the published model out.F (9; the 2 x 3 affine models of ransac_a_fused.hip: 6);
+//   CANDIDATES          false: the kernel calls solve().  true (EModel, ransac_e_fused.hip): the models were solved by an
+//                       earlier launch; load() reads model id hyp_begin + k from out.cand, and a wave scores only the
+//                       hypotheses whose valid flag is set.
 template <int KIND>
 struct FModel {
     static constexpr int MIN_PTS = 8;
     static constexpr bool SHARD_OUT = true;
     static constexpr int OUT_WORDS = 9;
+    static constexpr bool CANDIDATES = false;
     template <typename DIAG>
     static __device__ __forceinline__ bool solve(const pm_points_view& v, const int* __restrict__ offs, int n, uint64_t seed,
                                                  uint64_t h, double (&F)[9])
@@ -543,6 +551,37 @@ __device__ __forceinline__ void score_lds(const float (*s_mdl)[12], int* s_cnt, 
     }
 }
 
+// The same over NH explicit hypotheses ss[0..NH) (wave-uniform): the scorer of CANDIDATES policies, which skips the ids
+// whose valid flag is 0.
+template <typename MODEL, int NH>
+__device__ __forceinline__ void score_lds_ids(const float (*s_mdl)[12], int* s_cnt, const f32x2* pp, int kslots, const int (&ss)[4],
+                                              float thr2, int lane)
+{
+    ModelS ms[NH];
+    int c[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const float* m = s_mdl[ss[h]];
+        ms[h] = model_to_sgprs(*reinterpret_cast<const f32x4v*>(m), *reinterpret_cast<const f32x4v*>(m + 4),
+                               *reinterpret_cast<const f32x2*>(m + 8));
+        c[h] = 0;
+    }
+    for (int slot = 0; slot < kslots; ++slot) {
+        const f32x2 x = pp[0], y = pp[64], xp = pp[128], yp = pp[192];
+        pp += 256;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            bool ia, ib;
+            MODEL::inlier_pk(ms[h], x, y, xp, yp, thr2, ia, ib);
+            c[h] += __popcll(__ballot(ia)) + __popcll(__ballot(ib));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int h = 0; h < NH; ++h) s_cnt[ss[h]] += c[h];
+    }
+}
+
 template <typename MODEL, typename DIAG>
 __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v, uint64_t seed, int64_t hyp_begin, int nh, int hb,
                                                                float thr2, int tile_slots, RfSlot* __restrict__ slots,
@@ -609,8 +648,12 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
             bool ok = false;
 #pragma unroll
             for (int i = 0; i < 9; ++i) F[i] = 0.0;
-            if (n >= MODEL::MIN_PTS)
-                ok = MODEL::template solve<DIAG>(v, s_offs, n, seed, static_cast<uint64_t>(hyp_begin + h0 + tid), F);
+            if constexpr (MODEL::CANDIDATES) {
+                if (n >= MODEL::MIN_PTS) ok = MODEL::load(out.cand, h0 + tid, F);
+            } else {
+                if (n >= MODEL::MIN_PTS)
+                    ok = MODEL::template solve<DIAG>(v, s_offs, n, seed, static_cast<uint64_t>(hyp_begin + h0 + tid), F);
+            }
 #pragma unroll
             for (int i = 0; i < 9; ++i) { s_mdl[tid][i] = static_cast<float>(F[i]); s_m64[tid][i] = F[i]; }
             s_mdl[tid][9] = ok ? 1.f : 0.f;
@@ -633,12 +676,35 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
             for (int slot = wave; slot < kslots; slot += RL_WAVES) load_pair(t * tile_pts, slot, lane);
             __syncthreads();
         }
-        for (int s = wave; s < hcount; s += 4 * RL_WAVES) {
-            const int left = (hcount - s + RL_WAVES - 1) / RL_WAVES;       // hypotheses of this wave from s on
-            if (left >= 4) score_lds<MODEL, 4>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else if (left == 3) score_lds<MODEL, 3>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else if (left == 2) score_lds<MODEL, 2>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
-            else score_lds<MODEL, 1>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+        if constexpr (MODEL::CANDIDATES) {
+            // bit k: hypothesis wave + 12k is valid (k <= 10: hb <= 128); up to four of them per pass
+            const int sk = wave + RL_WAVES * lane;
+            unsigned long long live = __ballot(sk < hcount && s_mdl[sk < hcount ? sk : 0][9] != 0.f);
+            while (live) {
+                int ss[4];
+                int k = 0;
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    ss[h] = wave;
+                    if (live) {
+                        ss[h] = wave + RL_WAVES * static_cast<int>(__builtin_ctzll(live));
+                        live &= live - 1;
+                        k = h + 1;
+                    }
+                }
+                if (k == 4) score_lds_ids<MODEL, 4>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else if (k == 3) score_lds_ids<MODEL, 3>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else if (k == 2) score_lds_ids<MODEL, 2>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else score_lds_ids<MODEL, 1>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+            }
+        } else {
+            for (int s = wave; s < hcount; s += 4 * RL_WAVES) {
+                const int left = (hcount - s + RL_WAVES - 1) / RL_WAVES;   // hypotheses of this wave from s on
+                if (left >= 4) score_lds<MODEL, 4>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+                else if (left == 3) score_lds<MODEL, 3>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+                else if (left == 2) score_lds<MODEL, 2>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+                else score_lds<MODEL, 1>(s_mdl, s_cnt, s_pts + lane, kslots, s, thr2, lane);
+            }
         }
     }
     DIAG::phase(5);
@@ -784,7 +850,8 @@ int fused_lds_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_param
 // fused_scratch_bytes(); the workgroup slots are carved here.
 template <typename MODEL>
 int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int sync_word, const char* timer,
-                      unsigned long long* d_key, double* d_model, uint8_t* d_mask, int mask_len, int* d_ninl)
+                      unsigned long long* d_key, double* d_model, uint8_t* d_mask, int mask_len, int* d_ninl,
+                      const double* d_cand = nullptr)
 {
     const long long nh = p->hyp_end - p->hyp_begin;
     const int hb = fused_hb(ctx, nh);
@@ -796,6 +863,7 @@ int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_para
     if (rc != PM_OK) return rc;
     RfOut out{};
     out.key = d_key; out.F = d_model; out.mask = d_mask; out.mask_len = mask_len; out.n_inliers = d_ninl;
+    out.cand = d_cand;
     pm::ScopedKernelTime t(ctx, timer);
     return fused_lds_launch<MODEL, NoDiag>(ctx, v, p, nwg, hb, slots, sync + sync_word, out);
 }

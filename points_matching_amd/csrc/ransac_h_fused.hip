@@ -26,6 +26,7 @@ struct HModel {
     static constexpr int MIN_PTS = 4;
     static constexpr bool SHARD_OUT = false;               // key, H, mask and count only
     static constexpr int OUT_WORDS = 9;
+    static constexpr bool CANDIDATES = false;
 
     // SPEC S19, S20: sample and solve hypothesis h.
     template <typename DIAG>

@@ -1,8 +1,8 @@
 // ransac_internal.hpp — host functions shared across translation units: the entry points of ransac_fused.hip used by
 // the C-ABI functions in ransac.hip (host-pointer and device-resident single-shard runs) and by the multi-GPU driver
 // (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue each of the planar estimators'
-// kernel files (ransac_h_fused.hip, ransac_a_fused.hip, homography_refine.hip, affine_refine.hip), which
-// planar_estimators.cpp drives.
+// kernel files (ransac_h_fused.hip, ransac_a_fused.hip, homography_refine.hip, affine_refine.hip) and of the
+// calibrated-pose ones (essential_solve.hip, ransac_e_fused.hip, recover_pose.hip), which planar_estimators.cpp drives.
 #pragma once
 #include "ransac_core.hpp"
 
@@ -34,5 +34,18 @@ int homography_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const uint8_
                               int max_iters, double* d_H_out, pm_h_refine_info* d_info);
 int affine_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_A_in,
                           double* d_A_out, pm_h_refine_info* d_info);
+
+// Calibrated relative pose.  essential_solve_enqueue normalises the view by K into d_xyn (two arrays of 2 * parts * cap
+// floats) with its count in *d_n, and solves samples [hyp_begin, hyp_end) of p into d_cand (100 doubles per sample);
+// ransac_e_enqueue scores model ids [q->hyp_begin, q->hyp_end) (10 per sample, d_cand at the first) on the normalised
+// view vn, q->thresh_px being the normalised threshold (carves its slots like ransac_h_enqueue); recover_pose_enqueue
+// is one workgroup over the raw view.
+int essential_solve_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const pm_ransac_params* p, float* d_xyn,
+                            int* d_n, double* d_cand);
+int ransac_e_enqueue(pm_ctx* ctx, const pm_points_view& vn, const pm_ransac_params* q, const double* d_cand,
+                     unsigned long long* d_key, double* d_E, uint8_t* d_mask, int mask_len, int* d_ninl);
+int recover_pose_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const double* d_E, const uint8_t* d_mask_in,
+                         double dist, double* d_R, double* d_t, uint8_t* d_mask_out, int mask_len, int* d_n_good,
+                         float* d_points4);
 
 }  // namespace pm_ransac

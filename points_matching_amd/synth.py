@@ -227,6 +227,65 @@ def planar_view(n, seed=0xC5, outlier_frac=0.3, noise_px=0.5, width=993, height=
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), H, inl
 
 
+def calibrated_view(n, seed=0xE5, K=None, R=None, t=None, outlier_frac=0.3, noise_px=0.5, planar=False, forward=False,
+                    width=993, height=660):
+    """Correspondences of a calibrated two-view scene (visual odometry, SfM, a stereo rig): 3-D points seen by one
+    pinhole camera K at [I|0] and at [R|t], plus N(0, noise_px) in both images; `outlier_frac` of the pairs get
+    uniform-random image-2 positions.  Defaults: K with fx != fy and an off-centre principal point; R a rotation up to
+    ~6 degrees; t a unit sideways baseline, or (`forward`) mostly along the optical axis.  `planar`: the points lie on
+    one tilted plane.  Points are kept in front of both cameras.
+
+    Returns xy1, xy2 (n x 2 float32 pixels), K (3 x 3), R (3 x 3), t (unit 3-vector; x2 ~ K (R X + t)), X (n x 3 points
+    in camera-1 coordinates) and the boolean ground-truth inlier flags.
+    """
+    rng = np.random.default_rng([seed, 0xE55E])
+    if K is None:
+        K = np.array([[rng.uniform(700, 900), 0, width / 2.0 + rng.uniform(-40, 40)],
+                      [0, rng.uniform(750, 950), height / 2.0 + rng.uniform(-30, 30)], [0, 0, 1.0]])
+    K = np.asarray(K, np.float64)
+    if R is None:
+        w = rng.normal(size=3)
+        w *= rng.uniform(0.03, 0.1) / np.linalg.norm(w)
+        th = np.linalg.norm(w)
+        k = w / th
+        Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+        R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+    R = np.asarray(R, np.float64)
+    if t is None:
+        t = np.array([0.2, 0.05, -1.0]) if forward else np.array([1.0, rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)])
+    t = np.asarray(t, np.float64) / np.linalg.norm(t)
+    Ki = np.linalg.inv(K)
+    X = np.zeros((0, 3))
+    while X.shape[0] < n:
+        m = 2 * n
+        px = rng.uniform([0, 0], [width, height], (m, 2))
+        ray = np.c_[px, np.ones(m)] @ Ki.T
+        if planar:
+            nrm = np.array([0.1, -0.2, 1.0])
+            d = 8.0
+            z = d / (ray @ nrm)
+        else:
+            z = rng.uniform(4.0, 12.0, m)
+        P = ray * z[:, None]
+        P2 = P @ R.T + t
+        P = P[(P[:, 2] > 0.5) & (P2[:, 2] > 0.5)]
+        X = np.r_[X, P]
+    X = X[:n]
+    x1 = X @ K.T
+    x1 = x1[:, :2] / x1[:, 2:3]
+    x2 = (X @ R.T + t) @ K.T
+    x2 = x2[:, :2] / x2[:, 2:3]
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
+    return (np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), K, R, t, X, inl)
+
+
 def affine_view(n, seed=0xA5, outlier_frac=0.3, noise_px=0.5, partial=False, width=993, height=660):
     """Correspondences of a 2D affine scene (a document scan, an aerial mosaic tile, a stabilised video frame): image-2
     points are image-1 points mapped by a known affine map about the image centre, plus N(0, noise_px) in both images;
