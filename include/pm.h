@@ -127,7 +127,10 @@ enum {
     PM_OPT_HAMMING_REFINE = 19, /* Hamming matrix-core route, refinement: 1 = one wave per query (round 1), 2 = four queries per
                                    wave, one 16-lane row each (default where a query has <= 64 candidate entries); in both
                                    the rare whole-sub-list scans are done by the whole workgroup                       */
-    PM_OPT_COUNT_         = 20
+    PM_OPT_KNN_SUPERTILE  = 20, /* u8 coarse kernel, two-buffer form, 8-row groups: 128-row tiles per LDS buffer and per
+                                   workgroup barrier, 1 = one (default), 2 = two, 3 = four; timed as knn_l2_mfma_u8,
+                                   knn_l2_mfma_u8_s2, knn_l2_mfma_u8_s4 (measured, not faster: DESIGN.md 2.1)        */
+    PM_OPT_COUNT_         = 21
 };
 int  pm_ctx_set_option(pm_ctx* ctx, int option, int value);
 int  pm_ctx_get_option(pm_ctx* ctx, int option, int* value);

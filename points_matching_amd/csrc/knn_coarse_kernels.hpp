@@ -682,12 +682,19 @@ __device__ __forceinline__ void h_tile(const uint4* __restrict__ tb, const uint4
 // 128 B/clk is exactly the matrix pipe's time), and the two groups' lists meet in LDS once, at the end — the split
 // count (and with it the refinement's input) stays that of one workgroup per CU.
 // mode bit 0: 0 = run always (hint / i8), 1 = run only if prep16 found the data eligible (auto); bit 1: XCD-tiled grid
-template <typename R, int NQB, bool DMA, int GR, typename ABL>
+// S (seeded LDS-DMA form, GR = 1): SUPER-TILES of S consecutive 128-row tiles per LDS buffer and per barrier.  Super-tile
+// u + 1 is requested when super-tile u starts, so the barrier's fence (vmcnt(0)) has S x 1024 matrix-pipe cycles to cover
+// the DMA instead of 1024, and the waves meet S times less often.  Tile tix = S*u + i keeps its group ids (lb = tix * 4 *
+// GPB): the candidates are those of S = 1 bit for bit.  The last super-tile of a split may be partial: tiles past the
+// split are neither requested nor computed.
+template <typename R, int NQB, bool DMA, int GR, int S, typename ABL>
 __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 2 ? 1 : 2) : (NQB == 2 ? 2 : 4))) void knn_mfma_rows288(
     const uint4* __restrict__ Qh, const uint4* __restrict__ Th, const uint4* __restrict__ seeds_g, int nq, int nt,
     int tiles_per_split, unsigned par, typename R::list* __restrict__ cand_val, int slots,
     const unsigned long long* __restrict__ stats, unsigned epoch, int mode)
 {
+    static_assert(S == 1 || ((S == 2 || S == 4) && GR == 1 && DMA && R::SEEDED), "super-tiles: the seeded LDS-DMA form, one row group");
+    ABL::stamp(0);
     typedef typename R::frag frag;
     typedef typename R::acc acc;
     typedef typename R::list list;
@@ -699,10 +706,10 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
         if (static_cast<unsigned>(s1 >> 32) == epoch && (s1 & 2ull) && static_cast<unsigned>(s3 >> 32) == epoch)
             return;                    // not integer-valued AND the rounded-copy route withdrew: the f32 kernel takes over
     }
-    extern __shared__ __attribute__((aligned(16))) uint4 hsm[];                   // [2][H_TT][R::LDS_ROW16] (+ [2][64] seeds)
+    extern __shared__ __attribute__((aligned(16))) uint4 hsm[];                   // [2][S][H_TT][R::LDS_ROW16] (+ [2][S][64] seeds)
     static_assert(!R::SEEDED || DMA, "the seeded routes stage by LDS-DMA only");
     constexpr int TILE_SLOTS = H_TT * R::LDS_ROW16;
-    uint4* const ssm = hsm + 2 * TILE_SLOTS;                                      // seeded routes: [2][64] (1 KiB per DMA piece, 512 B used)
+    uint4* const ssm = hsm + 2 * S * TILE_SLOTS;                                  // seeded routes: [2][S][64] (1 KiB per DMA piece, 512 B used)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int gw = wave % WPG, grp = wave / WPG;           // wave inside its row group, row group
@@ -719,15 +726,35 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
     // seeds: one more 1-KiB piece per tile, issued by the last wave (the source array carries one tile of slack)
     const __amdgpu_buffer_rsrc_t s_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint4*>(R::SEEDED ? seeds_g : Th), 0, (ntiles + 1) * SEED_TILE_BYTES, 0x00020000);
-    auto seed_issue = [&](int tile, int buf) {
+    // (the seed piece of tile i of a super-tile is issued by wave NW - 1 - i: S <= 4 <= NW)
+    auto seed_issue = [&](int tile, int buf, int i) {
         typedef __attribute__((address_space(3))) void* lptr_t;
-        if (R::SEEDED && wave == THREADS / 64 - 1)
+        if (R::SEEDED && wave == THREADS / 64 - 1 - i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(s_rsrc, (lptr_t)(ssm + 64 * buf), 16, lane * 16, tile * SEED_TILE_BYTES, 0, 0);
     };
+    int tile1 = tile0 + tiles_per_split;
+    if (tile1 > ntiles) tile1 = ntiles;
+    const int ntl = tile1 - tile0;                              // tiles of this split (>= 1 for every split the host sizes)
+    static_assert(S <= THREADS / 64, "one wave per seed piece of a super-tile");
+    // super-tile u into buffer b: its tiles that exist (wave-uniform); S = 1 keeps the clamped re-stage past the end
+    auto super_issue = [&](int u, int b) {
+#pragma unroll
+        for (int i = 0; i < S; ++i) {
+            if constexpr (S == 1) {
+                const int t = tile0 + u < ntiles ? tile0 + u : (tile0 + u - 1 < ntiles ? tile0 + u - 1 : ntiles - 1);
+                dma.issue(t_rsrc, t, hsm, b, wave);
+                seed_issue(t, b, 0);
+            } else if (S * u + i < ntl) {
+                dma.issue(t_rsrc, tile0 + S * u + i, hsm, b * S + i, wave);
+                seed_issue(tile0 + S * u + i, b * S + i, i);
+            }
+        }
+    };
+    ABL::stamp(18);
     if (DMA) {
         dma.init(lane, wave);
-        dma.issue(t_rsrc, tile0 < ntiles ? tile0 : ntiles - 1, hsm, 0, wave);
-        seed_issue(tile0 < ntiles ? tile0 : ntiles - 1, 0);
+        super_issue(0, 0);
+        ABL::stamp(19);
     } else {
         st.load(Th, tile0 < ntiles ? tile0 : ntiles - 1, tid);      // unconditional (clamped): nt >= 1
     }
@@ -735,8 +762,13 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb)
 #pragma unroll
-        for (int c = 0; c < R::NCH; ++c)
-            qf[qb][c] = *reinterpret_cast<const frag*>(Qh + static_cast<size_t>(qbase + 32 * qb + r) * R::ROW16 + 2 * c + h);
+        for (int c = 0; c < R::NCH; ++c) {
+            if constexpr (R::SEEDED && R::NCH == U8_NCH)     // u8 route: the copy in B-fragment order (u8_qfrag_index2)
+                qf[qb][c] = *reinterpret_cast<const frag*>(Qh + (static_cast<size_t>((qbase >> 5) + qb) * R::NCH + c) * 64 + lane);
+            else
+                qf[qb][c] = *reinterpret_cast<const frag*>(Qh + static_cast<size_t>(qbase + 32 * qb + r) * R::ROW16 + 2 * c + h);
+        }
+    ABL::stamp(1);
     // make the fragments opaque: hipcc otherwise treats the loads as rematerialisable and re-reads
     // some of them from global memory inside the tile loop
 #pragma unroll
@@ -749,8 +781,6 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
             qf[qb][c] = __builtin_bit_cast(frag, t);
         }
 
-    int tile1 = tile0 + tiles_per_split;
-    if (tile1 > ntiles) tile1 = ntiles;
     list cl[NQB];
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) cl[qb] = R::empty();
@@ -758,31 +788,39 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
     if (tile0 < tile1) {
         if (!DMA) st.store(hsm, 0, tid);
         __syncthreads();                                        // (with DMA in flight the barrier's fence waits vmcnt(0))
+        ABL::stamp(2);                                          // stamp 2 + u: super-tile u is ready (u + 1 = its end)
         acc A[NQB], B[NQB];
-        for (int tix = 0; tix < tile1 - tile0; ++tix) {
-            const int buf = tix & 1;
-            const uint4* tb = hsm + (buf * H_TT + r) * R::LDS_ROW16 + h;
+        for (int u = 0; u < (ntl + S - 1) / S; ++u) {
+            const int buf = u & 1;
             constexpr unsigned G = R::GPB;
-            const unsigned lb = static_cast<unsigned>(tix) * (4u * G);     // group ids of this tile: lb + GPB*blk + g
-            // the last tile is simply staged again: past the end nothing reads the other buffer
+            // S = 1: the last tile is simply staged again: past the end nothing reads the other buffer
             if constexpr (!ABL::no_stage) {
-                // the other buffer was last read in tile tix - 1, and every wave has passed that tile's barrier
-                if (DMA) {
-                    dma.issue(t_rsrc, tile0 + tix + 1 < ntiles ? tile0 + tix + 1 : tile0 + tix, hsm, buf ^ 1, wave);
-                    seed_issue(tile0 + tix + 1 < ntiles ? tile0 + tix + 1 : tile0 + tix, buf ^ 1);
-                } else st.load(Th, tile0 + tix + 1 < ntiles ? tile0 + tix + 1 : tile0 + tix, tid);
+                // the other buffer was last read in super-tile u - 1, and every wave has passed that super-tile's barrier
+                if (DMA) super_issue(u + 1, buf ^ 1);
+                else st.load(Th, tile0 + u + 1 < ntiles ? tile0 + u + 1 : tile0 + u, tid);
             }
-            const uint4* sb = ssm + 64 * buf + 4 * h;             // block b of the tile: sb + 8 * b
             if constexpr (GR == 1) {
-                if (tix == 0) h_block<R, NQB, false, ABL>(tb, sb, qf, A, A, 0u, par, cl);
-                else h_block<R, NQB, true, ABL>(tb, sb, qf, A, B, lb - G, par, cl);                 // B = block 3 of tile-1
-                h_block<R, NQB, true, ABL>(tb + 32 * R::LDS_ROW16, sb + 8, qf, B, A, lb, par, cl);
-                h_block<R, NQB, true, ABL>(tb + 64 * R::LDS_ROW16, sb + 16, qf, A, B, lb + G, par, cl);
-                if constexpr (!ABL::no_stage) {
-                    if (!DMA) st.store(hsm, buf ^ 1, tid);
+#pragma unroll
+                for (int i = 0; i < S; ++i) {
+                    const int tix = S * u + i;
+                    if (S > 1 && tix >= ntl) break;                      // partial last super-tile (workgroup-uniform)
+                    const uint4* tb = hsm + ((buf * S + i) * H_TT + r) * R::LDS_ROW16 + h;
+                    const uint4* sb = ssm + 64 * (buf * S + i) + 4 * h;  // block b of the tile: sb + 8 * b
+                    const unsigned lb = static_cast<unsigned>(tix) * (4u * G);     // group ids of this tile: lb + GPB*blk + g
+                    if (tix == 0) h_block<R, NQB, false, ABL>(tb, sb, qf, A, A, 0u, par, cl);
+                    else h_block<R, NQB, true, ABL>(tb, sb, qf, A, B, lb - G, par, cl);             // B = block 3 of tile-1
+                    h_block<R, NQB, true, ABL>(tb + 32 * R::LDS_ROW16, sb + 8, qf, B, A, lb, par, cl);
+                    h_block<R, NQB, true, ABL>(tb + 64 * R::LDS_ROW16, sb + 16, qf, A, B, lb + G, par, cl);
+                    if constexpr (!ABL::no_stage) {
+                        if (!DMA) st.store(hsm, buf ^ 1, tid);
+                    }
+                    h_block<R, NQB, true, ABL>(tb + 96 * R::LDS_ROW16, sb + 24, qf, B, A, lb + 2u * G, par, cl);
                 }
-                h_block<R, NQB, true, ABL>(tb + 96 * R::LDS_ROW16, sb + 24, qf, B, A, lb + 2u * G, par, cl);
             } else {
+                const int tix = u;
+                const uint4* tb = hsm + (buf * H_TT + r) * R::LDS_ROW16 + h;
+                const uint4* sb = ssm + 64 * buf + 4 * h;
+                const unsigned lb = static_cast<unsigned>(tix) * (4u * G);
                 // this group's blocks 2*grp and 2*grp + 1 of the tile (group ids lb + G*block + g, as above)
                 const uint4* tg = tb + grp * 64 * R::LDS_ROW16;
                 const uint4* sg = sb + 16 * grp;
@@ -795,6 +833,7 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
                 h_block<R, NQB, true, ABL>(tg + 32 * R::LDS_ROW16, sg + 8, qf, B, A, gb, par, cl);
             }
             tile_barrier<ABL>();
+            if (u < 13) ABL::stamp(3 + u);
         }
         const unsigned lb = static_cast<unsigned>(tile1 - tile0 - 1) * (4u * R::GPB) +
                             (GR == 1 ? 3u : 2u * static_cast<unsigned>(grp) + 1u) * R::GPB;
@@ -803,6 +842,7 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
 #pragma unroll
             for (int g = 0; g < R::GPB; ++g) R::select(B[qb], par, (lb + static_cast<unsigned>(g)) << 1, cl[qb], g);
     }
+    ABL::stamp(16);
     if constexpr (GR == 2) {
         // the two row groups' lists of a query meet in LDS (the tile buffers are idle: every wave is past the last
         // tile's barrier, whose fence also drained the LDS-DMA)
@@ -834,6 +874,7 @@ __global__ __launch_bounds__(H_QB / (32 * NQB) * 64 * GR, (R::NCH > 9 ? (NQB == 
             if (q < nq) cand_val[(static_cast<size_t>(q) * slots + (wg.split * 2 + h) * KNN_C) / KNN_C] = cl[qb];
         }
     }
+    ABL::stamp(17);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1105,28 +1146,41 @@ int coarse_f32_dispatch(pm_ctx* ctx, const float* dq, int nq, const float* dt, i
 #undef PM_LAUNCH_MFMA
 }
 
+// st: 128-row tiles per super-tile (1, 2, 4; u8 route only, see knn_mfma_rows288)
 template <typename R, typename ABL>
 int launch_rows288(pm_ctx* ctx, const char* name, const void* Qh, const void* Th, const void* seeds, int nq, int nq_pad, int nt,
                    int splits, int tiles_per_split, unsigned par, void* cval, int slots, const unsigned long long* stats,
-                   unsigned epoch, int mode)
+                   unsigned epoch, int mode, int st = 1)
 {
-    const size_t lds = sizeof(uint4) * (2 * H_TT * R::LDS_ROW16 + (R::SEEDED ? 2 * 64 : 0));
+    constexpr bool SUPER = std::is_same<R, RouteU8T<2>>::value;      // the u8 route with its default 8-row groups
+    PM_REQUIRE(st == 1 || (SUPER && (st == 2 || st == 4)), PM_E_INVALID, "super-tiles exist for the u8 route's 8-row groups only");
+    auto lds_of = [](int s_) { return sizeof(uint4) * s_ * (2 * H_TT * R::LDS_ROW16 + (R::SEEDED ? 2 * 64 : 0)); };
+    static_assert(!SUPER || 4 * sizeof(uint4) * (2 * H_TT * R::LDS_ROW16 + 2 * 64) <= 160 * 1024, "S = 4 exceeds the CU's LDS");
     // few tiles per workgroup: the 8-wave form covers latency better; long sweeps: the 4-wave form halves LDS reads
     const int nqb_opt = ctx->opts[PM_OPT_KNN_F16_WAVES];
     const int nqb = nqb_opt ? nqb_opt : (tiles_per_split <= 8 ? 1 : 2);          // 3: two row groups of 4 waves x 64 queries
+    if (nqb == 3) st = 1;                                                         // (the two-row-group form has no super-tiles)
+    const size_t lds = lds_of(st);
+    if constexpr (SUPER) {                                       // a super-tile form is timed (kernels_us) under a name of its own
+        if (st == 2) name = "knn_l2_mfma_u8_s2";
+        if (st == 4) name = "knn_l2_mfma_u8_s4";
+    }
     static bool attr_done_dev[PM_MAX_DEVICES] = {};          // the attribute is per device (and per template instance)
     bool& attr_done = attr_done_dev[ctx->device];
     if (!attr_done) {
-#define PM_ATTR(NQB_, DMA_, GR_)                                                                                  \
-    PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_mfma_rows288<R, NQB_, DMA_, GR_, ABL>),        \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)))
+#define PM_ATTR_S(NQB_, DMA_, GR_, S_)                                                                            \
+    PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_mfma_rows288<R, NQB_, DMA_, GR_, S_, ABL>),    \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_of(S_))))
+#define PM_ATTR(NQB_, DMA_, GR_) PM_ATTR_S(NQB_, DMA_, GR_, 1)
         PM_ATTR(1, true, 1); PM_ATTR(2, true, 1);
+        if constexpr (SUPER) { PM_ATTR_S(1, true, 1, 2); PM_ATTR_S(2, true, 1, 2); PM_ATTR_S(1, true, 1, 4); PM_ATTR_S(2, true, 1, 4); }
         if constexpr (!R::SEEDED) { PM_ATTR(1, false, 1); PM_ATTR(2, false, 1); }
         if constexpr (R::MERGE) {
             PM_ATTR(2, true, 2);
             if constexpr (!R::SEEDED) PM_ATTR(2, false, 2);
         }
 #undef PM_ATTR
+#undef PM_ATTR_S
         attr_done = true;
     }
     pm::ScopedKernelTime t(ctx, name);
@@ -1140,9 +1194,19 @@ int launch_rows288(pm_ctx* ctx, const char* name, const void* Qh, const void* Th
     // the seeded routes exist in the DMA form only: their callers check rows288_dma_ok first)
     const bool dma = R::SEEDED || (ctx->opts[PM_OPT_KNN_STAGING] != 1 && rows288_dma_ok<R>(nt));
     PM_REQUIRE(!R::SEEDED || rows288_dma_ok<R>(nt), PM_E_UNSUPPORTED, "train set too large for the seeded coarse routes");
-#define PM_GO(NQB_, DMA_, GR_, THREADS_)                                                                           \
-    hipLaunchKernelGGL((knn_mfma_rows288<R, NQB_, DMA_, GR_, ABL>), dim3(nq_pad / H_QB, splits), dim3(THREADS_), lds,  \
+#define PM_GOS(NQB_, DMA_, GR_, S_, THREADS_)                                                                      \
+    hipLaunchKernelGGL((knn_mfma_rows288<R, NQB_, DMA_, GR_, S_, ABL>), dim3(nq_pad / H_QB, splits), dim3(THREADS_), lds, \
                        ctx->stream, q4, t4, s4, nq, nt, tiles_per_split, par, out, slots, stats, epoch, mode)
+#define PM_GO(NQB_, DMA_, GR_, THREADS_)                                                                           \
+    do {                                                                                                           \
+        if constexpr (SUPER && GR_ == 1) {                                                                         \
+            if (st == 4) PM_GOS(NQB_, true, 1, 4, THREADS_);                                                       \
+            else if (st == 2) PM_GOS(NQB_, true, 1, 2, THREADS_);                                                  \
+            else PM_GOS(NQB_, true, 1, 1, THREADS_);                                                               \
+        } else {                                                                                                   \
+            PM_GOS(NQB_, DMA_, GR_, 1, THREADS_);                                                                  \
+        }                                                                                                          \
+    } while (0)
 #define PM_GO2(NQB_, GR_, THREADS_)                                                                                \
     do {                                                                                                           \
         if constexpr (R::SEEDED) { PM_GO(NQB_, true, GR_, THREADS_); }                                             \
@@ -1161,6 +1225,7 @@ int launch_rows288(pm_ctx* ctx, const char* name, const void* Qh, const void* Th
     else PM_GO2(1, 1, 512);
 #undef PM_GO2
 #undef PM_GO
+#undef PM_GOS
     PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
 }
@@ -1574,8 +1639,8 @@ int launch_rega(pm_ctx* ctx, const char* name, const void* Q8, const void* T8, c
 
 // u8 route: group size (rows per candidate group) x staging form
 template <typename ABL>
-int coarse_u8_dispatch(pm_ctx* ctx, const void* Q8, const void* T8, const int* seeds, int nq, int nq_pad, int nt, int splits,
-                       int tiles_per_split, int* cval, int slots, int group_rows, int form)
+int coarse_u8_dispatch(pm_ctx* ctx, const void* Q8, const void* Qf, const void* T8, const int* seeds, int nq, int nq_pad, int nt,
+                       int splits, int tiles_per_split, int* cval, int slots, int group_rows, int form)
 {
     // form: 0 / 1 two LDS tile buffers, 2 / 3 ring of eight, 4 / 5 / 6 register-operand forms (the caller sized the grid
     // and the splits for 128 queries per workgroup); 2 .. 6 exist for the default group size only
@@ -1583,9 +1648,17 @@ int coarse_u8_dispatch(pm_ctx* ctx, const void* Q8, const void* T8, const int* s
         return launch_rega<2, ABL>(ctx, "knn_l2_mfma_u8", Q8, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, cval, slots, form);
     if (form >= 2 && group_rows == 8)
         return launch_ring<RouteU8T<2>, 8, ABL>(ctx, "knn_l2_mfma_u8", Q8, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, 0u, cval, slots);
+    // two-buffer form: 128-row tiles per super-tile (PM_OPT_KNN_SUPERTILE 1 / 2 / 3 = 1 / 2 / 4).  Automatic: 1.  Measured
+    // (DESIGN.md 2.1): a tile that issues DMA costs the same ~1800 cycles whether the waves meet after every tile or every
+    // second or fourth one, and the wait for the first tile stays ~1.2k cycles; only tiles that issue no DMA (the last
+    // super-tile) are cheaper (~1550), so workgroup lifetimes at C3 are equal within 3 %; at 32k x 32k the larger LDS
+    // footprint costs co-residency: C3 13.4-13.9 / 13.1-13.9 / 13.2-14.7 us, 32k 115 / 119-121 / 146-151 us for S = 1 / 2 / 4.
+    const int st_opt = group_rows == 8 ? ctx->opts[PM_OPT_KNN_SUPERTILE] : 0;     // (8-row groups only)
+    const int st = st_opt == 3 ? 4 : (st_opt == 2 ? 2 : 1);
+    PM_REQUIRE(Qf != nullptr, PM_E_INVALID, "the two-buffer u8 form reads the query copy in B-fragment order");
 #define PM_U8(GPB_)                                                                                                        \
-    launch_rows288<RouteU8T<GPB_>, ABL>(ctx, "knn_l2_mfma_u8", Q8, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, 0u, cval,   \
-                                        slots, nullptr, 0u, 0)
+    launch_rows288<RouteU8T<GPB_>, ABL>(ctx, "knn_l2_mfma_u8", Qf, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, 0u, cval,   \
+                                        slots, nullptr, 0u, 0, st)
     if (group_rows == 16) return PM_U8(1);
     if (group_rows == 8) return PM_U8(2);
     return PM_U8(4);

@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q,
                                                     float* __restrict__ qnorm, float* __restrict__ tnorm,
                                                     uint2* __restrict__ Q8, uint2* __restrict__ T8,
                                                     int* __restrict__ seeds, unsigned long long* __restrict__ stats,
-                                                    unsigned epoch, int t_wide)
+                                                    unsigned epoch, int t_wide, uint2* __restrict__ Qf)
 {
     __shared__ unsigned wbad[4];
     const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
@@ -377,6 +377,7 @@ __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q,
         for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
         if (!okrow) bad |= 2u;
         x8[static_cast<size_t>(row) * ((is_t && t_wide) ? U8_WIDE_ROW16 * 2 : U8_DP / 8) + sub] = uint2{w[0], w[1]};
+        if (!is_t && Qf) Qf[u8_qfrag_index2(row, sub)] = uint2{w[0], w[1]};      // (the coarse kernel's B-fragment order)
         if (sub == 0) {
             const int si = static_cast<int>(s);
             if (is_t) {
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256) void knn_l2_prep8_u8(const uint8_t* __restrict
                                                        const uint8_t* __restrict__ T, int nt, int nt_pad, int dim,
                                                        float* __restrict__ qnorm, float* __restrict__ tnorm,
                                                        uint2* __restrict__ Q8, uint2* __restrict__ T8, int* __restrict__ seeds,
-                                                       int t_wide)
+                                                       int t_wide, uint2* __restrict__ Qf)
 {
     const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const int qblocks = nq_pad / 64;
@@ -440,6 +441,7 @@ __global__ __launch_bounds__(256) void knn_l2_prep8_u8(const uint8_t* __restrict
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) si += __shfl_xor(si, o, 16);
         x8[static_cast<size_t>(row) * ((is_t && t_wide) ? U8_WIDE_ROW16 * 2 : U8_DP / 8) + sub] = uint2{w[0], w[1]};
+        if (!is_t && Qf) Qf[u8_qfrag_index2(row, sub)] = uint2{w[0], w[1]};
         if (sub == 0) {
             if (is_t) {
                 seeds[seed_pos(row)] = live ? -(si >> 1) : U8_PAD_SEED;
@@ -1820,10 +1822,12 @@ int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt
     const int t_wide = (u8r && u8_form >= 5) ? 1 : 0;            // 144-byte train rows with the seeds in the pad slots (knn_u8_rega)
     const size_t th = want16 ? (t_wide ? static_cast<size_t>(U8_WIDE_ROW16) * 16 : rowb) * static_cast<size_t>(nt_pad) : 0;
     const size_t sdb = (u8r || f16s) ? 4 * static_cast<size_t>(nt_pad + H_TT) : 0;       // seeds (+ one tile of slack)
+    // u8 route, two-buffer coarse form (the only one that reads it): the query copy in B-fragment order too
+    const size_t qfb = (u8r && u8_form <= 1) ? qh : 0;
     const size_t pkb = fuse ? sizeof(unsigned long long) * static_cast<size_t>(nq) : 0;
     const size_t need = pm::align_up(sizeof(float) * nq, 256) + pm::align_up(sizeof(float) * nt, 256) +
                         pm::align_up(c32, 256) + pm::align_up(c16, 256) + pm::align_up(qh, 256) + pm::align_up(th, 256) +
-                        pm::align_up(sdb, 256) + pm::align_up(pkb, 256) + 2048;
+                        pm::align_up(sdb, 256) + pm::align_up(pkb, 256) + pm::align_up(qfb, 256) + 2048;
     int rc = pm::arena_reserve(ctx, need);
     if (rc != PM_OK) return rc;
     pm::arena_reset(ctx);
@@ -1834,8 +1838,9 @@ int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt
     _Float16* Qh = want16 ? static_cast<_Float16*>(pm::arena_take(ctx, qh)) : nullptr;
     _Float16* Th = want16 ? static_cast<_Float16*>(pm::arena_take(ctx, th)) : nullptr;
     void* seeds = sdb ? pm::arena_take(ctx, sdb) : nullptr;
-    PM_REQUIRE(qnorm && tnorm && (!want32 || cval32) && (!want16 || (cval16 && Qh && Th)) && (!sdb || seeds), PM_E_NOMEM,
-               "scratch arena too small");
+    void* Qf = qfb ? pm::arena_take(ctx, qfb) : nullptr;
+    PM_REQUIRE(qnorm && tnorm && (!want32 || cval32) && (!want16 || (cval16 && Qh && Th)) && (!sdb || seeds) && (!qfb || Qf),
+               PM_E_NOMEM, "scratch arena too small");
     KnnFuse fz{};
     if (fuse) {
         fz = *fuse;
@@ -1864,15 +1869,15 @@ int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         if (u8in)
             hipLaunchKernelGGL(knn_l2_prep8_u8, dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, uq, nq, nq_pad, ut, nt,
                                nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), t_wide);
+                               static_cast<int*>(seeds), t_wide, static_cast<uint2*>(Qf));
         else if (u8r && ctx->opts[PM_OPT_KNN_PREP_ROWS] != 1)      // 16 rows per workgroup: matcher call 23.5 -> 22.2 us at C3, 15.1 -> 14.2 at C2
             hipLaunchKernelGGL(knn_l2_prep8<1>, dim3(nq_pad / 16 + nt_pad / 16), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt,
                                nt, nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), stats, epoch, t_wide);
+                               static_cast<int*>(seeds), stats, epoch, t_wide, static_cast<uint2*>(Qf));
         else if (u8r)
             hipLaunchKernelGGL(knn_l2_prep8<4>, dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt,
                                nt, nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), stats, epoch, t_wide);
+                               static_cast<int*>(seeds), stats, epoch, t_wide, static_cast<uint2*>(Qf));
         else if (f16s)
             hipLaunchKernelGGL((knn_l2_prep16<true, 128, true>), dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq,
                                nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm, Qh, Th, static_cast<float*>(seeds), stats, epoch);
@@ -1910,7 +1915,7 @@ int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         PM_HIP_CHECK(hipGetLastError());
     }
     if (u8r) {
-        rc = launch_coarse_u8(ctx, Qh, Th, static_cast<const int*>(seeds), nq, nq_pad, nt, splits16, g16.tiles_per_split,
+        rc = launch_coarse_u8(ctx, Qh, Qf, Th, static_cast<const int*>(seeds), nq, nq_pad, nt, splits16, g16.tiles_per_split,
                               reinterpret_cast<int*>(cval16), g16.slots, u8_group, u8_form);
         if (rc != PM_OK) return rc;
     } else if (f16s) {

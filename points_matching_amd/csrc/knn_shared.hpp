@@ -68,6 +68,15 @@ __host__ __device__ inline int seed_pos(int row)
     return (row & ~31) + 16 * ((i >> 2) & 1) + (i & 3) + 4 * (i >> 3);
 }
 
+// Query copy of the u8 two-buffer coarse kernel in B-FRAGMENT order: for every block of 32 queries, k-chunk c and lane
+// l = 32h + r, the 16 bytes that lane l of a wave holds as its chunk-c B operand (query 32*blk + r, bytes 32c + 16h ..
+// + 15).  A wave's fragment load of one chunk is then 1 KiB of contiguous memory (8 cache lines) instead of 32 lines.
+// Index, in 8-byte units, of bytes 8*sub .. 8*sub + 7 of query row `row`:
+__host__ __device__ inline size_t u8_qfrag_index2(int row, int sub)
+{
+    return ((static_cast<size_t>(row >> 5) * U8_NCH + (sub >> 2)) * 64 + ((sub >> 1) & 1) * 32 + (row & 31)) * 2 + (sub & 1);
+}
+
 // "wide" train rows of the register-operand coarse form with a split per wave (knn_u8_rega<.., WSPLIT>): 144 bytes = the
 // LDS image of a row, so a 32-row block is 4.5 KiB of contiguous memory that LDS-DMA copies as it is; the 16-byte pad slot
 // of row j < 8 of a block holds the block's seeds at seed-order positions 4j .. 4j+3 (a lane half's 16 C-in values are
@@ -85,8 +94,9 @@ __host__ __device__ inline size_t u8_wide_seed_index(int row)           // index
 // group_rows: rows per candidate group (4, 8 or 16); form: 0 / 1 two LDS tile buffers, 2 / 3 ring of 8 LDS tile buffers
 // with counted waits, 4 / 5 / 6 the register-operand forms (grid and splits sized for 128 queries per workgroup; 6: one
 // split per WAVE, grid.y = ceil(splits / 8)).
-int launch_coarse_u8(pm_ctx* ctx, const void* Q8, const void* T8, const int* seeds, int nq, int nq_pad, int nt, int splits,
-                     int tiles_per_split, int* cval, int slots, int group_rows, int form);
+// Qf: the query copy in B-fragment order (u8_qfrag_index2), read by the two-buffer form (form 0 / 1) instead of Q8.
+int launch_coarse_u8(pm_ctx* ctx, const void* Q8, const void* Qf, const void* T8, const int* seeds, int nq, int nq_pad, int nt,
+                     int splits, int tiles_per_split, int* cval, int slots, int group_rows, int form);
 int launch_coarse_f16s(pm_ctx* ctx, const _Float16* Qh, const _Float16* Th, const float* seeds, int nq, int nq_pad, int nt,
                        int splits, int tiles_per_split, unsigned keep_mask, float* cval, int slots);
 

@@ -1,11 +1,12 @@
 // knn_coarse_stamps.hip — diagnostic build of the coarse kNN kernels with in-kernel shader-clock stamps (MI355X guide,
-// "In-kernel stamps"): where a workgroup of the ring kernel (csrc/knn_coarse_kernels.hpp: knn_mfma_ring) spends its
-// cycles.  This translation unit replaces csrc/knn_coarse.hip in a library of its own (tools/build_stamps.sh); it
+// "In-kernel stamps"): where a workgroup of the u8 coarse kernels (csrc/knn_coarse_kernels.hpp: knn_mfma_rows288,
+// knn_mfma_ring, knn_u8_rega) spends its cycles.  This translation unit replaces csrc/knn_coarse.hip in a library of its own (tools/build_stamps.sh); it
 // instantiates the same kernel bodies with a stamping policy and exports the read-back entry point
 // tools/prof_knn_stamps.py uses.  Never part of libpm_hip.so; the stamps go to a buffer nothing else reads.
 #include "knn_coarse_kernels.hpp"
 
-// [workgroup][slot]: 0 entry, 1 requests issued, 2 + t tile t's barrier passed (t < 14), 16 sweep done, 17 lists stored,
+// [workgroup][slot]: 0 entry, 1 requests issued, 2 + t tile (two-buffer form: super-tile) t ready (t < 14), 16 sweep done, 17 lists
+// stored, 18 / 19 two-buffer kernel: arguments and rsrc set up / first DMA issued,
 // 20 / 21 s_memrealtime at entry / exit (100 MHz, chip-wide), 22 XCC id
 __device__ unsigned long long g_knn_stamps[4096 * 24];
 
@@ -65,10 +66,10 @@ int launch_coarse_i8(pm_ctx* ctx, const void* Qe, const void* Te, int nq, int nq
                                             0u, cval, slots, nullptr, 0u, 0);
 }
 
-int launch_coarse_u8(pm_ctx* ctx, const void* Q8, const void* T8, const int* seeds, int nq, int nq_pad, int nt, int splits,
-                     int tiles_per_split, int* cval, int slots, int group_rows, int form)
+int launch_coarse_u8(pm_ctx* ctx, const void* Q8, const void* Qf, const void* T8, const int* seeds, int nq, int nq_pad, int nt,
+                     int splits, int tiles_per_split, int* cval, int slots, int group_rows, int form)
 {
-    return coarse_u8_dispatch<AblStamp>(ctx, Q8, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, cval, slots, group_rows, form);
+    return coarse_u8_dispatch<AblStamp>(ctx, Q8, Qf, T8, seeds, nq, nq_pad, nt, splits, tiles_per_split, cval, slots, group_rows, form);
 }
 
 int launch_coarse_f16s(pm_ctx* ctx, const _Float16* Qh, const _Float16* Th, const float* seeds, int nq, int nq_pad, int nt,

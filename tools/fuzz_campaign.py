@@ -75,7 +75,9 @@ def l2_case(i):
                 A.PM_OPT_KNN_SEEDED: int(rng.integers(0, 3)), A.PM_OPT_KNN_U8_GROUP: int(rng.integers(0, 4)),
                 A.PM_OPT_KNN_RING: int(rng.integers(0, 7)), A.PM_OPT_KNN_U8_REFINE: int(rng.integers(0, 3)),
                 A.PM_OPT_KNN_RING_PROLOGUE: int(rng.integers(0, 9)), A.PM_OPT_KNN_WIDE: int(rng.integers(0, 3)),
-                A.PM_OPT_KNN_PREP_ROWS: int(rng.integers(0, 3))}
+                A.PM_OPT_KNN_PREP_ROWS: int(rng.integers(0, 3)),
+                # u8 two-buffer coarse kernel: 128-row tiles per super-tile
+                A.PM_OPT_KNN_SUPERTILE: int(rng.integers(0, 4))}
     u8_valued = q.size and t.size and q.min() >= 0 and q.max() <= 255 and t.min() >= 0 and t.max() <= 255 and \
         bool((q == np.rint(q)).all()) and bool((t == np.rint(t)).all())
     try:

@@ -1,6 +1,8 @@
-"""Timeline of the u8 ring coarse kernel from in-kernel stamps (diagnostic build: tools/build_stamps.sh).
-    PM_LIB_PATH=points_matching_amd/build/abl/libpm_knnstamps.so python tools/prof_knn_stamps.py [nq nt]
-Prints, over the workgroups of the last launch: dispatch spread, cycles to the first tile, per-tile cycles, tail."""
+"""Timeline of the u8 coarse kernels from in-kernel stamps (diagnostic build: tools/build_stamps.sh).
+    PM_LIB_PATH=points_matching_amd/build/abl/libpm_knnstamps.so python tools/prof_knn_stamps.py [nq nt [option=value ...]]
+Stamped forms: the two-buffer tile kernel (default, 12=1; 20=1/2/3 = 1/2/4 tiles per super-tile), the ring forms (12=2 /
+12=3) and the register-operand forms (12=5 / 12=6).  Prints, over the workgroups of the last launch: dispatch spread,
+cycles to the first (super-)tile being ready, cycles per (super-)tile, tail."""
 import ctypes as C
 import os
 import sys
@@ -40,7 +42,8 @@ lib.pm_debug_knn_stamps(buf.ctypes.data_as(C.c_void_p), buf.size)
 s = buf.reshape(4096, 24).astype(np.int64)
 s = s[s[:, 0] != 0]
 if s.shape[0] == 0:
-    print("this coarse-kernel form carries no stamps (the ring forms 12=2 / 12=3 and the register-operand forms 12=5 / 12=6 do)")
+    print("this coarse-kernel form carries no stamps (the two-buffer form 12=1, the ring forms 12=2 / 12=3 and the register-operand "
+          "forms 12=5 / 12=6 do)")
     sys.exit(0)
 rega = any(o.startswith("12=") and int(o[3:]) >= 4 for o in opts)
 rt0, rt1 = s[:, 20], s[:, 21]
@@ -55,8 +58,22 @@ def show(name, a, b):
     if ok.any():
         d = d[ok]
         print("  %-34s median %7d  p90 %7d  max %7d cycles" % (name, np.median(d), np.percentile(d, 90), d.max()))
+two_buf = not rega and (s[:, 18] != 0).any()   # two-buffer tile kernel (only it writes slots 18 / 19)
+if two_buf:
+    show("entry -> arguments, rsrc set up", 0, 18)
+    show("rsrc set up -> first DMA issued", 18, 19)
+    show("DMA issued -> query fragments issued", 19, 1)
 show("entry -> %s" % ("query fragments loaded" if rega else "requests issued"), 0, 1)
-if not rega:
+if two_buf:
+    # slot 2 + u: super-tile u is ready (2: the first barrier passed; 3 + u: the barrier that ends super-tile u passed)
+    S = {2: 2, 3: 4}.get(next((int(o[3:]) for o in opts if o.startswith("20=")), 1), 1)
+    show("requests issued -> %s 0 ready" % ("super-tile" if S > 1 else "tile"), 1, 2)
+    nst = int(((s[0, 2:16]) != 0).sum()) - 1
+    for u in range(nst):
+        show("%s %d (%d rows, ready to ready)" % ("super-tile" if S > 1 else "tile", u, 128 * S), 2 + u, 3 + u)
+    show("final selection", 2 + nst, 16)
+elif not rega:
+    # ring kernel: slot 2 + t = tile t is ready
     show("requests issued -> tile 0 ready", 1, 2)
     ntl = int(((s[0, 2:16]) != 0).sum())
     for t in range(1, ntl):
