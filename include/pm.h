@@ -525,6 +525,72 @@ int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, con
                      const pm_ransac_params* p, double dist, double E[9], double R[9], double t[3], uint8_t* mask,
                      int* n_inliers, int* n_good, uint64_t* best_key);
 
+/* ---- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P: locating a new frame against 3-D points that are
+ * already known, e.g. those pm_recover_pose triangulates) — docs/SPEC.md S36-S39.  Correspondence i is a world point
+ * xyz[3i .. 3i+2] and its pixel uv[2i .. 2i+1] (f32).  One pinhole pm_camera K, no distortion; K is invalid unless fx, fy > 0
+ * and all four values are finite.  Pose: x_cam = R X + t, pixel ~ K x_cam; R 9 doubles row-major, t 3 doubles.
+ * pm_ransac_params with error_kind = PM_ERR_REPROJ and thresh_px finite and > 0 (OpenCV's default reprojectionError is
+ * 8); sample h in [hyp_begin, hyp_end) draws 3 correspondences (S37) and the P3P solve (Grunert's quartic, S38) gives up
+ * to 4 candidates, model ids 4h + j; every candidate is scored with the squared pixel reprojection error
+ * ||uv - proj(R X + t)||^2 <= thresh_px^2, points behind the camera rejected (S39).  OpenCV picks one P3P candidate with a
+ * fourth point instead [recalled]; here all are scored.  Winner: most inliers, ties -> lowest id; the key is
+ * (inliers << 32) | (0xFFFFFFFF - id), so 4 * hyp_end <= 2^32 (and 4 * (hyp_end - hyp_begin) <= 2^31 - 1).  Statuses:
+ * PM_E_INVALID (bad K, threshold, range or error_kind, null params / points / outputs, null ctx), n < 4 -> PM_E_TOO_FEW,
+ * no valid candidate -> PM_E_NO_MODEL with R = 0, t = 0, mask = 0.  Graph capture: as the homography calls (no per-call
+ * state; the host forms synchronise).  pm_pnp_refine* (below) refines the pose on its inliers, pm_solve_pnp_ransac does
+ * both. */
+/* Plain arrays of correspondences on the device with an optional device-side count (clamped to [0, cap]; NULL: cap). */
+typedef struct pm_pnp_view {
+    const float*   xyz;     /* cap x 3 world points */
+    const float*   uv;      /* cap x 2 pixels */
+    const int32_t* count;
+    int32_t cap;
+    int32_t reserved;
+} pm_pnp_view;
+/* Host in, host out (cv::solvePnPRansac without its refinement).  mask (n bytes), n_inliers, best_key may be NULL. */
+int pm_ransac_pnp(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K, const pm_ransac_params* p,
+                  double R[9], double t[3], uint8_t* mask, int* n_inliers, uint64_t* best_key);
+/* All candidates of ONE sample id (0 <= hyp, 4 * hyp + 4 <= 2^32; p's range is ignored): Rt[4 * 12] (slot j = the j-th
+ * real root of S38: R then t, zero when unused), counts[j] = its inlier count (-1: unused slot), *n_models = valid slots.
+ * No valid candidate -> PM_E_NO_MODEL. */
+int pm_ransac_pnp_from_hyp(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K,
+                           const pm_ransac_params* p, int64_t hyp, double Rt[48], int32_t counts[4], int* n_models);
+/* Whole run on the device over a pm_pnp_view (count read on the device): writes *d_best_key, d_Rt (12 doubles: R, then
+ * t), d_mask[0..mask_len) (zero beyond n) and *d_n_inliers; n < 4 or no valid model leaves key 0, Rt = 0, mask = 0.
+ * All four output pointers are required. */
+int pm_ransac_pnp_run_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const pm_ransac_params* p,
+                          uint64_t* d_best_key, double* d_Rt, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers);
+/* ---- refinement of the absolute pose on its inliers (the final solvePnP(..., SOLVEPNP_ITERATIVE) that cv::solvePnPRansac
+ * runs on its inliers from the RANSAC pose [recalled]) — docs/SPEC.md S40.  Levenberg-Marquardt on the sum of squared
+ * pixel reprojection errors over mask[i] != 0 with 6 parameters (a Cayley rotation step, no transcendental function),
+ * sums in S23's fixed order, S24's Cholesky and damping; it runs only with at least 4 inliers and max_iters > 0 and
+ * accepts only cost decreases, so cost_out <= cost_in.  The mask is not recomputed.  max_iters in [0, 100] (OpenCV's
+ * ITERATIVE solver stops at 20 [recalled]).  Info: pm_h_refine_info, costs in px^2; status 0 = refined, 1 = kept the
+ * input (R_out, t_out = R_in, t_in bit for bit), 2 = the input pose is zero (no model).  One launch of one workgroup; the
+ * device forms keep no per-call state.  Host in, host out: outputs may alias the inputs; info may be NULL.  Statuses:
+ * PM_E_INVALID (bad K or max_iters, null arrays, null ctx), n < 4 -> PM_E_TOO_FEW (outputs = inputs), zero input pose ->
+ * PM_E_NO_MODEL. */
+int pm_pnp_refine(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K, const uint8_t* mask,
+                  const double R_in[9], const double t_in[3], int max_iters, double R_out[9], double t_out[3],
+                  pm_h_refine_info* info);
+/* Device form over a pm_pnp_view (count read on the device): chains after pm_ransac_pnp_run_dev with no host round trip.
+ * d_Rt_in / d_Rt_out: 12 doubles (R, then t), d_Rt_out may equal d_Rt_in; d_info may be NULL; data outcomes are reported
+ * in *d_info only. */
+int pm_pnp_refine_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const uint8_t* d_mask, const double* d_Rt_in,
+                      int max_iters, double* d_Rt_out, pm_h_refine_info* d_info);
+/* cv::solvePnPRansac in one call: pm_ransac_pnp, then the refinement of its winner on its mask, one synchronisation.
+ * mask / n_inliers / best_key as the RANSAC call (the RANSAC mask); R, t refined; info (may be NULL) the refinement's.
+ * Statuses as pm_ransac_pnp, plus max_iters outside [0, 100] -> PM_E_INVALID. */
+int pm_solve_pnp_ransac(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K, const pm_ransac_params* p,
+                        int max_iters, double R[9], double t[3], uint8_t* mask, int* n_inliers, uint64_t* best_key,
+                        pm_h_refine_info* info);
+/* The device chain's gather: the compacted match list of pm_bf_knn_l2_*_ratio_dev / pm_filter_ratio_gather_dev (records
+ * d_matches[0 .. n), n = *d_count clamped to [0, cap], d_count NULL: cap) into PnP rows: d_uv[i] = d_kp_xy[queryIdx] (the
+ * frame's keypoints), d_xyz[i] = d_obj_xyz[trainIdx] (the map's points).  The count passes through unchanged: the view
+ * {d_xyz, d_uv, d_count, cap} feeds pm_ransac_pnp_run_dev.  An index out of range gives a NaN row (never an inlier). */
+int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_kp_xy, int n_kp,
+                      const float* d_obj_xyz, int n_obj, float* d_uv, float* d_xyz);
+
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median
  * loop over 7-point minimal solves (main.cpp:95-98) [recalled].  Arithmetic: docs/SPEC.md S13-S15.

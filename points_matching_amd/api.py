@@ -56,6 +56,8 @@ EXPORTS = [
     "pm_estimate_affine",
     "pm_ransac_essential", "pm_ransac_essential_from_hyp", "pm_ransac_essential_run_dev", "pm_recover_pose",
     "pm_recover_pose_dev", "pm_estimate_pose",
+    "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
+    "pm_solve_pnp_ransac", "pm_gather_pnp_dev",
 ]
 
 
@@ -89,6 +91,11 @@ def _camera(K):
     if k.shape == (3, 3):
         return Camera(k[0, 0], k[1, 1], k[0, 2], k[1, 2])
     return Camera(*[float(v) for v in k.reshape(4)])
+
+
+class PnpView(C.Structure):
+    """pm_pnp_view: world points (cap x 3) and pixels (cap x 2) on the device with an optional device-side count."""
+    _fields_ = [("xyz", C.c_void_p), ("uv", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_int32), ("reserved", C.c_int32)]
 
 
 class HRefineInfo(C.Structure):
@@ -665,6 +672,85 @@ class Context:
                                              C.c_double(dist), _p(E), _p(R), _p(t), _p(mask), C.byref(ninl), C.byref(ng),
                                              C.byref(key)))
         return rc, E.reshape(3, 3), R.reshape(3, 3), t, mask[:n], ninl.value, ng.value, key.value
+
+    # -- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P, SPEC S36-S39) -------------------------------------
+    # xyz: n x 3 world points, uv: n x 2 pixels; K as for the calibrated pose.  R is returned as 3 x 3, t as 3 float64.
+    def ransac_pnp(self, xyz, uv, K, iters, thresh_px, seed, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """Samples [hyp_begin, iters).  Returns (status, R(3x3), t(3), mask, n_inliers, best_key); raises on anything other
+        than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
+        xyz, uv, n = _pnp_pair(xyz, uv)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        R, t = np.zeros(9, np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        rc = _outcome(lib().pm_ransac_pnp(self._h, _p(xyz), _p(uv), n, C.byref(_camera(K)), C.byref(prm), _p(R), _p(t),
+                                          _p(mask), C.byref(ninl), C.byref(key)))
+        return rc, R.reshape(3, 3), t, mask[:n], ninl.value, key.value
+
+    def ransac_pnp_from_hyp(self, xyz, uv, K, hyp, thresh_px, seed, kind=PM_ERR_REPROJ):
+        """All candidates of one sample id: (status, Rt(4 x 12: R row-major, then t), counts(4; -1 = unused slot),
+        n_models)."""
+        xyz, uv, n = _pnp_pair(xyz, uv)
+        prm = RansacParams(0, 0, seed, thresh_px, kind)
+        Rt = np.zeros(48, np.float64)
+        counts = np.zeros(4, np.int32)
+        nm = C.c_int()
+        rc = _outcome(lib().pm_ransac_pnp_from_hyp(self._h, _p(xyz), _p(uv), n, C.byref(_camera(K)), C.byref(prm),
+                                                   C.c_int64(hyp), _p(Rt), _p(counts), C.byref(nm)))
+        return rc, Rt.reshape(4, 12), counts, nm.value
+
+    def ransac_pnp_run_dev(self, view, K, hyp_begin, hyp_end, thresh_px, seed, dkey_ptr, dRt_ptr, dmask_ptr, mask_len,
+                           dninl_ptr, kind=PM_ERR_REPROJ):
+        """Device-resident run over a PnpView (count read on the device); outputs are device pointers (Rt: 12 doubles)."""
+        prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)
+        _check(lib().pm_ransac_pnp_run_dev(self._h, C.byref(view), C.byref(_camera(K)), C.byref(prm), C.c_void_p(dkey_ptr),
+                                           C.c_void_p(dRt_ptr), C.c_void_p(dmask_ptr), mask_len, C.c_void_p(dninl_ptr)))
+
+    def pnp_refine(self, xyz, uv, K, mask, R_in, t_in, max_iters=20):
+        """LM refinement of a pose on its inliers (SPEC S40): (status, R(3x3), t(3), HRefineInfo); raises on anything other
+        than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xyz, uv, n = _pnp_pair(xyz, uv)
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n:
+            raise ValueError("xyz, uv and mask must have the same length")
+        Rin = np.ascontiguousarray(R_in, np.float64).reshape(9)
+        tin = np.ascontiguousarray(t_in, np.float64).reshape(3)
+        R, t = np.zeros(9, np.float64), np.zeros(3, np.float64)
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_pnp_refine(self._h, _p(xyz), _p(uv), n, C.byref(_camera(K)), _p(mask), _p(Rin), _p(tin),
+                                          max_iters, _p(R), _p(t), C.byref(info)))
+        return rc, R.reshape(3, 3), t, info
+
+    def pnp_refine_dev(self, view, K, dmask_ptr, dRt_in_ptr, max_iters, dRt_out_ptr, dinfo_ptr=None):
+        """Device form over a PnpView; Rt: 12 doubles (R, then t); dinfo_ptr (32 bytes, H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_pnp_refine_dev(self._h, C.byref(view), C.byref(_camera(K)), C.c_void_p(dmask_ptr),
+                                       C.c_void_p(dRt_in_ptr), max_iters, C.c_void_p(dRt_out_ptr), C.c_void_p(dinfo_ptr)))
+
+    def solve_pnp_ransac(self, xyz, uv, K, iters, thresh_px, seed, max_iters=20, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """RANSAC-PnP + refinement, one synchronisation: (status, R(3x3), t(3), mask, n_inliers, best_key, HRefineInfo)."""
+        xyz, uv, n = _pnp_pair(xyz, uv)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        R, t = np.zeros(9, np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_solve_pnp_ransac(self._h, _p(xyz), _p(uv), n, C.byref(_camera(K)), C.byref(prm), max_iters,
+                                                _p(R), _p(t), _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
+        return rc, R.reshape(3, 3), t, mask[:n], ninl.value, key.value, info
+
+    def gather_pnp_dev(self, dmatches_ptr, dcount_ptr, cap, dkp_ptr, n_kp, dobj_ptr, n_obj, duv_ptr, dxyz_ptr):
+        """Compacted matches -> PnP rows on the device (uv = keypoint of queryIdx, xyz = map point of trainIdx)."""
+        _check(lib().pm_gather_pnp_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dkp_ptr),
+                                       n_kp, C.c_void_p(dobj_ptr), n_obj, C.c_void_p(duv_ptr), C.c_void_p(dxyz_ptr)))
+
+
+def _pnp_pair(xyz, uv):
+    """2D-3D correspondences as contiguous float32 (n, 3) and (n, 2) arrays, and n."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    if xyz.shape[0] != uv.shape[0]:
+        raise ValueError("xyz and uv must have the same length")
+    return xyz, uv, xyz.shape[0]
 
 
 class LmedsParams(C.Structure):

@@ -18,7 +18,8 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
            "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
-           "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "planar_estimators.cpp",
+           "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
+           "pnp_refine.hip", "planar_estimators.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
@@ -28,7 +29,12 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # lane-serial fp64 5-point solver (its 10 x 20 elimination matrix lives in scratch) and the one-workgroup pose
          # recovery: report their registers, scratch and spills
          "essential_solve.hip": ["-Rpass-analysis=kernel-resource-usage"],
-         "recover_pose.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "recover_pose.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # lane-serial fp64 P3P solver and the PnP scorer with its 5-plane LDS tile
+         "pnp_solve.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "ransac_p_fused.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # one 512-thread workgroup holding 28 fp64 partial sums per thread (S40)
+         "pnp_refine.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -233,32 +233,34 @@ __device__ __forceinline__ void detpoly(const Bz& B, double (&p)[11])
     for (int k = 0; k < 11; ++k) p[k] = p[k] + w[k];
 }
 
-// S33: real roots of the degree-10 p, ascending, by bracketing with the roots of its successive (monic) derivatives
-// and BISECT_STEPS bisection steps per sign change.  Returns their number.
-__device__ __forceinline__ int real_roots(const double (&p)[11], double (&roots)[10])
+// S33 step 6: real roots of the degree-DEG p (ascending coefficients), ascending, by bracketing with the roots of its
+// successive (monic) derivatives and BISECT_STEPS bisection steps per sign change.  Returns their number.  DEG = 10:
+// the 5-point solve; DEG = 4: the P3P quartic (pnp_core.hpp, S38).
+template <int DEG>
+__device__ __forceinline__ int real_roots(const double (&p)[DEG + 1], double (&roots)[DEG])
 {
-    const double c10 = p[10];
+    const double c10 = p[DEG];
     if (!(fabs(c10) > 0.0) || !(fabs(c10) < __builtin_inf())) return 0;
-    double D[11][10];
+    double D[DEG + 1][DEG];
     double mx = 0.0;
     bool fin = true;
 #pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        D[10][k] = p[k] / c10;
-        fin = fin && fabs(D[10][k]) < __builtin_inf();
-        if (fabs(D[10][k]) > mx) mx = fabs(D[10][k]);
+    for (int k = 0; k < DEG; ++k) {
+        D[DEG][k] = p[k] / c10;
+        fin = fin && fabs(D[DEG][k]) < __builtin_inf();
+        if (fabs(D[DEG][k]) > mx) mx = fabs(D[DEG][k]);
     }
     if (!fin) return 0;
     const double R = 1.0 + mx;
 #pragma unroll
-    for (int d = 10; d >= 2; --d)
+    for (int d = DEG; d >= 2; --d)
 #pragma unroll
         for (int k = 0; k < d - 1; ++k) D[d - 1][k] = D[d][k + 1] * (static_cast<double>(k + 1) / static_cast<double>(d));
-    double r[10], e[12];
+    double r[DEG], e[DEG + 2];
     int m = 1;
     r[0] = -D[1][0];
 #pragma unroll
-    for (int d = 2; d <= 10; ++d) {
+    for (int d = 2; d <= DEG; ++d) {
         e[0] = -R;
         for (int i = 0; i < m; ++i) e[i + 1] = r[i] < -R ? -R : (r[i] > R ? R : r[i]);
         e[m + 1] = R;
@@ -362,7 +364,7 @@ __device__ __forceinline__ int solve5(const double (&x1)[5], const double (&y1)[
     make_bz(A, Bm);
     double p[11], roots[10];
     detpoly(Bm, p);
-    const int nr = real_roots(p, roots);
+    const int nr = real_roots<10>(p, roots);
     int nv = 0;
     for (int j = 0; j < nr; ++j) {
         const double z = roots[j];

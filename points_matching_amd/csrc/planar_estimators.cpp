@@ -1,8 +1,10 @@
 // planar_estimators.cpp — the C-ABI entry points of the two planar model families of include/pm.h: the robust
 // homography (RANSAC-H, ransac_h_fused.hip, refined by homography_refine.hip) and the robust affine / similarity model
-// (RANSAC-A, ransac_a_fused.hip, refitted by affine_refine.hip).  Those files hold the kernels and one enqueue each;
-// here are the argument checks, the staging of host arrays and one driver for every host-pointer form: upload, RANSAC
-// and / or the refit on one stream, one readback into pinned memory, one synchronisation.
+// (RANSAC-A, ransac_a_fused.hip, refitted by affine_refine.hip); also the calibrated relative pose (RANSAC-E) and the
+// absolute pose (RANSAC-PnP, pnp_solve.hip + ransac_p_fused.hip, refined by pnp_refine.hip).  Those files hold the
+// kernels and one enqueue each; here are the argument checks, the staging of host arrays and one driver for every
+// host-pointer form: upload, RANSAC and / or the refit on one stream, one readback into pinned memory, one
+// synchronisation.
 #include <cmath>
 
 #include "affine_core.hpp"
@@ -459,6 +461,212 @@ int run_e_host(pm_ctx* ctx, int steps, const float* xy1, const float* xy2, int n
     return PM_OK;
 }
 
+// ---- absolute pose (RANSAC-PnP) -------------------------------------------------------------------------------------
+// S36 and the range, kind and threshold rules of S38 / S39, in this order
+int check_pnp(const pm_camera* K, const pm_ransac_params* p)
+{
+    PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
+    PM_REQUIRE(p->hyp_begin >= 0 && p->hyp_end > p->hyp_begin && p->hyp_end <= 0x100000000LL / 4, PM_E_INVALID,
+               "sample ids must satisfy 0 <= begin < end and 4 * end <= 2^32 (model ids 4h + j)");
+    PM_REQUIRE(4 * (p->hyp_end - p->hyp_begin) <= 0x7FFFFFFFLL, PM_E_INVALID,
+               "a single launch takes at most (2^31 - 1) / 4 samples: split the range");
+    PM_REQUIRE(p->error_kind == PM_ERR_REPROJ, PM_E_INVALID, "error_kind must be PM_ERR_REPROJ");
+    PM_REQUIRE(p->thresh_px > 0.0f && std::isfinite(p->thresh_px), PM_E_INVALID, "thresh_px must be finite and > 0");
+    PM_REQUIRE(K != nullptr, PM_E_INVALID, "K is null");
+    const bool fin = std::isfinite(K->fx) && std::isfinite(K->fy) && std::isfinite(K->cx) && std::isfinite(K->cy);
+    PM_REQUIRE(fin && K->fx > 0.0 && K->fy > 0.0, PM_E_INVALID, "K needs finite values and fx, fy > 0");
+    return PM_OK;
+}
+
+// The scorer's parameters: model ids [4 begin, 4 end)
+pm_ransac_params pnp_ids(const pm_ransac_params* p)
+{
+    pm_ransac_params q = *p;
+    q.hyp_begin = 4 * p->hyp_begin;
+    q.hyp_end = 4 * p->hyp_end;
+    return q;
+}
+
+// Arena bytes of a RANSAC-PnP run: candidates (80 doubles per sample), scorer slots
+size_t pnp_scratch_bytes(const pm_ctx* ctx, const pm_ransac_params* p)
+{
+    const pm_ransac_params q = pnp_ids(p);
+    return pm::align_up(sizeof(double) * 80 * static_cast<size_t>(p->hyp_end - p->hyp_begin), 256) +
+           fused_scratch_bytes(ctx, &q) + 1024;
+}
+
+// Solve + score on ctx->stream (the arena reserved for pnp_scratch_bytes; carved here).  With d_cand_out the scoring
+// launch is left to the caller, who receives the candidate buffer.
+int enqueue_pnp(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const pm_ransac_params* p,
+                unsigned long long* d_key, double* d_Rt, uint8_t* d_mask, int mask_len, int* d_ninl,
+                double** d_cand_out = nullptr)
+{
+    double* cand = static_cast<double*>(pm::arena_take(ctx, sizeof(double) * 80 * static_cast<size_t>(p->hyp_end - p->hyp_begin)));
+    PM_REQUIRE(cand, PM_E_NOMEM, "scratch arena too small");
+    int rc = pnp_solve_enqueue(ctx, v, K, p, cand);
+    if (rc != PM_OK) return rc;
+    if (d_cand_out) {
+        *d_cand_out = cand;
+        return PM_OK;
+    }
+    const pm_ransac_params q = pnp_ids(p);
+    return ransac_p_enqueue(ctx, v, &q, cand, d_key, d_Rt, d_mask, mask_len, d_ninl);
+}
+
+// The small results of a host-pointer call (the mask follows the pinned block)
+struct PResults {
+    unsigned long long key;
+    double Rt[12];
+    int32_t count;
+    int32_t pad;
+    unsigned long long keys[4];
+    double cand[80];
+    pm_h_refine_info info;
+};
+
+enum PStep { P_RANSAC = 1, P_REFINE = 2, P_CANDIDATES = 4 };
+
+struct PHostOut {
+    double* R;                  // 9
+    double* t;                  // 3
+    uint8_t* mask;              // n bytes
+    int* n_inliers;
+    uint64_t* best_key;
+    pm_h_refine_info* info;
+    double* Rt;                 // P_CANDIDATES: 48
+    int32_t* counts;            // P_CANDIDATES: 4
+    int* n_models;
+};
+
+// Driver of the host-pointer forms: RANSAC-PnP over p's samples (P_RANSAC) and / or the S40 refinement of its winner on
+// its mask or of (R_in, t_in) on mask_in (P_REFINE), or every candidate of p's one sample with its count
+// (P_CANDIDATES); one readback, one synchronisation.  Outputs are zeroed before the first check (refinement alone:
+// R, t = R_in, t_in and info status 1).
+int run_pnp_host(pm_ctx* ctx, int steps, const float* xyz, const float* uv, int n, const pm_camera* K,
+                 const pm_ransac_params* p, const uint8_t* mask_in, const double* R_in, const double* t_in, int max_iters,
+                 const PHostOut& out)
+{
+    const bool ransac = steps & (P_RANSAC | P_CANDIDATES), refine = steps & P_REFINE, cands = steps & P_CANDIDATES;
+    double in[12] = {};
+    if (!ransac) {
+        PM_REQUIRE(R_in && t_in && out.R && out.t, PM_E_INVALID, "null R or t");
+        memcpy(in, R_in, sizeof(double) * 9);
+        memcpy(in + 9, t_in, sizeof(double) * 3);
+    }
+    if (out.R) memcpy(out.R, in, sizeof(double) * 9);
+    if (out.t) memcpy(out.t, in + 9, sizeof(double) * 3);
+    if (out.mask && n > 0) memset(out.mask, 0, static_cast<size_t>(n));
+    if (out.n_inliers) *out.n_inliers = 0;
+    if (out.best_key) *out.best_key = 0;
+    if (out.info) *out.info = pm_h_refine_info{0.0, 0.0, 0, 0, ransac ? 2 : 1, 0};
+    if (out.Rt) memset(out.Rt, 0, sizeof(double) * 48);
+    if (out.counts) for (int j = 0; j < 4; ++j) out.counts[j] = -1;
+    if (out.n_models) *out.n_models = 0;
+    int rc = ransac ? check_pnp(K, p) : PM_OK;
+    if (rc != PM_OK) return rc;
+    if (!ransac) {
+        PM_REQUIRE(K != nullptr, PM_E_INVALID, "K is null");
+        const bool fin = std::isfinite(K->fx) && std::isfinite(K->fy) && std::isfinite(K->cx) && std::isfinite(K->cy);
+        PM_REQUIRE(fin && K->fx > 0.0 && K->fy > 0.0, PM_E_INVALID, "K needs finite values and fx, fy > 0");
+    }
+    if (refine) PM_REQUIRE(max_iters >= 0 && max_iters <= 100, PM_E_INVALID, "max_iters must lie in [0, 100]");
+    if (cands) PM_REQUIRE(out.Rt && out.counts, PM_E_INVALID, "null Rt or counts");
+    PM_REQUIRE(n >= 0 && (n == 0 || (xyz && uv && (ransac || mask_in))), PM_E_INVALID,
+               ransac ? "bad point arrays" : "bad point or mask arrays");
+    if (n < 4) {
+        pm::set_error("need at least 4 correspondences, got %d", n);
+        return PM_E_TOO_FEW;
+    }
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+
+    const size_t xb = sizeof(float) * 3 * static_cast<size_t>(n), ub = sizeof(float) * 2 * static_cast<size_t>(n);
+    rc = pm::arena_reserve(ctx, pm::align_up(xb, 256) + pm::align_up(ub, 256) + pm::align_up(static_cast<size_t>(n), 256) +
+                                    pm::align_up(sizeof(PResults), 256) + (ransac ? pnp_scratch_bytes(ctx, p) : 0) +
+                                    (cands ? 4 * 1024 : 0));
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    float* dxyz = static_cast<float*>(pm::arena_take(ctx, xb));
+    float* duv = static_cast<float*>(pm::arena_take(ctx, ub));
+    uint8_t* dmask = static_cast<uint8_t*>(pm::arena_take(ctx, static_cast<size_t>(n)));
+    PResults* dres = static_cast<PResults*>(pm::arena_take(ctx, sizeof(PResults)));
+    PM_REQUIRE(dxyz && duv && dmask && dres, PM_E_NOMEM, "scratch arena too small");
+    rc = pm::pinned_reserve(ctx, sizeof(PResults) + static_cast<size_t>(n));
+    if (rc != PM_OK) return rc;
+    PResults* hres = static_cast<PResults*>(ctx->pinned);
+    uint8_t* hmask = reinterpret_cast<uint8_t*>(hres + 1);
+
+    PM_HIP_CHECK(hipMemcpyAsync(dxyz, xyz, xb, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipMemcpyAsync(duv, uv, ub, hipMemcpyHostToDevice, ctx->stream));
+    if (!ransac) {
+        memcpy(hres->Rt, in, sizeof in);
+        PM_HIP_CHECK(hipMemcpyAsync(dres->Rt, hres->Rt, sizeof in, hipMemcpyHostToDevice, ctx->stream));
+        PM_HIP_CHECK(hipMemcpyAsync(dmask, mask_in, static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
+    }
+    const pm_points_view v{dxyz, duv, nullptr, 1, n, 0, 1, 0};
+    if (cands) {
+        double* dcand = nullptr;
+        rc = enqueue_pnp(ctx, v, *K, p, nullptr, nullptr, nullptr, 0, nullptr, &dcand);
+        if (rc != PM_OK) return rc;
+        // each candidate alone: model ids [4 hyp + j, 4 hyp + j + 1); its key holds its count
+        for (int j = 0; j < 4; ++j) {
+            pm_ransac_params q = pnp_ids(p);
+            q.hyp_begin += j;
+            q.hyp_end = q.hyp_begin + 1;
+            rc = ransac_p_enqueue(ctx, v, &q, dcand + 20 * j, &dres->keys[j], nullptr, dmask, 0, nullptr);
+            if (rc != PM_OK) return rc;
+        }
+        PM_HIP_CHECK(hipMemcpyAsync(dres->cand, dcand, sizeof(double) * 80, hipMemcpyDeviceToDevice, ctx->stream));
+    } else if (ransac) {
+        rc = enqueue_pnp(ctx, v, *K, p, &dres->key, dres->Rt, dmask, n, &dres->count);
+        if (rc != PM_OK) return rc;
+    }
+    if (refine) {
+        rc = pnp_refine_enqueue(ctx, v, *K, dmask, dres->Rt, max_iters, dres->Rt, &dres->info);
+        if (rc != PM_OK) return rc;
+    }
+    PM_HIP_CHECK(hipMemcpyAsync(hres, dres, sizeof(PResults), hipMemcpyDeviceToHost, ctx->stream));
+    if (ransac) PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+
+    if (cands) {
+        int nm = 0;
+        for (int j = 0; j < 4; ++j) {
+            if (hres->cand[20 * j + 12] == 0.0) continue;
+            memcpy(out.Rt + 12 * j, hres->cand + 20 * j, sizeof(double) * 12);
+            out.counts[j] = static_cast<int32_t>(hres->keys[j] >> 32);
+            ++nm;
+        }
+        if (out.n_models) *out.n_models = nm;
+        if (nm == 0) {
+            pm::set_error("no valid candidate (degenerate sample)");
+            return PM_E_NO_MODEL;
+        }
+        return PM_OK;
+    }
+    if (!ransac) {
+        memcpy(out.R, hres->Rt, sizeof(double) * 9);
+        memcpy(out.t, hres->Rt + 9, sizeof(double) * 3);
+        if (out.info) *out.info = hres->info;
+        if (hres->info.status == 2) {
+            pm::set_error("the input pose is zero (no model)");
+            return PM_E_NO_MODEL;
+        }
+        return PM_OK;
+    }
+    if (out.best_key) *out.best_key = hres->key;
+    if (out.info && refine) *out.info = hres->info;
+    if (hres->key == 0ull) {
+        pm::set_error("no valid model (all samples degenerate)");
+        return PM_E_NO_MODEL;
+    }
+    if (out.R) memcpy(out.R, hres->Rt, sizeof(double) * 9);
+    if (out.t) memcpy(out.t, hres->Rt + 9, sizeof(double) * 3);
+    if (out.mask) memcpy(out.mask, hmask, static_cast<size_t>(n));
+    if (out.n_inliers) *out.n_inliers = hres->count;
+    return PM_OK;
+}
+
 }  // namespace
 }  // namespace pm_ransac
 
@@ -628,4 +836,88 @@ extern "C" int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2,
     EHostOut o{};
     o.E = E; o.mask = mask; o.n_inliers = n_inliers; o.best_key = best_key; o.R = R; o.t = t; o.n_good = n_good;
     return run_e_host(ctx, E_RANSAC | E_POSE, xy1, xy2, n, K, p, nullptr, nullptr, dist, o);
+}
+
+// ---- absolute pose
+extern "C" int pm_ransac_pnp(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K,
+                             const pm_ransac_params* p, double R[9], double t[3], uint8_t* mask, int* n_inliers,
+                             uint64_t* best_key)
+{
+    PHostOut o{};
+    o.R = R; o.t = t; o.mask = mask; o.n_inliers = n_inliers; o.best_key = best_key;
+    return run_pnp_host(ctx, P_RANSAC, xyz, uv, n, K, p, nullptr, nullptr, nullptr, 0, o);
+}
+
+extern "C" int pm_ransac_pnp_from_hyp(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K,
+                                      const pm_ransac_params* p, int64_t hyp, double Rt[48], int32_t counts[4], int* n_models)
+{
+    PHostOut o{};
+    o.Rt = Rt; o.counts = counts; o.n_models = n_models;
+    pm_ransac_params q{};
+    if (p) {
+        q = *p;
+        q.hyp_begin = hyp;
+        q.hyp_end = hyp + 1;
+    }
+    return run_pnp_host(ctx, P_CANDIDATES, xyz, uv, n, K, p ? &q : nullptr, nullptr, nullptr, nullptr, 0, o);
+}
+
+extern "C" int pm_ransac_pnp_run_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const pm_ransac_params* p,
+                                     uint64_t* d_best_key, double* d_Rt, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers)
+{
+    PM_REQUIRE(d_best_key && d_Rt && d_mask && d_n_inliers, PM_E_INVALID, "null argument");
+    PM_REQUIRE(mask_len >= 0, PM_E_INVALID, "mask_len must be >= 0");
+    int rc = check_pnp(K, p);
+    if (rc != PM_OK) return rc;
+    PM_REQUIRE(view != nullptr && view->xyz && view->uv && view->cap >= 1, PM_E_INVALID, "need a view with points and cap >= 1");
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    rc = pm::arena_reserve(ctx, pnp_scratch_bytes(ctx, p));
+    if (rc != PM_OK) return rc;
+    pm::arena_reset(ctx);
+    const pm_points_view v{view->xyz, view->uv, view->count, 1, view->cap, 0, 1, 0};
+    return enqueue_pnp(ctx, v, *K, p, reinterpret_cast<unsigned long long*>(d_best_key), d_Rt, d_mask, mask_len, d_n_inliers);
+}
+
+extern "C" int pm_pnp_refine(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K, const uint8_t* mask,
+                             const double R_in[9], const double t_in[3], int max_iters, double R_out[9], double t_out[3],
+                             pm_h_refine_info* info)
+{
+    PHostOut o{};
+    o.R = R_out; o.t = t_out; o.info = info;
+    return run_pnp_host(ctx, P_REFINE, xyz, uv, n, K, nullptr, mask, R_in, t_in, max_iters, o);
+}
+
+extern "C" int pm_pnp_refine_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const uint8_t* d_mask,
+                                 const double* d_Rt_in, int max_iters, double* d_Rt_out, pm_h_refine_info* d_info)
+{
+    PM_REQUIRE(d_mask && d_Rt_in && d_Rt_out, PM_E_INVALID, "null argument");
+    PM_REQUIRE(K != nullptr, PM_E_INVALID, "K is null");
+    const bool fin = std::isfinite(K->fx) && std::isfinite(K->fy) && std::isfinite(K->cx) && std::isfinite(K->cy);
+    PM_REQUIRE(fin && K->fx > 0.0 && K->fy > 0.0, PM_E_INVALID, "K needs finite values and fx, fy > 0");
+    PM_REQUIRE(max_iters >= 0 && max_iters <= 100, PM_E_INVALID, "max_iters must lie in [0, 100]");
+    PM_REQUIRE(view != nullptr && view->xyz && view->uv && view->cap >= 1, PM_E_INVALID, "need a view with points and cap >= 1");
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    const pm_points_view v{view->xyz, view->uv, view->count, 1, view->cap, 0, 1, 0};
+    return pnp_refine_enqueue(ctx, v, *K, d_mask, d_Rt_in, max_iters, d_Rt_out, d_info);
+}
+
+extern "C" int pm_solve_pnp_ransac(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K,
+                                   const pm_ransac_params* p, int max_iters, double R[9], double t[3], uint8_t* mask,
+                                   int* n_inliers, uint64_t* best_key, pm_h_refine_info* info)
+{
+    PHostOut o{};
+    o.R = R; o.t = t; o.mask = mask; o.n_inliers = n_inliers; o.best_key = best_key; o.info = info;
+    return run_pnp_host(ctx, P_RANSAC | P_REFINE, xyz, uv, n, K, p, nullptr, nullptr, nullptr, max_iters, o);
+}
+
+extern "C" int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_kp_xy,
+                                 int n_kp, const float* d_obj_xyz, int n_obj, float* d_uv, float* d_xyz)
+{
+    PM_REQUIRE(d_matches && d_kp_xy && d_obj_xyz && d_uv && d_xyz, PM_E_INVALID, "null argument");
+    PM_REQUIRE(cap >= 1 && n_kp >= 0 && n_obj >= 0, PM_E_INVALID, "need cap >= 1, n_kp >= 0, n_obj >= 0");
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    return gather_pnp_enqueue(ctx, d_matches, d_count, cap, d_kp_xy, n_kp, d_obj_xyz, n_obj, d_uv, d_xyz);
 }

@@ -22,13 +22,15 @@
 //
 // Everything here is templated on a diagnostics policy (ransac_core.hpp: NoDiag); the LDS form below is also templated on
 // a model policy (FModel here, HModel in csrc/ransac_h_fused.hip, AModel in csrc/ransac_a_fused.hip, EModel in
-// csrc/ransac_e_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
+// csrc/ransac_e_fused.hip, PModel in csrc/ransac_p_fused.hip).  The F kernels are instantiated by csrc/ransac_fused.hip
 // (the product launch: NoDiag, nothing else instantiated) and tools/ablation/ransac_fused_stamps.hip (a diagnostic launch
 // with in-kernel phase stamps; replaces ransac_fused.o in a library of its own, never shipped).  csrc/ransac_h_fused.hip
 // and csrc/ransac_a_fused.hip instantiate the LDS form (fused_lds_enqueue) for the homography and the affine models;
 // csrc/ransac_shard.hip (finish kernel + the sharded C-ABI entry points) and csrc/homography_refine.hip share the view
 // helpers.
 #pragma once
+#include <type_traits>
+
 #include "ransac_core.hpp"
 #include "ransac_internal.hpp"
 
@@ -60,8 +62,8 @@ struct RfOut {
     FinalOut* fo;                 // local, may be null (host entry point reads it back)
     union {
         pm_ransac_record* rec;    // shard
-        const double* cand;       // CANDIDATES policies (never SHARD_OUT): the solved models, 10 doubles (9 + valid flag)
-    };                            // per id from hyp_begin.  A union keeps the kernel arguments of F, H and A as they were
+        const double* cand;       // CANDIDATES policies (never SHARD_OUT): the solved models from hyp_begin (EModel: 10
+    };                            // doubles per id, 9 + valid flag).  A union keeps the kernel arguments of F, H and A as they were
 };
 
 // ---- correspondence view -------------------------------------------------------------------------------------
@@ -521,6 +523,25 @@ constexpr int RL_THREADS = RL_WAVES * 64;
 constexpr int RL_SLOT_PTS = 128;             // points per slot: 64 lanes x 2 (packed)
 constexpr int RL_MAX_SLOTS = 64;             // slots per LDS tile: 128 KiB dynamic (+ ~18 KiB static) of the CU's 160 KiB
 
+// LDS geometry of a model policy: PLANES packed-pair planes per 128-point slot, MW floats per scoring model in s_mdl with
+// the valid flag at FLAG, WORDS doubles per fp64 model (slots, winner, published model), MAX_SLOTS slots per LDS tile.
+// OWN = false is F's geometry (x, y, x', y' from a pm_points_view; 9 floats + flag in 12; 9 doubles), which the F, H, A
+// and E policies keep.  A policy that declares `using Geom = ...` with OWN = true supplies its own loader (load_pair),
+// scoring model (Regs, regs, inlier_pk / inlier_x2 over PLANES operands) and mask-phase model (mask_model): PModel,
+// ransac_p_fused.hip.
+struct GeomF {
+    static constexpr bool OWN = false;
+    static constexpr int PLANES = 4, MW = 12, FLAG = 9, WORDS = 9, MAX_SLOTS = RL_MAX_SLOTS;
+};
+template <typename M, typename = void>
+struct GeomOf {
+    using type = GeomF;
+};
+template <typename M>
+struct GeomOf<M, std::void_t<typename M::Geom>> {
+    using type = typename M::Geom;
+};
+
 // NH hypotheses of one wave (ids s0, s0 + RL_WAVES, ...) over the slots of the LDS tile in ONE pass: each operand read serves NH
 // models (the LDS port, 4 x 512 B per wave and slot, would otherwise be ~3/4 as busy as the VALU and the two contend).
 template <typename MODEL, int NH>
@@ -552,33 +573,59 @@ __device__ __forceinline__ void score_lds(const float (*s_mdl)[12], int* s_cnt, 
 }
 
 // The same over NH explicit hypotheses ss[0..NH) (wave-uniform): the scorer of CANDIDATES policies, which skips the ids
-// whose valid flag is 0.
-template <typename MODEL, int NH>
-__device__ __forceinline__ void score_lds_ids(const float (*s_mdl)[12], int* s_cnt, const f32x2* pp, int kslots, const int (&ss)[4],
+// whose valid flag is 0.  A policy with its own geometry G scores G::PLANES operands per slot with its own SGPR model.
+template <typename MODEL, int NH, typename G = GeomF>
+__device__ __forceinline__ void score_lds_ids(const float (*s_mdl)[G::MW], int* s_cnt, const f32x2* pp, int kslots, const int (&ss)[4],
                                               float thr2, int lane)
 {
-    ModelS ms[NH];
-    int c[NH];
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-        const float* m = s_mdl[ss[h]];
-        ms[h] = model_to_sgprs(*reinterpret_cast<const f32x4v*>(m), *reinterpret_cast<const f32x4v*>(m + 4),
-                               *reinterpret_cast<const f32x2*>(m + 8));
-        c[h] = 0;
-    }
-    for (int slot = 0; slot < kslots; ++slot) {
-        const f32x2 x = pp[0], y = pp[64], xp = pp[128], yp = pp[192];
-        pp += 256;
+    if constexpr (G::OWN) {
+        typename MODEL::Regs ms[NH];
+        int c[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            bool ia, ib;
-            MODEL::inlier_pk(ms[h], x, y, xp, yp, thr2, ia, ib);
-            c[h] += __popcll(__ballot(ia)) + __popcll(__ballot(ib));
+            ms[h] = MODEL::regs(s_mdl[ss[h]]);
+            c[h] = 0;
         }
-    }
-    if (lane == 0) {
+        for (int slot = 0; slot < kslots; ++slot) {
+            f32x2 op[G::PLANES];
 #pragma unroll
-        for (int h = 0; h < NH; ++h) s_cnt[ss[h]] += c[h];
+            for (int q = 0; q < G::PLANES; ++q) op[q] = pp[64 * q];
+            pp += 64 * G::PLANES;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                bool ia, ib;
+                MODEL::inlier_pk(ms[h], op, thr2, ia, ib);
+                c[h] += __popcll(__ballot(ia)) + __popcll(__ballot(ib));
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h) s_cnt[ss[h]] += c[h];
+        }
+    } else {
+        ModelS ms[NH];
+        int c[NH];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            const float* m = s_mdl[ss[h]];
+            ms[h] = model_to_sgprs(*reinterpret_cast<const f32x4v*>(m), *reinterpret_cast<const f32x4v*>(m + 4),
+                                   *reinterpret_cast<const f32x2*>(m + 8));
+            c[h] = 0;
+        }
+        for (int slot = 0; slot < kslots; ++slot) {
+            const f32x2 x = pp[0], y = pp[64], xp = pp[128], yp = pp[192];
+            pp += 256;
+#pragma unroll
+            for (int h = 0; h < NH; ++h) {
+                bool ia, ib;
+                MODEL::inlier_pk(ms[h], x, y, xp, yp, thr2, ia, ib);
+                c[h] += __popcll(__ballot(ia)) + __popcll(__ballot(ib));
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int h = 0; h < NH; ++h) s_cnt[ss[h]] += c[h];
+        }
     }
 }
 
@@ -587,13 +634,14 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
                                                                float thr2, int tile_slots, RfSlot* __restrict__ slots,
                                                                int* __restrict__ ticket, RfOut out)
 {
-    extern __shared__ __attribute__((aligned(16))) f32x2 s_pts[];           // [tile_slots][4][64]: X, Y, XP, YP pairs
-    __shared__ __attribute__((aligned(16))) float s_mdl[RF_HB_MAX][12];    // f32 model + valid flag of hypothesis s
-    __shared__ double s_m64[RF_HB_MAX][9];
+    using G = typename GeomOf<MODEL>::type;
+    extern __shared__ __attribute__((aligned(16))) f32x2 s_pts[];           // [tile_slots][G::PLANES][64]: X, Y, XP, YP pairs (F)
+    __shared__ __attribute__((aligned(16))) float s_mdl[RF_HB_MAX][G::MW];   // f32 model + valid flag of hypothesis s
+    __shared__ double s_m64[RF_HB_MAX][G::WORDS];
     __shared__ int s_cnt[RF_HB_MAX];
     __shared__ int s_offs[PM_MAX_PARTS + 1];
     __shared__ unsigned long long s_wk[RL_WAVES];
-    __shared__ double s_F64[9];
+    __shared__ double s_F64[G::WORDS];
     __shared__ int s_role;
     __shared__ int s_wc[RL_WAVES];
 
@@ -614,23 +662,27 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
     // slot `slot`, lane `l` of the tile that starts at point `base`: points base + 2*(64*slot + l) and +1 (NaN past n)
     auto load_pair = [&](int base, int slot, int l) {
         const int i0 = base + 2 * (64 * slot + l);
-        float2 a0 = {nanv, nanv}, b0 = a0, a1 = a0, b1 = a0;
-        if (v.parts == 1) {
-            if (n > 0) {
-                const int j0 = i0 < n ? i0 : n - 1, j1 = i0 + 1 < n ? i0 + 1 : n - 1;      // unconditional clamped loads
-                a0 = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(j0));
-                a1 = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(j1));
-                b0 = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(j0));
-                b1 = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(j1));
-            }
-            if (i0 >= n) { a0 = float2{nanv, nanv}; b0 = a0; }
-            if (i0 + 1 >= n) { a1 = float2{nanv, nanv}; b1 = a1; }
+        if constexpr (G::OWN) {
+            MODEL::load_pair(v, n, i0, s_pts + static_cast<size_t>(slot) * G::PLANES * 64 + l);
         } else {
-            if (i0 < n) view_point(v, s_offs, i0, a0, b0);
-            if (i0 + 1 < n) view_point(v, s_offs, i0 + 1, a1, b1);
+            float2 a0 = {nanv, nanv}, b0 = a0, a1 = a0, b1 = a0;
+            if (v.parts == 1) {
+                if (n > 0) {
+                    const int j0 = i0 < n ? i0 : n - 1, j1 = i0 + 1 < n ? i0 + 1 : n - 1;      // unconditional clamped loads
+                    a0 = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(j0));
+                    a1 = *reinterpret_cast<const float2*>(v.xy1 + 2 * static_cast<size_t>(j1));
+                    b0 = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(j0));
+                    b1 = *reinterpret_cast<const float2*>(v.xy2 + 2 * static_cast<size_t>(j1));
+                }
+                if (i0 >= n) { a0 = float2{nanv, nanv}; b0 = a0; }
+                if (i0 + 1 >= n) { a1 = float2{nanv, nanv}; b1 = a1; }
+            } else {
+                if (i0 < n) view_point(v, s_offs, i0, a0, b0);
+                if (i0 + 1 < n) view_point(v, s_offs, i0 + 1, a1, b1);
+            }
+            f32x2* d = s_pts + (static_cast<size_t>(slot) * 4) * 64 + l;
+            d[0] = f32x2{a0.x, a1.x}; d[64] = f32x2{a0.y, a1.y}; d[128] = f32x2{b0.x, b1.x}; d[192] = f32x2{b0.y, b1.y};
         }
-        f32x2* d = s_pts + (static_cast<size_t>(slot) * 4) * 64 + l;
-        d[0] = f32x2{a0.x, a1.x}; d[64] = f32x2{a0.y, a1.y}; d[128] = f32x2{b0.x, b1.x}; d[192] = f32x2{b0.y, b1.y};
     };
     auto tile_kslots = [&](int t) {
         int k = (n - t * tile_pts + RL_SLOT_PTS - 1) / RL_SLOT_PTS;
@@ -643,7 +695,19 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
     const int solver_waves = (hcount + 63) / 64;                            // 1 (or 2 beyond 64 ids per workgroup)
     DIAG::phase(2);
     if (wave < solver_waves) {
-        if (tid < hcount) {
+        if constexpr (G::OWN) {
+            if (tid < hcount) {
+                double F[G::WORDS];
+                bool ok = false;
+#pragma unroll
+                for (int i = 0; i < G::WORDS; ++i) F[i] = 0.0;
+                if (n >= MODEL::MIN_PTS) ok = MODEL::load(out.cand, h0 + tid, F, s_mdl[tid]);
+#pragma unroll
+                for (int i = 0; i < G::WORDS; ++i) s_m64[tid][i] = F[i];
+                s_mdl[tid][G::FLAG] = ok ? 1.f : 0.f;
+                s_cnt[tid] = 0;
+            }
+        } else if (tid < hcount) {
             double F[9];
             bool ok = false;
 #pragma unroll
@@ -679,7 +743,7 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         if constexpr (MODEL::CANDIDATES) {
             // bit k: hypothesis wave + 12k is valid (k <= 10: hb <= 128); up to four of them per pass
             const int sk = wave + RL_WAVES * lane;
-            unsigned long long live = __ballot(sk < hcount && s_mdl[sk < hcount ? sk : 0][9] != 0.f);
+            unsigned long long live = __ballot(sk < hcount && s_mdl[sk < hcount ? sk : 0][G::FLAG] != 0.f);
             while (live) {
                 int ss[4];
                 int k = 0;
@@ -692,10 +756,10 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
                         k = h + 1;
                     }
                 }
-                if (k == 4) score_lds_ids<MODEL, 4>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
-                else if (k == 3) score_lds_ids<MODEL, 3>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
-                else if (k == 2) score_lds_ids<MODEL, 2>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
-                else score_lds_ids<MODEL, 1>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                if (k == 4) score_lds_ids<MODEL, 4, G>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else if (k == 3) score_lds_ids<MODEL, 3, G>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else if (k == 2) score_lds_ids<MODEL, 2, G>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
+                else score_lds_ids<MODEL, 1, G>(s_mdl, s_cnt, s_pts + lane, kslots, ss, thr2, lane);
             }
         } else {
             for (int s = wave; s < hcount; s += 4 * RL_WAVES) {
@@ -712,16 +776,17 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
 
     // ---- the workgroup's best key (SPEC S9 / S22: most inliers, then lowest id) and its slot
     unsigned long long key = 0ull;
-    if (tid < hcount && s_mdl[tid][9] != 0.f)
+    if (tid < hcount && s_mdl[tid][G::FLAG] != 0.f)
         key = (static_cast<unsigned long long>(static_cast<uint32_t>(s_cnt[tid])) << 32) |
               static_cast<unsigned long long>(0xFFFFFFFFu - static_cast<uint32_t>(hyp_begin + h0 + tid));
     const unsigned long long kbest = wg_max_u64<RL_WAVES>(key, s_wk, tid);
     if (wave == 0) {
         const int sb = kbest ? static_cast<int>(static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(kbest)) - hyp_begin) - h0 : 0;
-        // slots as ten arrays of gridDim.x words (F[0] .. F[8], key): the last workgroup's scan reads them coalesced
+        // slots as G::WORDS + 1 arrays of gridDim.x words (F[0] .. F[8], key): the last workgroup's scan reads them
+        // coalesced (at most 16 arrays: RfSlot's 128 B per workgroup)
         double* sf = reinterpret_cast<double*>(slots) + static_cast<size_t>(lane) * gridDim.x + blockIdx.x;
-        if (lane < 9) __hip_atomic_store(sf, kbest ? s_m64[sb][lane] : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (lane == 9) __hip_atomic_store(reinterpret_cast<unsigned long long*>(sf), kbest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane < G::WORDS) __hip_atomic_store(sf, kbest ? s_m64[sb][lane] : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == G::WORDS) __hip_atomic_store(reinterpret_cast<unsigned long long*>(sf), kbest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the slot is written through before the ticket is drawn
         if (lane == 0) {
             const int tk = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -735,29 +800,29 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
     // ---- last workgroup: every slot is complete.  Winner = max key over the slots.
     if (tid == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
     unsigned long long kb = 0ull;
-    double fb[9];
+    double fb[G::WORDS];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) fb[i] = 0.0;
+    for (int i = 0; i < G::WORDS; ++i) fb[i] = 0.0;
     for (int j = tid; j < static_cast<int>(gridDim.x); j += RL_THREADS) {
         const double* sf = reinterpret_cast<const double*>(slots) + j;
-        const unsigned long long kj = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(sf + 9 * static_cast<size_t>(gridDim.x)),
+        const unsigned long long kj = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(sf + G::WORDS * static_cast<size_t>(gridDim.x)),
                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        double fj[9];
+        double fj[G::WORDS];
 #pragma unroll
-        for (int i = 0; i < 9; ++i) fj[i] = __hip_atomic_load(sf + i * static_cast<size_t>(gridDim.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = 0; i < G::WORDS; ++i) fj[i] = __hip_atomic_load(sf + i * static_cast<size_t>(gridDim.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (kj > kb) {
             kb = kj;
 #pragma unroll
-            for (int i = 0; i < 9; ++i) fb[i] = fj[i];
+            for (int i = 0; i < G::WORDS; ++i) fb[i] = fj[i];
         }
     }
     const unsigned long long kwin = wg_max_u64<RL_WAVES>(kb, s_wk, tid);
     const bool ok = kwin != 0ull && n >= MODEL::MIN_PTS;
-    if (tid < 9) s_F64[tid] = 0.0;
+    if (tid < G::WORDS) s_F64[tid] = 0.0;
     __syncthreads();
     if (ok && kb == kwin) {                                  // exactly one thread: keys of distinct ids differ
 #pragma unroll
-        for (int i = 0; i < 9; ++i) s_F64[i] = fb[i];
+        for (int i = 0; i < G::WORDS; ++i) s_F64[i] = fb[i];
     }
     __syncthreads();
     DIAG::phase(7);
@@ -766,17 +831,21 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
         if (tid == 9) out.rec->key = ok ? kwin : 0ull;
         return;
     }
-    if (tid < 9) {
-        if (out.F && (MODEL::OUT_WORDS == 9 || tid < MODEL::OUT_WORDS)) out.F[tid] = s_F64[tid];
+    if (tid < G::WORDS) {
+        if (out.F && (MODEL::OUT_WORDS == G::WORDS || tid < MODEL::OUT_WORDS)) out.F[tid] = s_F64[tid];
         if (MODEL::SHARD_OUT && out.fo) { out.fo->F[tid] = s_F64[tid]; out.fo->F32[tid] = static_cast<float>(s_F64[tid]); }
     }
-    if (tid == 9) {
+    if (tid == G::WORDS) {
         *out.key = ok ? kwin : 0ull;
         if (MODEL::SHARD_OUT && out.fo) out.fo->valid = ok ? 1 : 0;
     }
-    float fw[9];
+    float fw[G::OWN ? G::MW : 9];
+    if constexpr (G::OWN) {
+        MODEL::mask_model(out.cand, ok, kwin, hyp_begin, fw);
+    } else {
 #pragma unroll
-    for (int i = 0; i < 9; ++i) fw[i] = static_cast<float>(s_F64[i]);
+        for (int i = 0; i < 9; ++i) fw[i] = static_cast<float>(s_F64[i]);
+    }
     int mine = 0;
     for (int t = 0; t < ntiles; ++t) {
         const int kslots = tile_kslots(t);
@@ -786,9 +855,16 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
             __syncthreads();
         }
         for (int slot = wave; slot < kslots; slot += RL_WAVES) {
-            const f32x2* pp = s_pts + static_cast<size_t>(slot) * 256 + lane;
+            const f32x2* pp = s_pts + static_cast<size_t>(slot) * (64 * G::PLANES) + lane;
             bool ia, ib;
-            MODEL::inlier_x2(fw, pp[0], pp[64], pp[128], pp[192], thr2, ia, ib);
+            if constexpr (G::OWN) {
+                f32x2 op[G::PLANES];
+#pragma unroll
+                for (int q = 0; q < G::PLANES; ++q) op[q] = pp[64 * q];
+                MODEL::inlier_x2(fw, op, thr2, ia, ib);
+            } else {
+                MODEL::inlier_x2(fw, pp[0], pp[64], pp[128], pp[192], thr2, ia, ib);
+            }
             ia = ia && ok; ib = ib && ok;
             const int i0 = t * tile_pts + 2 * (64 * slot + lane);
             if (i0 < out.mask_len) out.mask[i0] = ia ? 1 : 0;
@@ -827,15 +903,16 @@ template <typename MODEL, typename DIAG>
 int fused_lds_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int nwg, int hb, RfSlot* slots,
                      int* ticket, const RfOut& out)
 {
+    using G = typename GeomOf<MODEL>::type;
     const long long cap_total = static_cast<long long>(v.parts) * v.cap;
     const long long need = (cap_total + RL_SLOT_PTS - 1) / RL_SLOT_PTS;
-    const int tile_slots = static_cast<int>(need < 1 ? 1 : (need > RL_MAX_SLOTS ? RL_MAX_SLOTS : need));
-    const size_t lds = static_cast<size_t>(tile_slots) * 4 * 64 * sizeof(f32x2);
+    const int tile_slots = static_cast<int>(need < 1 ? 1 : (need > G::MAX_SLOTS ? G::MAX_SLOTS : need));
+    const size_t lds = static_cast<size_t>(tile_slots) * G::PLANES * 64 * sizeof(f32x2);
     static bool attr_done_dev[PM_MAX_DEVICES] = {};
     if (!attr_done_dev[ctx->device]) {
         PM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ransac_fused_lds<MODEL, DIAG>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         RL_MAX_SLOTS * 4 * 64 * static_cast<int>(sizeof(f32x2))));
+                                         G::MAX_SLOTS * G::PLANES * 64 * static_cast<int>(sizeof(f32x2))));
         attr_done_dev[ctx->device] = true;
     }
     const float thr2 = p->thresh_px * p->thresh_px;

@@ -2,7 +2,8 @@
 // the C-ABI functions in ransac.hip (host-pointer and device-resident single-shard runs) and by the multi-GPU driver
 // (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue each of the planar estimators'
 // kernel files (ransac_h_fused.hip, ransac_a_fused.hip, homography_refine.hip, affine_refine.hip) and of the
-// calibrated-pose ones (essential_solve.hip, ransac_e_fused.hip, recover_pose.hip), which planar_estimators.cpp drives.
+// calibrated-pose ones (essential_solve.hip, ransac_e_fused.hip, recover_pose.hip, pnp_solve.hip, ransac_p_fused.hip),
+// which planar_estimators.cpp drives.
 #pragma once
 #include "ransac_core.hpp"
 
@@ -47,5 +48,17 @@ int ransac_e_enqueue(pm_ctx* ctx, const pm_points_view& vn, const pm_ransac_para
 int recover_pose_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const double* d_E, const uint8_t* d_mask_in,
                          double dist, double* d_R, double* d_t, uint8_t* d_mask_out, int mask_len, int* d_n_good,
                          float* d_points4);
+
+// Absolute pose.  pnp_solve_enqueue solves samples [hyp_begin, hyp_end) of p into d_cand (80 doubles per sample) from the
+// one-part view v (xy1 = world points, 3 floats each; xy2 = pixels); ransac_p_enqueue scores model ids [q->hyp_begin,
+// q->hyp_end) (4 per sample, d_cand at the first) over the same view (carves its slots like ransac_h_enqueue).
+int pnp_solve_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const pm_ransac_params* p, double* d_cand);
+int ransac_p_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* q, const double* d_cand,
+                     unsigned long long* d_key, double* d_Rt, uint8_t* d_mask, int mask_len, int* d_ninl);
+// pnp_refine_enqueue: S40 on the same view, one workgroup; gather_pnp_enqueue: the device chain's match -> row gather.
+int pnp_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const uint8_t* d_mask, const double* d_Rt_in,
+                       int max_iters, double* d_Rt_out, pm_h_refine_info* d_info);
+int gather_pnp_enqueue(pm_ctx* ctx, const pm_match* d_m, const int32_t* d_count, int cap, const float* d_kp_xy, int n_kp,
+                       const float* d_obj, int n_obj, float* d_uv, float* d_xyz);
 
 }  // namespace pm_ransac

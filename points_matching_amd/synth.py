@@ -286,6 +286,41 @@ def calibrated_view(n, seed=0xE5, K=None, R=None, t=None, outlier_frac=0.3, nois
     return (np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), K, R, t, X, inl)
 
 
+def pnp_scene(n, seed=0x9F, K=None, outlier_frac=0.3, noise_px=0.5, width=993, height=660):
+    """2D-3D correspondences of one calibrated frame against a known map (visual odometry / SfM localisation): world
+    points in front of the camera seen by pinhole K at pose x_cam = R X + t, plus N(0, noise_px) on the pixels;
+    `outlier_frac` of the pixels are replaced by uniform-random image positions.  Defaults: K with fx != fy and an
+    off-centre principal point, R a rotation up to ~30 degrees, t up to ~2 units, depths 4-12.
+
+    Returns xyz (n x 3 float32 world points), uv (n x 2 float32 pixels), K (3 x 3), R (3 x 3), t (3) and the boolean
+    ground-truth inlier flags.
+    """
+    rng = np.random.default_rng([seed, 0x9A9F])
+    if K is None:
+        K = np.array([[rng.uniform(700, 900), 0, width / 2.0 + rng.uniform(-40, 40)],
+                      [0, rng.uniform(750, 950), height / 2.0 + rng.uniform(-30, 30)], [0, 0, 1.0]])
+    K = np.asarray(K, np.float64)
+    w = rng.normal(size=3)
+    w *= rng.uniform(0.1, 0.5) / np.linalg.norm(w)
+    th = np.linalg.norm(w)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+    t = rng.uniform(-2.0, 2.0, 3)
+    px = rng.uniform([0, 0], [width, height], (n, 2))
+    Xc = np.c_[px, np.ones(n)] @ np.linalg.inv(K).T * rng.uniform(4.0, 12.0, n)[:, None]
+    X = (Xc - t) @ R                                           # world = R^T (x_cam - t)
+    uv = Xc @ K.T
+    uv = uv[:, :2] / uv[:, 2:3] + rng.normal(0, noise_px, (n, 2))
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        uv[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
+    return np.ascontiguousarray(X.astype(np.float32)), np.ascontiguousarray(uv.astype(np.float32)), K, R, t, inl
+
+
 def affine_view(n, seed=0xA5, outlier_frac=0.3, noise_px=0.5, partial=False, width=993, height=660):
     """Correspondences of a 2D affine scene (a document scan, an aerial mosaic tile, a stabilised video frame): image-2
     points are image-1 points mapped by a known affine map about the image centre, plus N(0, noise_px) in both images;
