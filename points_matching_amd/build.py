@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
            "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
-           "pnp_refine.hip", "planar_estimators.cpp",
+           "pnp_refine.hip", "estimators.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],

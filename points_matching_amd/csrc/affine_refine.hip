@@ -8,7 +8,7 @@
 //   1. count, coordinate sums and the cost of A_in (6 sums);
 //   2. the centred second moments (7 sums full, 3 partial), then the 2 x 2 cofactor solve in every thread;
 //   3. the cost of the refit, which is kept only if it is not higher than A_in's.
-// The launch keeps no per-call state, so the device form may be captured; the host forms (planar_estimators.cpp)
+// The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp)
 // synchronise.
 #include "affine_core.hpp"
 #include "ransac_fused_kernels.hpp"

@@ -11,7 +11,7 @@
 // Passes: sums + cost of H_in, centroid distances, normal matrix, cost of the refit, then the LM passes (one at the
 // start point, one per iteration).
 //
-// The launch keeps no per-call state, so the device form may be captured; the host forms (planar_estimators.cpp)
+// The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp)
 // synchronise.
 #include "homography_core.hpp"
 #include "homography_refine_core.hpp"

@@ -9,7 +9,7 @@
 // Cholesky of each step runs in thread 0; every thread then applies the same step (a Cayley rotation update: no
 // transcendental function) and the next pass runs at the trial pose.
 //
-// The launch keeps no per-call state, so the device form may be captured; the host forms (planar_estimators.cpp)
+// The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp)
 // synchronise.
 #include "pnp_core.hpp"
 #include "refine_reduce.hpp"

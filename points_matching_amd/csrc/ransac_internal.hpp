@@ -1,9 +1,9 @@
 // ransac_internal.hpp — host functions shared across translation units: the entry points of ransac_fused.hip used by
 // the C-ABI functions in ransac.hip (host-pointer and device-resident single-shard runs) and by the multi-GPU driver
-// (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue each of the planar estimators'
-// kernel files (ransac_h_fused.hip, ransac_a_fused.hip, homography_refine.hip, affine_refine.hip) and of the
-// calibrated-pose ones (essential_solve.hip, ransac_e_fused.hip, recover_pose.hip, pnp_solve.hip, ransac_p_fused.hip),
-// which planar_estimators.cpp drives.
+// (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue of each kernel file that
+// estimators.cpp drives for its four families: homography (ransac_h_fused.hip, homography_refine.hip), affine
+// (ransac_a_fused.hip, affine_refine.hip), calibrated relative pose (essential_solve.hip, ransac_e_fused.hip,
+// recover_pose.hip) and absolute pose (pnp_solve.hip, ransac_p_fused.hip, pnp_refine.hip).
 #pragma once
 #include "ransac_core.hpp"
 
@@ -24,9 +24,9 @@ inline int check_view(const pm_points_view* v)
     return PM_OK;
 }
 
-// The planar estimators' launches, each enqueued on ctx->stream with no synchronisation and no argument check.  The
-// RANSAC pair carves its workgroup slots from the arena, which must hold fused_scratch_bytes() more; model is
-// PM_AFFINE_FULL or PM_AFFINE_PARTIAL.
+// The launches below are each enqueued on ctx->stream with no synchronisation and no argument check.
+// Homography and affine.  The RANSAC pair carves its workgroup slots from the arena, which must hold
+// fused_scratch_bytes() more; model is PM_AFFINE_FULL or PM_AFFINE_PARTIAL.
 int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
                      double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl);
 int ransac_a_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,

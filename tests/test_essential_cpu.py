@@ -2,11 +2,13 @@
 true E among the 5-point candidates, the epipolar and cubic constraints, the Gauss-Jordan reduction and the real-root
 count against numpy's linear solve and companion-matrix roots, the decomposition against np.linalg.svd, the
 triangulation against the SVD DLT and the cheirality counts, plus a mutation check (a Gauss-Jordan without its pivot
-swap is caught by the same comparison)."""
+swap is caught by the same comparison), plus the argument checks of the shipped entry points, which need no device."""
+import ctypes as C
+
 import numpy as np
 
 import essential_ref as R
-from points_matching_amd import synth
+from points_matching_amd import api, synth
 
 
 def _skew(t):
@@ -252,3 +254,196 @@ def test_run_recovers_pose_on_cpu():
     assert ng >= 0.95 * c
     assert np.degrees(np.arccos(np.clip((np.trace(Rr.T @ Rg) - 1) / 2, -1, 1))) < 0.5
     assert np.degrees(np.arccos(np.clip(tr @ tg, -1, 1))) < 3.0
+
+
+def test_library_rejects_bad_arguments_without_a_device():
+    """Every check of the six entry points, tripped alone and in pairs that pin the order, with ctx = NULL: the checks
+    all sit before the ctx check.  Messages are matched on the text after PM_REQUIRE's function-name prefix."""
+    L = api.lib()
+    INV, FEW = api.PM_E_INVALID, api.PM_E_TOO_FEW
+    xy = np.zeros((10, 2), np.float32)
+    m = np.ones(10, np.uint8)
+    cam = api.Camera(800.0, 800.0, 320.0, 240.0)
+    cam0, caminf = api.Camera(0.0, 800.0, 320.0, 240.0), api.Camera(800.0, 800.0, float("inf"), 240.0)
+    good = api.RansacParams(0, 10, 1, 1.0, api.PM_ERR_SAMPSON)
+    kind = api.RansacParams(0, 10, 1, 1.0, api.PM_ERR_REPROJ)
+    empty = api.RansacParams(5, 5, 1, 1.0, api.PM_ERR_SAMPSON)
+    neg = api.RansacParams(-1, 5, 1, 1.0, api.PM_ERR_SAMPSON)
+    high = api.RansacParams(0, (1 << 32) // 10 + 1, 1, 1.0, api.PM_ERR_SAMPSON)
+    wide = api.RansacParams(0, ((1 << 31) - 1) // 10 + 1, 1, 1.0, api.PM_ERR_SAMPSON)
+    thr0 = api.RansacParams(0, 10, 1, 0.0, api.PM_ERR_SAMPSON)
+    thrnan = api.RansacParams(0, 10, 1, float("nan"), api.PM_ERR_SAMPSON)
+    E, Rm, t = np.zeros(9), np.zeros(9), np.zeros(3)
+    E90, counts = np.zeros(90), np.zeros(10, np.int32)
+    mask, pts4 = np.zeros(10, np.uint8), np.zeros((10, 4), np.float32)
+    key, ninl, ng, nm = C.c_uint64(), C.c_int(), C.c_int(), C.c_int()
+    Ein = np.array([0.0, -1, 0, 1, 0, 0, 0, 0, 0])
+    nz = [10]
+
+    def ref(p):
+        return C.byref(p) if p is not None else None
+
+    def refused(rc, status, frag):
+        msg = L.pm_last_error()
+        assert rc == status and frag in msg, (rc, msg)
+        return True
+
+    def poison(n):
+        nz[0] = max(n, 0)                                        # the mask and the points are zeroed over n entries
+        for a in (E, Rm, t, E90, pts4):
+            a[...] = 7.0
+        counts[:] = 7
+        mask[:] = 7
+        key.value, ninl.value, ng.value, nm.value = 7, 7, 7, 7
+
+    # ---- pm_ransac_essential: params, K, point arrays, n < 5, ctx
+    def run(prm=good, k=cam, n=10, pts=True):
+        poison(n)
+        return L.pm_ransac_essential(None, api._p(xy) if pts else None, api._p(xy) if pts else None, n, ref(k), ref(prm),
+                                     api._p(E), api._p(mask), C.byref(ninl), C.byref(key))
+
+    def run_zeroed():
+        return not E.any() and not mask[:nz[0]].any() and (mask[nz[0]:] == 7).all() and ninl.value == 0 and key.value == 0
+
+    assert refused(run(prm=None), INV, b"params is null") and run_zeroed()
+    for prm in (empty, neg, high):
+        assert refused(run(prm=prm), INV, b"sample ids must") and run_zeroed()
+    assert refused(run(prm=wide), INV, b"split the range")
+    assert refused(run(prm=kind), INV, b"error_kind") and run_zeroed()
+    assert refused(run(k=None), INV, b"K is null") and run_zeroed()
+    assert refused(run(k=cam0), INV, b"K needs") and refused(run(k=caminf), INV, b"K needs")
+    assert refused(run(prm=thr0), INV, b"normalised threshold") and refused(run(prm=thrnan), INV, b"normalised threshold")
+    assert refused(run(pts=False), INV, b"bad point arrays") and refused(run(n=-1), INV, b"bad point arrays")
+    assert refused(run(n=4), FEW, b"need at least 5") and run_zeroed()
+    assert refused(run(n=0), FEW, b"need at least 5") and refused(run(n=0, pts=False), FEW, b"need at least 5")
+    # the order: params (null, range, kind), K (null, values, threshold), point arrays, n < 5, ctx
+    assert refused(run(prm=None, k=None), INV, b"params is null")
+    assert refused(run(prm=wide, k=None), INV, b"split the range")
+    assert refused(run(prm=kind, k=cam0), INV, b"error_kind")
+    assert refused(run(prm=thr0, k=cam0), INV, b"K needs")
+    assert refused(run(prm=thr0, pts=False), INV, b"normalised threshold")
+    assert refused(run(pts=False, n=4), INV, b"bad point arrays")
+    assert refused(run(n=5), INV, b"ctx is null") and run_zeroed()      # ctx last: everything else passed
+
+    # ---- pm_ransac_essential_from_hyp: hyp, params, then as above with the candidates' outputs before the point arrays
+    def hyp(prm=good, h=0, k=cam, n=10, pts=True, e=E90, cnt=counts):
+        poison(n)
+        return L.pm_ransac_essential_from_hyp(None, api._p(xy) if pts else None, api._p(xy) if pts else None, n, ref(k),
+                                              ref(prm), C.c_int64(h), api._p(e), api._p(cnt), C.byref(nm))
+
+    def hyp_zeroed():
+        return not E90.any() and (counts == -1).all() and nm.value == 0
+
+    for h in (-1, (1 << 32) // 10):
+        assert refused(hyp(h=h), INV, b"sample id must") and hyp_zeroed()
+    assert refused(hyp(prm=None), INV, b"params is null") and hyp_zeroed()
+    assert refused(hyp(prm=kind), INV, b"error_kind") and hyp_zeroed()
+    assert refused(hyp(k=None), INV, b"K is null") and refused(hyp(k=cam0), INV, b"K needs")
+    assert refused(hyp(prm=thr0), INV, b"normalised threshold")
+    assert refused(hyp(e=None), INV, b"null E or counts") and (counts == -1).all() and nm.value == 0
+    assert refused(hyp(cnt=None), INV, b"null E or counts") and not E90.any()
+    assert refused(hyp(pts=False), INV, b"bad point arrays")
+    assert refused(hyp(n=4), FEW, b"need at least 5") and hyp_zeroed()
+    assert refused(hyp(h=-1, prm=None), INV, b"sample id must")
+    assert refused(hyp(prm=None, k=None), INV, b"params is null")
+    assert refused(hyp(prm=kind, k=None), INV, b"error_kind")
+    assert refused(hyp(k=cam0, e=None), INV, b"K needs")
+    assert refused(hyp(e=None, pts=False), INV, b"null E or counts")
+    assert refused(hyp(pts=False, n=4), INV, b"bad point arrays")
+    assert refused(hyp(prm=empty, h=(1 << 32) // 10 - 1, n=5), INV, b"ctx is null") and hyp_zeroed()   # p's own range is unused
+
+    # ---- pm_ransac_essential_run_dev: outputs, mask_len, params, K, view, ctx
+    view = api.PointsView(1, 1, None, 1, 10, 0, 1, 0)
+    d = C.c_void_p(16)                                           # never dereferenced: the calls fail before any launch
+
+    def dev(v=view, k=cam, prm=good, outs=(d, d, d, d), mask_len=10):
+        return L.pm_ransac_essential_run_dev(None, ref(v), ref(k), ref(prm), outs[0], outs[1], outs[2], mask_len, outs[3])
+
+    for i in range(4):
+        assert refused(dev(outs=tuple(None if j == i else d for j in range(4))), INV, b"null argument")
+    assert refused(dev(mask_len=-1), INV, b"mask_len")
+    assert refused(dev(prm=None), INV, b"params is null")
+    assert refused(dev(prm=empty), INV, b"sample ids must") and refused(dev(prm=high), INV, b"sample ids must")
+    assert refused(dev(prm=wide), INV, b"split the range")
+    assert refused(dev(prm=kind), INV, b"error_kind")
+    assert refused(dev(k=None), INV, b"K is null") and refused(dev(k=cam0), INV, b"K needs")
+    assert refused(dev(prm=thr0), INV, b"normalised threshold")
+    assert refused(dev(v=None), INV, b"null correspondence view")
+    assert refused(dev(v=api.PointsView(None, 1, None, 1, 10, 0, 1, 0)), INV, b"null correspondence view")
+    assert refused(dev(v=api.PointsView(1, 1, None, 0, 10, 0, 1, 0)), INV, b"need 1 <= parts")
+    assert refused(dev(v=api.PointsView(1, 1, None, 1, 0, 0, 1, 0)), INV, b"need 1 <= parts")
+    assert refused(dev(v=api.PointsView(1, 1, None, 2, 10, 19, 1, 0)), INV, b"pitch_xy smaller")
+    assert refused(dev(outs=(None, d, d, d), mask_len=-1), INV, b"null argument")
+    assert refused(dev(mask_len=-1, prm=None), INV, b"mask_len")
+    assert refused(dev(prm=kind, k=None), INV, b"error_kind")
+    assert refused(dev(prm=thr0, v=None), INV, b"normalised threshold")
+    assert refused(dev(mask_len=0), INV, b"ctx is null")
+    assert refused(dev(), INV, b"ctx is null")
+
+    # ---- pm_recover_pose: K, E, dist, point arrays (mask_in may be null), n < 5, ctx
+    def pose(k=cam, e=Ein, mi=m, dist=50.0, n=10, pts=True, p4=pts4):
+        poison(n)
+        return L.pm_recover_pose(None, api._p(xy) if pts else None, api._p(xy) if pts else None, n, ref(k), api._p(e),
+                                 api._p(mi), C.c_double(dist), api._p(Rm), api._p(t), api._p(mask), C.byref(ng), api._p(p4))
+
+    def pose_zeroed():
+        return (not Rm.any() and not t.any() and not mask[:nz[0]].any() and ng.value == 0 and not pts4[:nz[0]].any() and
+                (pts4[nz[0]:] == 7).all())
+
+    assert refused(pose(k=None), INV, b"K is null") and pose_zeroed()
+    assert refused(pose(k=cam0), INV, b"K needs") and refused(pose(k=caminf), INV, b"K needs")
+    assert refused(pose(e=None), INV, b"null E") and pose_zeroed()
+    for dist in (0.0, -1.0, float("nan")):
+        assert refused(pose(dist=dist), INV, b"dist must") and pose_zeroed()
+    assert refused(pose(pts=False), INV, b"bad point arrays") and refused(pose(n=-1), INV, b"bad point arrays")
+    assert refused(pose(n=4), FEW, b"need at least 5") and pose_zeroed()
+    assert refused(pose(k=cam0, dist=0.0), INV, b"K needs")
+    assert refused(pose(k=None, e=None), INV, b"K is null")
+    assert refused(pose(e=None, dist=0.0), INV, b"null E")
+    assert refused(pose(dist=0.0, n=4), INV, b"dist must")
+    assert refused(pose(dist=0.0, pts=False), INV, b"dist must")
+    assert refused(pose(pts=False, n=4), INV, b"bad point arrays")
+    assert refused(pose(mi=None, p4=None), INV, b"ctx is null")         # the input mask and the points are optional
+    assert refused(pose(n=5), INV, b"ctx is null") and pose_zeroed()
+
+    # ---- pm_recover_pose_dev: required pointers (mask_in and points4 optional), K, dist, view, ctx
+    def posed(v=view, k=cam, args=(d, d, d, d, d, d, d), dist=50.0):
+        e, mi, r, tt, mo, g, p4 = args
+        return L.pm_recover_pose_dev(None, ref(v), ref(k), e, mi, C.c_double(dist), r, tt, mo, g, p4)
+
+    for i in (0, 2, 3, 4, 5):
+        assert refused(posed(args=tuple(None if j == i else d for j in range(7))), INV, b"null argument")
+    assert refused(posed(k=None), INV, b"K is null") and refused(posed(k=cam0), INV, b"K needs")
+    assert refused(posed(dist=0.0), INV, b"dist must")
+    assert refused(posed(v=None), INV, b"null correspondence view")
+    assert refused(posed(v=api.PointsView(1, 1, None, 65, 10, 20, 1, 0)), INV, b"need 1 <= parts")
+    assert refused(posed(args=(None, d, d, d, d, d, d), k=None), INV, b"null argument")
+    assert refused(posed(k=cam0, dist=0.0), INV, b"K needs")
+    assert refused(posed(dist=0.0, v=None), INV, b"dist must")
+    assert refused(posed(args=(d, None, d, d, d, d, None)), INV, b"ctx is null")
+    assert refused(posed(), INV, b"ctx is null")
+
+    # ---- pm_estimate_pose: params, K, dist, point arrays, n < 5, ctx
+    def est(prm=good, k=cam, dist=50.0, n=10, pts=True):
+        poison(n)
+        return L.pm_estimate_pose(None, api._p(xy) if pts else None, api._p(xy) if pts else None, n, ref(k), ref(prm),
+                                  C.c_double(dist), api._p(E), api._p(Rm), api._p(t), api._p(mask), C.byref(ninl),
+                                  C.byref(ng), C.byref(key))
+
+    def est_zeroed():
+        return run_zeroed() and not Rm.any() and not t.any() and ng.value == 0
+
+    assert refused(est(prm=None), INV, b"params is null") and est_zeroed()
+    assert refused(est(prm=empty), INV, b"sample ids must") and refused(est(prm=wide), INV, b"split the range")
+    assert refused(est(prm=kind), INV, b"error_kind")
+    assert refused(est(k=None), INV, b"K is null") and refused(est(k=cam0), INV, b"K needs") and est_zeroed()
+    assert refused(est(prm=thr0), INV, b"normalised threshold")
+    assert refused(est(dist=0.0), INV, b"dist must") and est_zeroed()
+    assert refused(est(pts=False), INV, b"bad point arrays")
+    assert refused(est(n=4), FEW, b"need at least 5") and est_zeroed()
+    assert refused(est(prm=kind, k=cam0), INV, b"error_kind")
+    assert refused(est(k=cam0, dist=0.0), INV, b"K needs")
+    assert refused(est(prm=thr0, dist=0.0), INV, b"normalised threshold")
+    assert refused(est(dist=0.0, n=4), INV, b"dist must")
+    assert refused(est(pts=False, n=4), INV, b"bad point arrays")
+    assert refused(est(n=5), INV, b"ctx is null") and est_zeroed()

@@ -1,13 +1,16 @@
 """CPU: the C restatement of docs/SPEC.md S36-S39 (tests/pnp_ref.c) against independent numpy references: the planted
 pose among the P3P candidates, every candidate a rotation that reprojects its three points, the real-root count of the
 quartic against np.roots, the reprojection test against a float64 pixel error, the sampler and camera rules, a whole
-run that finds the planted pose, and the S40 refinement against scipy.optimize.least_squares on the same inliers."""
+run that finds the planted pose, and the S40 refinement against scipy.optimize.least_squares on the same inliers; plus
+the argument checks of the shipped entry points, which need no device."""
+import ctypes as C
+
 import numpy as np
 from scipy.optimize import least_squares
 from scipy.spatial.transform import Rotation
 
 import pnp_ref as R
-from points_matching_amd import synth
+from points_matching_amd import api, synth
 
 
 def _rot(rng, s=0.5):
@@ -203,3 +206,198 @@ def test_refinement_status_rules():
     assert info.cost_out == info.cost_in
     out, info = R.refine(xyz, uv, k, inl.astype(np.uint8), Rt0, 0)                # max_iters 0
     assert info.status == 1 and (out == Rt0).all()
+
+
+def test_library_rejects_bad_arguments_without_a_device():
+    """Every check of the seven entry points, tripped alone and in pairs that pin the order, with ctx = NULL: the checks
+    all sit before the ctx check.  Messages are matched on the text after PM_REQUIRE's function-name prefix."""
+    L = api.lib()
+    INV, FEW = api.PM_E_INVALID, api.PM_E_TOO_FEW
+    xyz, uv = np.zeros((10, 3), np.float32), np.zeros((10, 2), np.float32)
+    m = np.ones(10, np.uint8)
+    cam = api.Camera(800.0, 800.0, 320.0, 240.0)
+    cam0, camnan = api.Camera(800.0, -1.0, 320.0, 240.0), api.Camera(800.0, 800.0, 320.0, float("nan"))
+    good = api.RansacParams(0, 10, 1, 2.0, api.PM_ERR_REPROJ)
+    kind = api.RansacParams(0, 10, 1, 2.0, api.PM_ERR_SAMPSON)
+    empty = api.RansacParams(5, 5, 1, 2.0, api.PM_ERR_REPROJ)
+    neg = api.RansacParams(-1, 5, 1, 2.0, api.PM_ERR_REPROJ)
+    high = api.RansacParams(0, (1 << 32) // 4 + 1, 1, 2.0, api.PM_ERR_REPROJ)
+    wide = api.RansacParams(0, ((1 << 31) - 1) // 4 + 1, 1, 2.0, api.PM_ERR_REPROJ)
+    thr0 = api.RansacParams(0, 10, 1, 0.0, api.PM_ERR_REPROJ)
+    thrinf = api.RansacParams(0, 10, 1, float("inf"), api.PM_ERR_REPROJ)
+    Rm, t, Rt48 = np.zeros(9), np.zeros(3), np.zeros(48)
+    counts, mask = np.zeros(4, np.int32), np.zeros(10, np.uint8)
+    key, ninl, nm = C.c_uint64(), C.c_int(), C.c_int()
+    info = api.HRefineInfo()
+    Rin, tin = np.eye(3).reshape(9), np.array([0.1, 0.2, 3.0])
+    nz = [10]
+
+    def ref(p):
+        return C.byref(p) if p is not None else None
+
+    def refused(rc, status, frag):
+        msg = L.pm_last_error()
+        assert rc == status and frag in msg, (rc, msg)
+        return True
+
+    def poison(n):
+        nz[0] = max(n, 0)                                        # the mask is zeroed over n entries
+        for a in (Rm, t, Rt48):
+            a[...] = 7.0
+        counts[:] = 7
+        mask[:] = 7
+        key.value, ninl.value, nm.value, info.status, info.n_used, info.cost_in = 7, 7, 7, 7, 7, 7.0
+
+    def zeroed(with_info):
+        return (not Rm.any() and not t.any() and not mask[:nz[0]].any() and (mask[nz[0]:] == 7).all() and
+                ninl.value == 0 and key.value == 0 and
+                (not with_info or (info.status == 2 and info.n_used == 0 and info.cost_in == 0.0)))
+
+    # ---- pm_ransac_pnp: params (null, range, kind, threshold), K, point arrays, n < 4, ctx
+    def run(prm=good, k=cam, n=10, pts=True):
+        poison(n)
+        return L.pm_ransac_pnp(None, api._p(xyz) if pts else None, api._p(uv) if pts else None, n, ref(k), ref(prm),
+                               api._p(Rm), api._p(t), api._p(mask), C.byref(ninl), C.byref(key))
+
+    assert refused(run(prm=None), INV, b"params is null") and zeroed(False)
+    for prm in (empty, neg, high):
+        assert refused(run(prm=prm), INV, b"sample ids must") and zeroed(False)
+    assert refused(run(prm=wide), INV, b"split the range")
+    assert refused(run(prm=kind), INV, b"error_kind") and zeroed(False)
+    assert refused(run(prm=thr0), INV, b"thresh_px") and refused(run(prm=thrinf), INV, b"thresh_px")
+    assert refused(run(k=None), INV, b"K is null") and zeroed(False)
+    assert refused(run(k=cam0), INV, b"K needs") and refused(run(k=camnan), INV, b"K needs")
+    assert refused(run(pts=False), INV, b"bad point arrays") and refused(run(n=-1), INV, b"bad point arrays")
+    assert refused(run(n=3), FEW, b"need at least 4") and zeroed(False)
+    assert refused(run(n=0, pts=False), FEW, b"need at least 4")
+    assert refused(run(prm=None, k=None), INV, b"params is null")
+    assert refused(run(prm=wide, k=None), INV, b"split the range")
+    assert refused(run(prm=kind, k=cam0), INV, b"error_kind")
+    assert refused(run(prm=thr0, k=None), INV, b"thresh_px")
+    assert refused(run(k=cam0, pts=False), INV, b"K needs")
+    assert refused(run(pts=False, n=3), INV, b"bad point arrays")
+    assert refused(run(n=4), INV, b"ctx is null") and zeroed(False)     # ctx last: everything else passed
+
+    # ---- pm_ransac_pnp_from_hyp: as above over [hyp, hyp + 1) (the range check reports a bad hyp), the candidates' outputs
+    # before the point arrays
+    def hyp(prm=good, h=0, k=cam, n=10, pts=True, rt=Rt48, cnt=counts):
+        poison(n)
+        return L.pm_ransac_pnp_from_hyp(None, api._p(xyz) if pts else None, api._p(uv) if pts else None, n, ref(k),
+                                        ref(prm), C.c_int64(h), api._p(rt), api._p(cnt), C.byref(nm))
+
+    def hyp_zeroed():
+        return not Rt48.any() and (counts == -1).all() and nm.value == 0
+
+    assert refused(hyp(prm=None), INV, b"params is null") and hyp_zeroed()
+    for h in (-1, (1 << 32) // 4):
+        assert refused(hyp(h=h), INV, b"sample ids must") and hyp_zeroed()
+    assert refused(hyp(prm=kind), INV, b"error_kind") and refused(hyp(prm=thr0), INV, b"thresh_px")
+    assert refused(hyp(k=None), INV, b"K is null") and refused(hyp(k=cam0), INV, b"K needs")
+    assert refused(hyp(rt=None), INV, b"null Rt or counts") and (counts == -1).all() and nm.value == 0
+    assert refused(hyp(cnt=None), INV, b"null Rt or counts") and not Rt48.any()
+    assert refused(hyp(pts=False), INV, b"bad point arrays")
+    assert refused(hyp(n=3), FEW, b"need at least 4") and hyp_zeroed()
+    assert refused(hyp(prm=None, h=-1), INV, b"params is null")
+    assert refused(hyp(h=-1, prm=kind), INV, b"sample ids must")
+    assert refused(hyp(prm=thr0, k=None), INV, b"thresh_px")
+    assert refused(hyp(k=cam0, rt=None), INV, b"K needs")
+    assert refused(hyp(rt=None, pts=False), INV, b"null Rt or counts")
+    assert refused(hyp(pts=False, n=3), INV, b"bad point arrays")
+    assert refused(hyp(prm=empty, h=(1 << 32) // 4 - 1, n=4), INV, b"ctx is null") and hyp_zeroed()    # p's own range is unused
+
+    # ---- pm_ransac_pnp_run_dev: outputs, mask_len, params, K, view, ctx
+    view = api.PnpView(1, 1, None, 10, 0)
+    d = C.c_void_p(16)                                           # never dereferenced: the calls fail before any launch
+
+    def dev(v=view, k=cam, prm=good, outs=(d, d, d, d), mask_len=10):
+        return L.pm_ransac_pnp_run_dev(None, ref(v), ref(k), ref(prm), outs[0], outs[1], outs[2], mask_len, outs[3])
+
+    for i in range(4):
+        assert refused(dev(outs=tuple(None if j == i else d for j in range(4))), INV, b"null argument")
+    assert refused(dev(mask_len=-1), INV, b"mask_len")
+    assert refused(dev(prm=None), INV, b"params is null")
+    assert refused(dev(prm=empty), INV, b"sample ids must") and refused(dev(prm=wide), INV, b"split the range")
+    assert refused(dev(prm=kind), INV, b"error_kind") and refused(dev(prm=thr0), INV, b"thresh_px")
+    assert refused(dev(k=None), INV, b"K is null") and refused(dev(k=cam0), INV, b"K needs")
+    for v in (None, api.PnpView(None, 1, None, 10, 0), api.PnpView(1, None, None, 10, 0), api.PnpView(1, 1, None, 0, 0)):
+        assert refused(dev(v=v), INV, b"need a view")
+    assert refused(dev(outs=(d, d, d, None), mask_len=-1), INV, b"null argument")
+    assert refused(dev(mask_len=-1, prm=None), INV, b"mask_len")
+    assert refused(dev(prm=kind, k=None), INV, b"error_kind")
+    assert refused(dev(k=cam0, v=None), INV, b"K needs")
+    assert refused(dev(mask_len=0), INV, b"ctx is null")
+    assert refused(dev(), INV, b"ctx is null")
+
+    # ---- pm_pnp_refine: R_in / t_in / R_out / t_out before everything (nothing written), then K, max_iters, arrays, n, ctx
+    def refine(k=cam, mi=m, r_in=Rin, t_in=tin, iters=20, r_out=Rm, t_out=t, n=10, pts=True):
+        poison(n)
+        return L.pm_pnp_refine(None, api._p(xyz) if pts else None, api._p(uv) if pts else None, n, ref(k), api._p(mi),
+                               api._p(r_in), api._p(t_in), iters, api._p(r_out), api._p(t_out), C.byref(info))
+
+    def passed_through():
+        return (Rm == Rin).all() and (t == tin).all() and info.status == 1 and info.n_used == 0 and info.cost_in == 0.0
+
+    for kw in ({"r_in": None}, {"t_in": None}, {"r_out": None}, {"t_out": None}):
+        assert refused(refine(**kw), INV, b"null R or t")                            # before any output is written
+        assert info.status == 7 and (Rm == 7.0).all() and (t == 7.0).all()
+    assert refused(refine(k=None), INV, b"K is null") and passed_through()
+    assert refused(refine(k=cam0), INV, b"K needs") and refused(refine(k=camnan), INV, b"K needs") and passed_through()
+    for iters in (-1, 101):
+        assert refused(refine(iters=iters), INV, b"max_iters") and passed_through()
+    assert refused(refine(mi=None), INV, b"bad point or mask arrays") and passed_through()
+    assert refused(refine(pts=False), INV, b"bad point or mask arrays") and refused(refine(n=-1), INV, b"bad point or mask")
+    assert refused(refine(n=3), FEW, b"need at least 4") and passed_through()           # R_out, t_out = R_in, t_in
+    assert refused(refine(n=0, mi=None, pts=False), FEW, b"need at least 4")
+    assert refused(refine(r_in=None, k=None), INV, b"null R or t")
+    assert refused(refine(k=cam0, iters=-1), INV, b"K needs")
+    assert refused(refine(iters=101, mi=None), INV, b"max_iters")
+    assert refused(refine(mi=None, n=3), INV, b"bad point or mask arrays")
+    assert refused(refine(iters=0, n=4), INV, b"ctx is null") and passed_through()
+    assert refused(refine(iters=100), INV, b"ctx is null")
+
+    # ---- pm_pnp_refine_dev: pointers (info optional), K, max_iters, view, ctx
+    def refd(v=view, k=cam, args=(d, d, d), iters=20, inf=None):
+        return L.pm_pnp_refine_dev(None, ref(v), ref(k), args[0], args[1], iters, args[2], inf)
+
+    for i in range(3):
+        assert refused(refd(args=tuple(None if j == i else d for j in range(3))), INV, b"null argument")
+    assert refused(refd(k=None), INV, b"K is null") and refused(refd(k=cam0), INV, b"K needs")
+    assert refused(refd(iters=-1), INV, b"max_iters") and refused(refd(iters=101), INV, b"max_iters")
+    assert refused(refd(v=None), INV, b"need a view") and refused(refd(v=api.PnpView(1, 1, None, 0, 0)), INV, b"need a view")
+    assert refused(refd(args=(None, d, d), k=None), INV, b"null argument")
+    assert refused(refd(k=cam0, iters=-1), INV, b"K needs")
+    assert refused(refd(iters=-1, v=None), INV, b"max_iters")
+    assert refused(refd(), INV, b"ctx is null") and refused(refd(inf=d), INV, b"ctx is null")
+
+    # ---- pm_solve_pnp_ransac: params, K, max_iters, point arrays, n < 4, ctx
+    def solve(prm=good, k=cam, iters=20, n=10, pts=True):
+        poison(n)
+        return L.pm_solve_pnp_ransac(None, api._p(xyz) if pts else None, api._p(uv) if pts else None, n, ref(k), ref(prm),
+                                     iters, api._p(Rm), api._p(t), api._p(mask), C.byref(ninl), C.byref(key), C.byref(info))
+
+    assert refused(solve(prm=None), INV, b"params is null") and zeroed(True)
+    assert refused(solve(prm=empty), INV, b"sample ids must") and refused(solve(prm=wide), INV, b"split the range")
+    assert refused(solve(prm=kind), INV, b"error_kind") and refused(solve(prm=thr0), INV, b"thresh_px") and zeroed(True)
+    assert refused(solve(k=None), INV, b"K is null") and refused(solve(k=cam0), INV, b"K needs") and zeroed(True)
+    assert refused(solve(iters=-1), INV, b"max_iters") and refused(solve(iters=101), INV, b"max_iters") and zeroed(True)
+    assert refused(solve(pts=False), INV, b"bad point arrays")
+    assert refused(solve(n=3), FEW, b"need at least 4") and zeroed(True)
+    assert refused(solve(prm=kind, k=cam0), INV, b"error_kind")       # a bad K together with a wrong kind reports the kind
+    assert refused(solve(prm=thr0, k=cam0), INV, b"thresh_px")
+    assert refused(solve(k=cam0, iters=-1), INV, b"K needs")
+    assert refused(solve(iters=-1, pts=False), INV, b"max_iters")
+    assert refused(solve(pts=False, n=3), INV, b"bad point arrays")
+    assert refused(solve(n=4), INV, b"ctx is null") and zeroed(True)
+
+    # ---- pm_gather_pnp_dev: pointers (the count is optional), sizes, ctx
+    def gather(args=(d, d, d, d, d, d), cap=10, n_kp=5, n_obj=5):
+        mt, cnt, kp, obj, o_uv, o_xyz = args
+        return L.pm_gather_pnp_dev(None, mt, cnt, cap, kp, n_kp, obj, n_obj, o_uv, o_xyz)
+
+    for i in (0, 2, 3, 4, 5):
+        assert refused(gather(args=tuple(None if j == i else d for j in range(6))), INV, b"null argument")
+    assert refused(gather(cap=0), INV, b"need cap >= 1")
+    assert refused(gather(n_kp=-1), INV, b"need cap >= 1") and refused(gather(n_obj=-1), INV, b"need cap >= 1")
+    assert refused(gather(args=(None, d, d, d, d, d), cap=0), INV, b"null argument")
+    assert refused(gather(args=(d, None, d, d, d, d), n_kp=0, n_obj=0), INV, b"ctx is null")
+    assert refused(gather(), INV, b"ctx is null")
