@@ -67,7 +67,7 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * pm_ctx_timing_get: mean milliseconds and launch count of the named kernel since the last
  * pm_ctx_timing_reset (synchronises the stream).  Names: "knn_l2_prep", "knn_l2_mfma_f16",
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
- * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "concat_points",
+ * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "filter_cross_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
  * "essential_solve", "ransac_e_fused", "recover_pose". */
@@ -254,6 +254,56 @@ int pm_filter_ratio_gather_dev(pm_ctx* ctx, const pm_match* d_knn, int nq, int k
 int pm_filter_midpoint_gather_dev(pm_ctx* ctx, const pm_match* d_m, int n, int k,
                                   const float* d_kp1_xy, const float* d_kp2_xy, pm_match* d_good,
                                   float* d_xy1, float* d_xy2, int32_t* d_n_good, double* d_minmax);
+/* ---- cross-check (cv::BFMatcher(norm, crossCheck = true): mutual nearest neighbours) — docs/SPEC.md S41-S42 --------
+ * fwd: nq x kf records, the matcher's output for (q, t); rev: nt x kr records, the matcher's output for (t, q), so its
+ * trainIdx names a QUERY row.  Row i survives iff j = fwd[i*kf].trainIdx lies in [0, nt), rev[j*kr].trainIdx == i, and
+ * with PM_CROSS_RATIO_FWD row i of fwd / with PM_CROSS_RATIO_REV row j of rev also passes the ratio test of
+ * pm_filter_ratio (d1 < ratio * d2, second neighbour present).  Survivors keep query order and emit fwd[i*kf]
+ * unchanged; their trainIdx are pairwise distinct (a one-to-one matching).  Indices only are compared: ties were
+ * settled by the matcher in both directions (lower index first). */
+#define PM_CROSS_RATIO_FWD 1    /* + ratio test on the forward row (needs kf >= 2) */
+#define PM_CROSS_RATIO_REV 2    /* + ratio test on the reverse row (needs kr >= 2) */
+/* Host-side, O(nq).  out holds nq records.  PM_E_INVALID: kf / kr < 1 or too small for cross_flags, unknown flag bits,
+ * null arrays.  nq == 0 or nt == 0: no survivor.  ratio is read only with a PM_CROSS_RATIO_* flag. */
+int pm_filter_cross(const pm_match* fwd, int nq, int kf, const pm_match* rev, int nt, int kr,
+                    int cross_flags, float ratio, pm_match* out, int* n_out);
+/* Device-resident form: the rule above + stable compaction in query order + keypoint gather in ONE launch (a third
+ * predicate of the pm_filter_ratio_gather_dev kernel; a trainIdx outside [0, nt) is a drop, never an address).  Output
+ * contract of pm_filter_ratio_gather_dev: d_good nq records, d_xy1 / d_xy2 nq x 2 floats (NULL together with the
+ * keypoint arrays), *d_n_good the survivor count.  d_xy1 row = d_kp1_xy[i], d_xy2 row = d_kp2_xy[j].  Timed as
+ * "filter_cross_gather".  Refused on a capturing stream like the other compaction calls. */
+int pm_filter_cross_gather_dev(pm_ctx* ctx, const pm_match* d_fwd, int nq, int kf, const pm_match* d_rev, int nt, int kr,
+                               int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
+                               pm_match* d_good, float* d_xy1, float* d_xy2, int32_t* d_n_good);
+/* One-call forms (S42), everything on the context's stream with no host round trip: forward pass pm_bf_knn_*_dev(q, t)
+ * with k = 2 if PM_CROSS_RATIO_FWD else 1 into d_fwd, reverse pass pm_bf_knn_*_dev(t, q) with k = 2 if
+ * PM_CROSS_RATIO_REV else 1 into d_rev, then pm_filter_cross_gather_dev — the outputs of those three calls, bit for
+ * bit.  d_fwd (nq x kf) and d_rev (nt x kr) are caller-owned record buffers and hold the two k-NN lists afterwards.
+ * knn_flags (pm_bf_knn_l2_f32_dev) go to both passes, except PM_KNN_HINT_UNIT_NORM, a statement about the train rows
+ * only, which the reverse pass does not receive.  The reverse pass is a second full matcher run.  nq == 0 or nt == 0:
+ * no survivor, PM_OK.  The survivor arrays feed a pm_points_view {d_xy1, d_xy2, counts = d_n_good} like those of
+ * pm_bf_knn_l2_ratio_dev.  Refused on a capturing stream before anything is enqueued. */
+int pm_bf_match_cross_l2_f32_dev(pm_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt, int dim, int knn_flags,
+                                 int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
+                                 pm_match* d_fwd, pm_match* d_rev, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                 int32_t* d_n_good);
+int pm_bf_match_cross_l2_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim,
+                                int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
+                                pm_match* d_fwd, pm_match* d_rev, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                int32_t* d_n_good);
+int pm_bf_match_cross_hamming_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytes,
+                                     int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
+                                     pm_match* d_fwd, pm_match* d_rev, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                     int32_t* d_n_good);
+/* Host conveniences (upload, run, download; block like pm_bf_knn_l2_f32): out holds up to nq records, *n_out their
+ * number. */
+int pm_bf_match_cross_l2_f32(pm_ctx* ctx, const float* q, int nq, const float* t, int nt, int dim, int knn_flags,
+                             int cross_flags, float ratio, pm_match* out, int* n_out);
+int pm_bf_match_cross_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int dim, int cross_flags,
+                            float ratio, pm_match* out, int* n_out);
+int pm_bf_match_cross_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int bytes,
+                                 int cross_flags, float ratio, pm_match* out, int* n_out);
+
 /* Multi-GPU glue: concatenates `parts` padded blocks of `stride` points (d_counts[p] valid in
  * block p), e.g. the all-gathered per-rank survivors of a query-row-sharded matcher, into one
  * contiguous correspondence array in part order; *d_n_total = sum of counts. */

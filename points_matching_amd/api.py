@@ -20,6 +20,8 @@ PM_KNN_FORCE_F32 = 2
 PM_KNN_HINT_INTEGER = 4
 PM_KNN_HINT_U8 = 8
 PM_KNN_HINT_UNIT_NORM = 16
+PM_CROSS_RATIO_FWD = 1     # cross-check (S41): + ratio test on the forward row
+PM_CROSS_RATIO_REV = 2     # ... on the reverse row
 PM_ERR_SAMPSON = 0
 PM_ERR_SYM_EPIPOLAR = 1
 PM_ERR_REPROJ = 2          # robust homography and affine (pm_ransac_homography*, pm_ransac_affine*)
@@ -58,6 +60,9 @@ EXPORTS = [
     "pm_recover_pose_dev", "pm_estimate_pose",
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
     "pm_solve_pnp_ransac", "pm_gather_pnp_dev",
+    "pm_filter_cross", "pm_filter_cross_gather_dev",
+    "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
+    "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
 ]
 
 
@@ -210,6 +215,18 @@ def filter_ratio(knn, ratio):
     return out[:n.value].copy()
 
 
+def filter_cross(fwd, rev, cross_flags=0, ratio=0.8):
+    """Cross-check (SPEC S41): fwd (nq, kf) records of the matcher on (q, t), rev (nt, kr) records on (t, q)."""
+    fwd = np.ascontiguousarray(fwd, MATCH_DTYPE)
+    rev = np.ascontiguousarray(rev, MATCH_DTYPE)
+    nq, kf = fwd.shape
+    nt, kr = rev.shape
+    out = np.zeros(max(nq, 1), MATCH_DTYPE)
+    n = C.c_int()
+    _check(lib().pm_filter_cross(_p(fwd), nq, kf, _p(rev), nt, kr, cross_flags, C.c_float(ratio), _p(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
 def match_indices(m):
     m = np.ascontiguousarray(m, MATCH_DTYPE).reshape(-1)
     qi = np.zeros(m.size, np.int32)
@@ -349,6 +366,56 @@ class Context:
                                                 C.c_void_p(dkp1_ptr), C.c_void_p(dkp2_ptr),
                                                 C.c_void_p(dgood_ptr), C.c_void_p(dxy1_ptr),
                                                 C.c_void_p(dxy2_ptr), C.c_void_p(dn_ptr)))
+
+    def filter_cross_gather_dev(self, dfwd_ptr, nq, kf, drev_ptr, nt, kr, cross_flags, ratio, dkp1_ptr, dkp2_ptr, dgood_ptr,
+                                dxy1_ptr, dxy2_ptr, dn_ptr):
+        _check(lib().pm_filter_cross_gather_dev(self._h, C.c_void_p(dfwd_ptr), nq, kf, C.c_void_p(drev_ptr), nt, kr,
+                                                cross_flags, C.c_float(ratio), C.c_void_p(dkp1_ptr or 0),
+                                                C.c_void_p(dkp2_ptr or 0), C.c_void_p(dgood_ptr), C.c_void_p(dxy1_ptr or 0),
+                                                C.c_void_p(dxy2_ptr or 0), C.c_void_p(dn_ptr)))
+
+    # -- one-call cross-check matching (SPEC S42): forward pass, reverse pass, fused filter + gather ----------------
+    def bf_match_cross_l2_dev(self, dq_ptr, nq, dt_ptr, nt, dim, knn_flags, cross_flags, ratio, dkp1_ptr, dkp2_ptr, dfwd_ptr,
+                              drev_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        _check(lib().pm_bf_match_cross_l2_f32_dev(self._h, C.c_void_p(dq_ptr), nq, C.c_void_p(dt_ptr), nt, dim, knn_flags,
+                                                  cross_flags, C.c_float(ratio), C.c_void_p(dkp1_ptr or 0),
+                                                  C.c_void_p(dkp2_ptr or 0), C.c_void_p(dfwd_ptr), C.c_void_p(drev_ptr),
+                                                  C.c_void_p(dgood_ptr), C.c_void_p(dxy1_ptr or 0), C.c_void_p(dxy2_ptr or 0),
+                                                  C.c_void_p(dn_ptr)))
+
+    def bf_match_cross_l2_u8_dev(self, dq_ptr, nq, dt_ptr, nt, dim, cross_flags, ratio, dkp1_ptr, dkp2_ptr, dfwd_ptr, drev_ptr,
+                                 dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        _check(lib().pm_bf_match_cross_l2_u8_dev(self._h, C.c_void_p(dq_ptr), nq, C.c_void_p(dt_ptr), nt, dim, cross_flags,
+                                                 C.c_float(ratio), C.c_void_p(dkp1_ptr or 0), C.c_void_p(dkp2_ptr or 0),
+                                                 C.c_void_p(dfwd_ptr), C.c_void_p(drev_ptr), C.c_void_p(dgood_ptr),
+                                                 C.c_void_p(dxy1_ptr or 0), C.c_void_p(dxy2_ptr or 0), C.c_void_p(dn_ptr)))
+
+    def bf_match_cross_hamming_dev(self, dq_ptr, nq, dt_ptr, nt, nbytes, cross_flags, ratio, dkp1_ptr, dkp2_ptr, dfwd_ptr,
+                                   drev_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        _check(lib().pm_bf_match_cross_hamming_u8_dev(self._h, C.c_void_p(dq_ptr), nq, C.c_void_p(dt_ptr), nt, nbytes,
+                                                      cross_flags, C.c_float(ratio), C.c_void_p(dkp1_ptr or 0),
+                                                      C.c_void_p(dkp2_ptr or 0), C.c_void_p(dfwd_ptr), C.c_void_p(drev_ptr),
+                                                      C.c_void_p(dgood_ptr), C.c_void_p(dxy1_ptr or 0),
+                                                      C.c_void_p(dxy2_ptr or 0), C.c_void_p(dn_ptr)))
+
+    def _match_cross_host(self, fn, q, t, dtype, *mid):
+        q = np.ascontiguousarray(q, dtype)
+        t = np.ascontiguousarray(t, dtype)
+        assert q.ndim == 2 and t.ndim == 2 and t.shape[1] == q.shape[1]
+        out = np.zeros(max(q.shape[0], 1), MATCH_DTYPE)
+        n = C.c_int()
+        _check(fn(self._h, _p(q), q.shape[0], _p(t), t.shape[0], q.shape[1], *mid, _p(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def bf_match_cross_l2(self, q, t, cross_flags=0, ratio=0.8, knn_flags=0):
+        """Mutual nearest neighbours of float rows (pm_bf_match_cross_l2_f32): the survivors, in query order."""
+        return self._match_cross_host(lib().pm_bf_match_cross_l2_f32, q, t, np.float32, knn_flags, cross_flags, C.c_float(ratio))
+
+    def bf_match_cross_l2_u8(self, q, t, cross_flags=0, ratio=0.8):
+        return self._match_cross_host(lib().pm_bf_match_cross_l2_u8, q, t, np.uint8, cross_flags, C.c_float(ratio))
+
+    def bf_match_cross_hamming(self, q, t, cross_flags=0, ratio=0.8):
+        return self._match_cross_host(lib().pm_bf_match_cross_hamming_u8, q, t, np.uint8, cross_flags, C.c_float(ratio))
 
     def filter_midpoint_gather_dev(self, dm_ptr, n, k, dkp1_ptr, dkp2_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr,
                                    dminmax_ptr=0):

@@ -3,7 +3,8 @@
 // KeyPoint::convert main.cpp:89-91, fused into one stable compaction so that a matched batch
 // never leaves HBM between the matcher and the RANSAC kernels.  Survivors keep query order
 // (the reference's push_back order, main.cpp:63-68).  Same predicate as pm_filter_ratio:
-// second neighbour present and d1 < ratio * d2 (float multiply, strict).
+// second neighbour present and d1 < ratio * d2 (float multiply, strict).  The cross-check rule of SPEC S41 (mutual
+// nearest neighbours, pm_filter_cross) is a third predicate of the same compaction.
 #include "pm_common.hpp"
 
 namespace {
@@ -20,10 +21,16 @@ constexpr int FG_ROWS = 256;
 constexpr int FG_MAX_BLOCKS = 4096;          // 1M query rows; more -> the caller is told so
 constexpr unsigned FG_SPIN_LIMIT = 200000u;
 
-enum { FG_RATIO = 0, FG_MIDPOINT = 1 };
+enum { FG_RATIO = 0, FG_MIDPOINT = 1, FG_CROSS = 2 };
+// FG_CROSS: the reverse k-NN list (nt x kr records whose trainIdx names a query row) and PM_CROSS_RATIO_* bits
+struct FgCross {
+    const pm_match* rev;
+    int nt, kr, flags;
+};
 struct FgParam {
     float ratio;       // FG_RATIO: d1 < ratio * d2
     double cut;        // FG_MIDPOINT: (double)d < cut, cut = min + (max - min)/2 (main.cpp:65)
+    FgCross x;
 };
 
 template <int MODE>
@@ -32,6 +39,28 @@ __device__ __forceinline__ bool fg_keep(const pm_match* __restrict__ knn, int i,
     const uint4 a = *reinterpret_cast<const uint4*>(knn + static_cast<size_t>(i) * k);
     best.queryIdx = static_cast<int>(a.x); best.trainIdx = static_cast<int>(a.y);
     best.imgIdx = static_cast<int>(a.z);   best.distance = __uint_as_float(a.w);
+    if (MODE == FG_CROSS) {
+        // S41: j = first neighbour of row i; keep iff j is a train row and the first neighbour of row j in the reverse
+        // list is i.  The reverse record is loaded only under the range guard: a trainIdx outside [0, nt) is a drop.
+        const int j = static_cast<int>(a.y);
+        bool ok = static_cast<unsigned>(j) < static_cast<unsigned>(prm.x.nt);
+        if (prm.x.flags & PM_CROSS_RATIO_FWD) {
+            const uint4 b = *reinterpret_cast<const uint4*>(knn + static_cast<size_t>(i) * k + 1);
+            const float rhs = prm.ratio * __uint_as_float(b.w);
+            ok = ok && static_cast<int>(b.y) >= 0 && best.distance < rhs;
+        }
+        if (ok) {
+            const pm_match* r = prm.x.rev + static_cast<size_t>(j) * prm.x.kr;
+            const uint4 c = *reinterpret_cast<const uint4*>(r);
+            ok = static_cast<int>(c.y) == i;
+            if (prm.x.flags & PM_CROSS_RATIO_REV) {
+                const uint4 d = *reinterpret_cast<const uint4*>(r + 1);
+                const float rhs = prm.ratio * __uint_as_float(d.w);
+                ok = ok && static_cast<int>(d.y) >= 0 && __uint_as_float(c.w) < rhs;
+            }
+        }
+        return ok;
+    }
     if (MODE == FG_RATIO) {
         const uint4 b = *reinterpret_cast<const uint4*>(knn + static_cast<size_t>(i) * k + 1);
         const float rhs = prm.ratio * __uint_as_float(b.w);
@@ -70,17 +99,16 @@ __global__ __launch_bounds__(FG_ROWS) void midpoint_minmax(const pm_match* __res
     }
 }
 
+// The compaction itself, shared by the three predicates (the kernels below differ in their arguments only).
 template <int MODE>
-__global__ __launch_bounds__(FG_ROWS) void filter_ratio_gather(const pm_match* __restrict__ knn, int nq, int k,
-                                                               float ratio, const float* __restrict__ kp1,
-                                                               const float* __restrict__ kp2,
-                                                               pm_match* __restrict__ good, float* __restrict__ xy1,
-                                                               float* __restrict__ xy2, int* __restrict__ n_out,
-                                                               unsigned* __restrict__ blk_counts, unsigned epoch,
-                                                               const unsigned long long* __restrict__ mm,
-                                                               double* __restrict__ minmax_out)
+__device__ __forceinline__ void fg_compact(const pm_match* __restrict__ knn, int nq, int k, float ratio,
+                                           const float* __restrict__ kp1, const float* __restrict__ kp2,
+                                           pm_match* __restrict__ good, float* __restrict__ xy1, float* __restrict__ xy2,
+                                           int* __restrict__ n_out, unsigned* __restrict__ blk_counts, unsigned epoch,
+                                           const unsigned long long* __restrict__ mm, double* __restrict__ minmax_out,
+                                           const FgCross& cross)
 {
-    FgParam prm{ratio, 0.0};
+    FgParam prm{ratio, 0.0, cross};
     double lo_d = 1.0, hi_d = 0.0;
     if (MODE == FG_MIDPOINT) {                     // the words were completed by midpoint_minmax (previous launch)
         lo_d = static_cast<double>(fg_unord(~static_cast<unsigned>(mm[0])));
@@ -97,7 +125,12 @@ __global__ __launch_bounds__(FG_ROWS) void filter_ratio_gather(const pm_match* _
     pm_match best;
     const bool keep = fg_keep<MODE>(knn, i < nq ? i : nq - 1, k, prm, best) && i < nq;
     float2 pa = {0.f, 0.f}, pb = {0.f, 0.f};
-    if (kp1) {
+    if (MODE == FG_CROSS) {                        // survivors only: row i itself (i < nq) and a trainIdx known to lie in [0, nt)
+        if (kp1 && keep) {
+            pa = *reinterpret_cast<const float2*>(kp1 + 2 * static_cast<size_t>(i));
+            pb = *reinterpret_cast<const float2*>(kp2 + 2 * static_cast<size_t>(best.trainIdx));
+        }
+    } else if (kp1) {
         pa = *reinterpret_cast<const float2*>(kp1 + 2 * static_cast<size_t>(best.queryIdx));
         pb = *reinterpret_cast<const float2*>(kp2 + 2 * static_cast<size_t>(best.trainIdx >= 0 ? best.trainIdx : 0));
     }
@@ -155,6 +188,30 @@ __global__ __launch_bounds__(FG_ROWS) void filter_ratio_gather(const pm_match* _
     }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(FG_ROWS) void filter_ratio_gather(const pm_match* __restrict__ knn, int nq, int k,
+                                                               float ratio, const float* __restrict__ kp1,
+                                                               const float* __restrict__ kp2,
+                                                               pm_match* __restrict__ good, float* __restrict__ xy1,
+                                                               float* __restrict__ xy2, int* __restrict__ n_out,
+                                                               unsigned* __restrict__ blk_counts, unsigned epoch,
+                                                               const unsigned long long* __restrict__ mm,
+                                                               double* __restrict__ minmax_out)
+{
+    fg_compact<MODE>(knn, nq, k, ratio, kp1, kp2, good, xy1, xy2, n_out, blk_counts, epoch, mm, minmax_out,
+                     FgCross{nullptr, 0, 0, 0});
+}
+
+// FG_CROSS: knn is the forward list (nq x k), cross names the reverse list
+__global__ __launch_bounds__(FG_ROWS) void filter_cross_gather(const pm_match* __restrict__ knn, int nq, int k, float ratio,
+                                                               const float* __restrict__ kp1, const float* __restrict__ kp2,
+                                                               pm_match* __restrict__ good, float* __restrict__ xy1,
+                                                               float* __restrict__ xy2, int* __restrict__ n_out,
+                                                               unsigned* __restrict__ blk_counts, unsigned epoch, FgCross cross)
+{
+    fg_compact<FG_CROSS>(knn, nq, k, ratio, kp1, kp2, good, xy1, xy2, n_out, blk_counts, epoch, nullptr, nullptr, cross);
+}
+
 // Concatenates `parts` padded point blocks (each `stride` points, counts[p] valid) into one
 // contiguous array in part order; used after the all-gather of the query-row-sharded matcher.
 __global__ __launch_bounds__(256) void concat_points(const float* __restrict__ xy1_parts,
@@ -186,10 +243,10 @@ __global__ __launch_bounds__(256) void concat_points(const float* __restrict__ x
 
 namespace {
 
-int fg_prepare(pm_ctx* ctx, int nq, int* nblk)
+int fg_prepare(pm_ctx* ctx, int nq, int* nblk, bool capture_checked = false)
 {
     *nblk = (nq + FG_ROWS - 1) / FG_ROWS;
-    PM_REFUSE_CAPTURE(ctx);
+    if (!capture_checked) PM_REFUSE_CAPTURE(ctx);
     PM_REQUIRE(*nblk <= FG_MAX_BLOCKS, PM_E_UNSUPPORTED, "more than 1M query rows per compaction call");
     if (!ctx->fg_counts) {
         // [FG_MAX_BLOCKS] survivor counts + 2 x 64-bit min/max words (8-byte aligned: FG_MAX_BLOCKS is even)
@@ -260,6 +317,38 @@ extern "C" int pm_filter_midpoint_gather_dev(pm_ctx* ctx, const pm_match* d_m, i
     PM_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(filter_ratio_gather<FG_MIDPOINT>, dim3(nblk), dim3(FG_ROWS), 0, ctx->stream, d_m, n, k, 0.f,
                        d_kp1_xy, d_kp2_xy, d_good, d_xy1, d_xy2, d_n_good, ctx->fg_counts, ctx->fg_epoch, mm, d_minmax);
+    PM_HIP_CHECK(hipGetLastError());
+    return PM_OK;
+}
+
+// SPEC S41 on the device: the mutual-nearest-neighbour rule (optionally with the ratio test on either row) as the
+// predicate of the same one-launch stable compaction; one dependent 16-byte load of the reverse record per lane.
+extern "C" int pm_filter_cross_gather_dev(pm_ctx* ctx, const pm_match* d_fwd, int nq, int kf, const pm_match* d_rev, int nt,
+                                          int kr, int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
+                                          pm_match* d_good, float* d_xy1, float* d_xy2, int32_t* d_n_good)
+{
+    PM_REQUIRE(ctx != nullptr && d_n_good != nullptr, PM_E_INVALID, "null argument");
+    PM_REFUSE_CAPTURE(ctx);
+    PM_REQUIRE(nq >= 0 && nt >= 0 && kf >= 1 && kr >= 1, PM_E_INVALID, "need nq, nt >= 0 and kf, kr >= 1");
+    PM_REQUIRE((cross_flags & ~(PM_CROSS_RATIO_FWD | PM_CROSS_RATIO_REV)) == 0, PM_E_INVALID, "unknown cross_flags bits");
+    PM_REQUIRE(!(cross_flags & PM_CROSS_RATIO_FWD) || kf >= 2, PM_E_INVALID, "PM_CROSS_RATIO_FWD needs kf >= 2");
+    PM_REQUIRE(!(cross_flags & PM_CROSS_RATIO_REV) || kr >= 2, PM_E_INVALID, "PM_CROSS_RATIO_REV needs kr >= 2");
+    PM_REQUIRE(nq == 0 || (d_fwd && d_good), PM_E_INVALID, "null match buffers");
+    PM_REQUIRE(nq == 0 || nt == 0 || d_rev, PM_E_INVALID, "null reverse records");
+    PM_REQUIRE((d_kp1_xy == nullptr) == (d_kp2_xy == nullptr), PM_E_INVALID, "give both keypoint arrays or none");
+    PM_REQUIRE(d_kp1_xy == nullptr || (d_xy1 && d_xy2), PM_E_INVALID, "null point outputs");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    pm::ScopedKernelTime t(ctx, "filter_cross_gather");
+    if (nq == 0 || nt == 0) {
+        PM_HIP_CHECK(hipMemsetAsync(d_n_good, 0, sizeof(int32_t), ctx->stream));
+        return PM_OK;
+    }
+    int nblk = 0;
+    const int rc = fg_prepare(ctx, nq, &nblk, /*capture_checked=*/true);
+    if (rc != PM_OK) return rc;
+    hipLaunchKernelGGL(filter_cross_gather, dim3(nblk), dim3(FG_ROWS), 0, ctx->stream, d_fwd, nq, kf, ratio, d_kp1_xy,
+                       d_kp2_xy, d_good, d_xy1, d_xy2, d_n_good, ctx->fg_counts, ctx->fg_epoch,
+                       FgCross{d_rev, nt, kr, cross_flags});
     PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
 }

@@ -323,6 +323,37 @@ int pm_filter_ratio(const pm_match* knn, int nq, int k, float ratio, pm_match* o
     return PM_OK;
 }
 
+// Cross-check (SPEC S41): row i survives iff its first neighbour j is a train row whose own first neighbour in the
+// reverse list is i; optionally the ratio test (S4) on row i of fwd and / or row j of rev.  Indices only.
+int pm_filter_cross(const pm_match* fwd, int nq, int kf, const pm_match* rev, int nt, int kr, int cross_flags,
+                    float ratio, pm_match* out, int* n_out)
+{
+    PM_REQUIRE(nq >= 0 && nt >= 0 && kf >= 1 && kr >= 1 && n_out, PM_E_INVALID, "bad argument");
+    PM_REQUIRE((cross_flags & ~(PM_CROSS_RATIO_FWD | PM_CROSS_RATIO_REV)) == 0, PM_E_INVALID, "unknown cross_flags bits");
+    PM_REQUIRE(!(cross_flags & PM_CROSS_RATIO_FWD) || kf >= 2, PM_E_INVALID, "PM_CROSS_RATIO_FWD needs kf >= 2");
+    PM_REQUIRE(!(cross_flags & PM_CROSS_RATIO_REV) || kr >= 2, PM_E_INVALID, "PM_CROSS_RATIO_REV needs kr >= 2");
+    PM_REQUIRE(nq == 0 || (fwd && out), PM_E_INVALID, "null forward / output records");
+    PM_REQUIRE(nq == 0 || nt == 0 || rev, PM_E_INVALID, "null reverse records");
+    auto ratio_ok = [ratio](const pm_match* row) {
+        if (row[0].trainIdx < 0 || row[1].trainIdx < 0) return false;
+        const float rhs = ratio * row[1].distance;
+        return row[0].distance < rhs;
+    };
+    int kept = 0;
+    for (int i = 0; i < nq; ++i) {
+        const pm_match* f = fwd + static_cast<size_t>(i) * kf;
+        const int j = f[0].trainIdx;
+        if (j < 0 || j >= nt) continue;
+        const pm_match* r = rev + static_cast<size_t>(j) * kr;
+        if (r[0].trainIdx != i) continue;
+        if ((cross_flags & PM_CROSS_RATIO_FWD) && !ratio_ok(f)) continue;
+        if ((cross_flags & PM_CROSS_RATIO_REV) && !ratio_ok(r)) continue;
+        out[kept++] = f[0];
+    }
+    *n_out = kept;
+    return PM_OK;
+}
+
 // ---- match list + gather (main.cpp:71-79, :89-91) ------------------------------------------
 
 int pm_match_indices(const pm_match* m, int n, int32_t* query_idx, int32_t* train_idx)

@@ -7,7 +7,7 @@
 //
 //   pm_cli --img1 left.pgm --img2 right.pgm [--max-kp 4000]        (image pair in: main.cpp:14-15, :22-40)
 //   pm_cli --desc1 a.pmm --desc2 b.pmm --kp1 ka.pmm --kp2 kb.pmm   (descriptor pair in)
-//          [--filter midpoint|ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
+//          [--filter midpoint|ratio|cross|cross-ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
@@ -18,6 +18,9 @@
 // size and reproducible (FLANN seeds its trees from C rand()); `--matcher flann` gives the reference's literal flow
 // (FLANN 1-NN -> midpoint filter -> 7-point LMedS).  The image front end (--img1/--img2) is a SIFT-style detector, not
 // the reference's SURF(8000) (main.cpp:22-40): no compatibility with OpenCV's keypoints is claimed.
+// --filter cross: mutual nearest neighbours (cv::BFMatcher crossCheck = true, docs/SPEC.md S41-S42): forward and reverse
+// matcher pass + the fused filter in one call; cross-ratio adds the ratio test (--ratio) on the forward row.  Brute-force
+// matcher on one GPU only (float and binary descriptors): with --matcher flann or --gpus / --mgpu it is a usage error.
 // --gpus N (> 1): matcher rows and hypothesis ids are sharded over N GPUs through pm_mgpu_match_ransac (RCCL behind
 // the C ABI); needs --filter ratio --method ransac8 (the sharded form of the path, BASELINE config C4).
 // --print-epilines / --epilines: main.cpp:127-142 — the epipolar lines of the image-1 points in image 2
@@ -243,7 +246,7 @@ int main(int argc, char** argv)
         if (d1.rows < 8 || d2.rows < 8) { fprintf(stderr, "pm_cli: too few keypoints\n"); return 1; }
     } else {
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
-        fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio] "
+        fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
                         "[--matcher bf|flann] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
@@ -258,7 +261,12 @@ int main(int argc, char** argv)
     }
     const bool want_ratio = filter == "ratio";
     if (method != "ransac8" && method != "7point-lmeds") { fprintf(stderr, "pm_cli: --method ransac8|7point-lmeds\n"); return 2; }
-    if (!want_ratio && filter != "midpoint") { fprintf(stderr, "pm_cli: --filter midpoint|ratio\n"); return 2; }
+    const bool want_cross = filter == "cross" || filter == "cross-ratio";
+    if (!want_ratio && !want_cross && filter != "midpoint") { fprintf(stderr, "pm_cli: --filter midpoint|ratio|cross|cross-ratio\n"); return 2; }
+    if (want_cross && (matcher != "bf" || gpus > 1 || force_mgpu)) {
+        fprintf(stderr, "pm_cli: --filter %s needs the brute-force matcher on a single GPU (no --matcher flann, --gpus N, --mgpu)\n", filter.c_str());
+        return 2;
+    }
     if (method == "ransac8" && !iters_given) iters = 10000;
     if ((gpus > 1 || force_mgpu) && (!want_ratio || method != "ransac8")) {
         fprintf(stderr, "pm_cli: --gpus N needs --filter ratio --method ransac8\n");
@@ -323,7 +331,16 @@ int main(int argc, char** argv)
     // ---- matcher.match(imageDesc1, imageDesc2, matchePoints, Mat())            main.cpp:42-46
     const int k = want_ratio ? 2 : 1;
     std::vector<pm_match> knn(static_cast<size_t>(d1.rows) * k);
-    if (matcher == "flann") {
+    if (want_cross) {
+        // matcher both ways + mutual-nearest-neighbour filter, one call (cv::BFMatcher(norm, crossCheck = true).match)
+        const int cross_flags = filter == "cross-ratio" ? PM_CROSS_RATIO_FWD : 0;
+        if (d1.dtype == 0)
+            rc = pm_bf_match_cross_l2_f32(ctx, d1.f32(), d1.rows, d2.f32(), d2.rows, d1.cols, knn_flags, cross_flags, ratio,
+                                          good.data(), &n_good);
+        else
+            rc = pm_bf_match_cross_hamming_u8(ctx, d1.data.data(), d1.rows, d2.data.data(), d2.rows, d1.cols, cross_flags, ratio,
+                                              good.data(), &n_good);
+    } else if (matcher == "flann") {
         pm_flann_params fp;
         fp.trees = 4; fp.checks = 32; fp.seed = seed;               // cv::flann defaults behind main.cpp:44
         pm_flann_index* ix = nullptr;
@@ -338,7 +355,9 @@ int main(int argc, char** argv)
     t1 = clk::now();
 
     // ---- selecting strong features                                             main.cpp:48-69
-    if (want_ratio) {
+    if (want_cross) {
+        // the survivors came out of the one-call form above
+    } else if (want_ratio) {
         rc = pm_filter_ratio(knn.data(), d1.rows, k, ratio, good.data(), &n_good);
     } else {
         // OpenCV drops queries without a neighbour (empty train set): keep only matched rows
