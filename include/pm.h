@@ -153,6 +153,21 @@ int  pm_version(void);                 /* major*100 + minor */
  *          exact VALU kernel.  All routes produce bit-identical output (tests assert it). */
 /* Device pointers of the _dev form: rows are read as 16-byte vectors when dim % 4 == 0 and both base pointers are
  * 16-byte aligned (hipMalloc / torch allocations are); otherwise the call takes the exact scalar-load kernel. */
+/* Train-set size regimes (nt = train rows; every size nt >= 0 is accepted and every regime returns the same records,
+ * bit for bit — tests/test_knn_large_train_gpu.py).  The matrix routes cut the train set into at most 64 splits of whole
+ * tiles (128 rows, f32 route 64 rows), so above 131072 rows a split is ceil(tiles / 64) tiles long:
+ *   nt <= 131072        splits of at most 2048 rows; the candidate's row-group id takes 9 low mantissa bits.
+ *   nt >  131072        the id takes 10 .. 16 bits (11 at 300 001 rows, 13 at 1.2 M, 15 at 7.4 M) and the refinement window
+ *                       widens by 2^(bits - 23) (||q||^2 + 2 max ||t||^2): more candidates, more lists scanned exactly (on
+ *                       4-dimensional rows at 7.4 M nearly every list).  PM_KNN_HINT_U8 is served by
+ *                       the f16 integer route (its integer candidates leave 9 bits for the id), and pm_bf_knn_l2_u8* widen
+ *                       the bytes to float on the device and take that route too (scratch: 4 bytes per element).
+ *   nt >  7 456 412     (dim <= 128; (nt + 128) * 288 bytes pass 2 GiB) the f16 copies are staged through registers
+ *                       instead of LDS-DMA.  (PM_OPT_KNN_SEEDED = 2, an LDS-DMA-only kernel on 256-byte rows, is honoured up
+ *                       to 8 388 352 rows and ignored above.)
+ *   nt >  16 777 216    more than 16 id bits: the whole call takes the exact VALU kernel (about 1.2 s for 131 queries of
+ *                       4 floats at that size, against 0.2 s one row below).
+ * Scratch of the matrix routes: 288 bytes per train row (f16 copy, dim <= 128), kept by the context. */
 #define PM_MAX_K 16
 #define PM_KNN_FORCE_EXACT  1   /* exact VALU kernel only                                           */
 #define PM_KNN_FORCE_F32    2   /* f32-MFMA coarse route only (any finite floats)                   */
@@ -224,7 +239,12 @@ int pm_flann_export(const pm_flann_index* ix, int32_t* n_nodes, int32_t* roots, 
 /* Binary descriptors (ORB-256 = 32 bytes/row): Hamming distance, popcount of XOR.
  * `bytes` must be a multiple of 4.  Replaces main.cpp:46 for BASELINE config C4.  32-byte
  * descriptors with k <= 2 (16-byte-aligned device buffers) run on the matrix cores (+-1 expansion on
- * i8 MFMA + popcount refinement), everything else on the integer VALU scan; same output. */
+ * i8 MFMA + popcount refinement), everything else on the integer VALU scan; same output.
+ * Train-set size regimes of the matrix-core route (same records in all of them): at most 64 splits of whole 128-row tiles;
+ * above 8 388 479 rows ((nt + 128) * 256 bytes pass 2 GiB) the +-1 byte copies are staged through registers instead of
+ * LDS-DMA; from 2^23 = 8 388 608 rows on the refinement's keys are 64-bit (below: distance << 23 | row); above
+ * 33 554 432 rows a split has more than 2^16 candidate ids and the call takes the VALU scan (about 0.34 s for 67 queries at
+ * that size against 11 ms one row below).  Scratch: 256 bytes per train row, kept by the context. */
 int pm_bf_knn_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt,
                          int bytes, int k, pm_match* out);
 int pm_bf_knn_hamming_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
