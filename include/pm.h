@@ -669,7 +669,12 @@ int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_c
  * -> lowest id); inliers are the correspondences within the robust sigma derived from that median.
  * F: row-major, x2^T F x1 = 0, unit Frobenius norm, F[8] >= 0 (pm_f_scale_f33 gives OpenCV's
  * F[8] = 1).  n <= 32768.  pm_lmeds_default_iters: OpenCV's iteration count
- * round(log(1 - confidence) / log(1 - (1 - outlier_ratio)^7)) (300 for 0.99 / 0.45). */
+ * round(log(1 - confidence) / log(1 - (1 - outlier_ratio)^7)) (300 for 0.99 / 0.45).
+ * pm_lmeds_fundamental_dev: n >= 8, device pointers in and out (any output may be NULL),
+ * asynchronous on the context's stream.  It cannot report PM_E_NO_MODEL without a host round trip:
+ * when no model wins (every sample degenerate, every median +inf) or the range is empty
+ * (hyp_begin == hyp_end) it returns PM_OK and leaves F = 0, mask = 0 (all n bytes),
+ * n_inliers = 0, best_model = -1 and median = +inf on the device. */
 typedef struct pm_lmeds_params {
     int64_t  hyp_begin, hyp_end;
     uint64_t seed;

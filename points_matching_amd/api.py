@@ -805,6 +805,16 @@ class Context:
                                                 _p(R), _p(t), _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
         return rc, R.reshape(3, 3), t, mask[:n], ninl.value, key.value, info
 
+    def lmeds_fundamental_dev(self, dxy1_ptr, dxy2_ptr, n, hyp_begin, hyp_end, seed, dF_ptr, dmask_ptr, dninl_ptr,
+                              dbest_ptr, dmed_ptr):
+        """Device-resident 7-point + LMedS (SPEC S13-S15): inputs and outputs are device pointers (F 9 doubles, mask n
+        bytes, int32 count, int64 model id, double median; any output may be None).  Asynchronous on the context's
+        stream.  No winning model is not an error here: the outputs are F = 0, mask = 0, count 0, id -1, median +inf."""
+        prm = LmedsParams(hyp_begin, hyp_end, seed)
+        _check(lib().pm_lmeds_fundamental_dev(self._h, C.c_void_p(dxy1_ptr), C.c_void_p(dxy2_ptr), n, C.byref(prm),
+                                              C.c_void_p(dF_ptr), C.c_void_p(dmask_ptr), C.c_void_p(dninl_ptr),
+                                              C.c_void_p(dbest_ptr), C.c_void_p(dmed_ptr)))
+
     def gather_pnp_dev(self, dmatches_ptr, dcount_ptr, cap, dkp_ptr, n_kp, dobj_ptr, n_obj, duv_ptr, dxyz_ptr):
         """Compacted matches -> PnP rows on the device (uv = keypoint of queryIdx, xyz = map point of trainIdx)."""
         _check(lib().pm_gather_pnp_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dkp_ptr),

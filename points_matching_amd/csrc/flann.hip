@@ -123,14 +123,21 @@ struct Builder {
             for (int k = 0; k < dim; ++k) { const float d = v[k] - mean[k]; var[k] += d * d; }
         }
         const int cutfeat = select_division();
-        const float cutval = mean[cutfeat];
+        float cutval = mean[cutfeat];
         int lim1, lim2;
         plane_split(ind, count, cutfeat, cutval, lim1, lim2);
+        if (lim1 == count || lim2 == 0) {
+            // every value lies strictly on one side of the mean: equal values whose f32 mean is an ulp off them.  FLANN
+            // splits such a node in the middle and keeps the mean, which leaves points on the wrong side of the stored
+            // cut.  Cut at a value of the node instead: it is neither below nor above itself, so both sides stay
+            // non-empty and every point agrees with the cut.
+            cutval = data[static_cast<size_t>(ind[count / 2]) * dim + cutfeat];
+            plane_split(ind, count, cutfeat, cutval, lim1, lim2);
+        }
         int index;
         if (lim1 > count / 2) index = lim1;
         else if (lim2 < count / 2) index = lim2;
         else index = count / 2;
-        if (lim1 == count || lim2 == 0) index = count / 2;    // all remaining values identical: split in the middle
         const int c1 = divide(ind, index);
         const int c2 = divide(ind + index, count - index);
         FlNode& nd = (*nodes)[me];
@@ -295,12 +302,16 @@ __global__ __launch_bounds__(64 * FL_QPW) void flann_search(FlSearch s, const fl
                 if (rcount < s.k || d < worst()) {
                     float cd = d;
                     int ci = idx;
+                    // once the new point is in, the rest only shifts down: a strict compare there would leave the second
+                    // of two equal neighbours in place and move the first behind it
+                    bool placed = false;
 #pragma unroll
                     for (int i = 0; i < FL_MAX_K; ++i) {
-                        if (i < s.k && cd < rd[i]) {
+                        if (i < s.k && (placed || cd < rd[i])) {
                             const float td = rd[i]; const int ti = ri[i];
                             rd[i] = cd; ri[i] = ci;
                             cd = td; ci = ti;
+                            placed = true;
                         }
                     }
                     if (rcount < s.k) ++rcount;

@@ -7,18 +7,9 @@ import pytest
 import points_matching_amd as pm
 from points_matching_amd import synth
 from points_matching_amd.api import PM_E_NO_MODEL, PM_E_TOO_FEW, PM_OK, lmeds_default_iters, lmeds_fundamental
+from util import assert_lmeds_equal as _same
 
 pytestmark = pytest.mark.gpu
-
-
-def _same(got, want, what):
-    rc_g, F_g, mask_g, n_g, best_g, med_g = got
-    rc_w, F_w, mask_w, n_w, best_w, med_w = want
-    assert rc_g == rc_w, what
-    assert best_g == best_w, (what, best_g, best_w, med_g, med_w)
-    assert np.float64(med_g).view(np.uint64) == np.float64(med_w).view(np.uint64), (what, med_g, med_w)
-    assert n_g == n_w and (mask_g == mask_w).all(), what
-    assert (F_g.view(np.uint64) == F_w.view(np.uint64)).all(), (what, F_g, F_w)
 
 
 @pytest.mark.parametrize("n,iters,out_frac,noise", [(500, 300, 0.0, 0.0), (501, 300, 0.3, 0.5), (1000, 300, 0.3, 0.5),
