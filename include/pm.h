@@ -70,7 +70,7 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "filter_cross_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
- * "essential_solve", "ransac_e_fused", "recover_pose". */
+ * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -499,6 +499,36 @@ int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2
                                  int max_iters, double H[9], uint8_t* mask, int* n_inliers, uint64_t* best_key,
                                  pm_h_refine_info* info);
 
+/* ---- refinement of the robust fundamental matrix on its inliers (the refit every SfM front end runs after
+ * cv::findFundamentalMat, which returns the minimal-sample model) — docs/SPEC.md S43-S45.  Over the correspondences with
+ * mask[i] != 0: a Hartley-normalised least-squares 8-point refit on all of them (S44, fp64, Jacobi eigen-solve, rank 2
+ * enforced as S7 does), then Levenberg-Marquardt on the sum of squared Sampson distances (px^2) over 7 parameters that
+ * cannot leave rank 2 (S45: F = U diag(1, sigma, 0) V^T in the refit's normalised coordinates, Cayley rotation steps on U
+ * and V, a step of sigma; up to max_iters iterations, one pass over the inliers each).  LM starts from the refit or from
+ * F_in, whichever has the lower cost (ties -> the refit); its result counts only if its cost in pixels is below the
+ * start's, so cost_out <= cost_in.  The refit and LM need at least 8 inliers.  The mask is not recomputed.  Output F:
+ * x2^T F x1 = 0, unit Frobenius norm, F[8] >= 0 (S10), rank 2 by construction.  max_iters in [0, 100]; 0 = refit only.
+ * Info: pm_h_refine_info, costs in px^2; status 0 = refined, 1 = kept F_in (fewer than 8 inliers, or no refit and no LM
+ * gain; F_out = F_in bit for bit), 2 = F_in is zero (no model; F_out = 0).  One launch of one workgroup.  Graph capture:
+ * the launch keeps no per-call state, so the device form is not refused on a capturing stream; the host forms synchronise
+ * and therefore cannot be captured.
+ * Host in, host out.  mask: n bytes 0/1 (e.g. from pm_ransac_fundamental); F_out may alias F_in; info may be NULL.
+ * Statuses: PM_E_INVALID (null arrays, max_iters out of range, null ctx), n < 8 -> PM_E_TOO_FEW (F_out = F_in),
+ * F_in zero -> PM_E_NO_MODEL (status 2). */
+int pm_fundamental_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
+                          const double F_in[9], int max_iters, double F_out[9], pm_h_refine_info* info);
+/* Device form over a view (count read on the device): chains after pm_ransac_run_dev / pm_ransac_finish_parts_dev with
+ * no host round trip.  d_mask covers the view's correspondences in view order; d_F_out may equal d_F_in; d_info may be
+ * NULL.  Data outcomes (zero F, fewer than 8 inliers) are reported in *d_info only. */
+int pm_fundamental_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask, const double* d_F_in,
+                              int max_iters, double* d_F_out, pm_h_refine_info* d_info);
+/* Convenience: pm_ransac_fundamental (over a non-empty hypothesis range, by the one-launch kernel) + refinement, one
+ * synchronisation; mask/n_inliers/best_key as the RANSAC call (the RANSAC mask), F refined, info may be NULL.  Statuses
+ * as pm_ransac_fundamental, plus an empty range or max_iters outside [0, 100] -> PM_E_INVALID. */
+int pm_ransac_fundamental_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
+                                  int max_iters, double F[9], uint8_t* mask, int* n_inliers, uint64_t* best_key,
+                                  pm_h_refine_info* info);
+
 /* ---- robust 2D affine and similarity (cv::estimateAffine2D / cv::estimateAffinePartial2D with RANSAC: the
  * alignment models of document scans, aerial mosaics and video stabilisation, where the perspective part of an H is
  * noise) — docs/SPEC.md S26-S30.  One family, the model chosen by `model`:
@@ -594,6 +624,35 @@ int pm_recover_pose_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera
 int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
                      const pm_ransac_params* p, double dist, double E[9], double R[9], double t[3], uint8_t* mask,
                      int* n_inliers, int* n_good, uint64_t* best_key);
+
+/* ---- refinement of the relative pose on its inliers — docs/SPEC.md S46-S47.  Over the correspondences with
+ * mask[i] != 0 (typically the pose mask of pm_recover_pose*): Levenberg-Marquardt on the sum of squared Sampson distances
+ * of E = [t]x R on the S31-normalised points, reported in px^2 by the factor ((fx + fy) / 2)^2, over 5 parameters: a
+ * Cayley rotation step on R (no transcendental function) and a step of t in the tangent plane of the unit sphere,
+ * renormalised.  Sums in S23's fixed order, S24's Cholesky and damping; it runs only with at least 5 inliers, max_iters > 0
+ * and a t_in of finite non-zero length, and accepts only cost decreases, so cost_out <= cost_in.  The mask is not
+ * recomputed.  max_iters in [0, 100]; 0 returns the input.  Outputs: R_out, t_out (unit norm when refined) and E_out =
+ * [t_out]x R_out in S33's convention (unit Frobenius norm, sign of the largest entry; zero if that E has no finite
+ * non-zero norm), so pm_recover_pose* can re-triangulate against the refined pose.  Info: pm_h_refine_info; status 0 =
+ * refined, 1 = kept the input (R_out, t_out = R_in, t_in bit for bit), 2 = the input pose is zero (no model, E_out = 0).
+ * One launch of one workgroup; the device form keeps no per-call state.  Host in, host out: outputs may alias the inputs;
+ * E_out and info may be NULL.  Statuses: PM_E_INVALID (bad K or max_iters, null arrays, null ctx), n < 5 -> PM_E_TOO_FEW
+ * (outputs = inputs), zero input pose -> PM_E_NO_MODEL. */
+int pm_pose_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K, const uint8_t* mask,
+                   const double R_in[9], const double t_in[3], int max_iters, double R_out[9], double t_out[3],
+                   double E_out[9], pm_h_refine_info* info);
+/* Device form over a view (count read on the device): chains after pm_recover_pose_dev with no host round trip, when
+ * that call's d_R and d_t are the two ends of one array of 12 doubles.  d_Rt_in / d_Rt_out: 12 doubles (R, then t),
+ * d_Rt_out may equal d_Rt_in; d_mask covers the view's correspondences in view order; d_E_out (9 doubles) and d_info may
+ * be NULL; data outcomes are reported in *d_info only. */
+int pm_pose_refine_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K, const uint8_t* d_mask,
+                       const double* d_Rt_in, int max_iters, double* d_Rt_out, double* d_E_out, pm_h_refine_info* d_info);
+/* pm_estimate_pose, then the refinement of its pose on its pose mask, one synchronisation.  mask / n_inliers / n_good /
+ * best_key as pm_estimate_pose; R, t refined; E: the E of the refined pose (E_out above); info (may be NULL) the
+ * refinement's.  Statuses as pm_estimate_pose, plus max_iters outside [0, 100] -> PM_E_INVALID. */
+int pm_estimate_pose_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                             const pm_ransac_params* p, double dist, int max_iters, double E[9], double R[9], double t[3],
+                             uint8_t* mask, int* n_inliers, int* n_good, uint64_t* best_key, pm_h_refine_info* info);
 
 /* ---- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P: locating a new frame against 3-D points that are
  * already known, e.g. those pm_recover_pose triangulates) — docs/SPEC.md S36-S39.  Correspondence i is a world point

@@ -58,6 +58,8 @@ EXPORTS = [
     "pm_estimate_affine",
     "pm_ransac_essential", "pm_ransac_essential_from_hyp", "pm_ransac_essential_run_dev", "pm_recover_pose",
     "pm_recover_pose_dev", "pm_estimate_pose",
+    "pm_fundamental_refine", "pm_fundamental_refine_dev", "pm_ransac_fundamental_refined",
+    "pm_pose_refine", "pm_pose_refine_dev", "pm_estimate_pose_refined",
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
     "pm_solve_pnp_ransac", "pm_gather_pnp_dev",
     "pm_filter_cross", "pm_filter_cross_gather_dev",
@@ -607,6 +609,37 @@ class Context:
         return rc, H.reshape(3, 3), mask[:n], ninl.value, key.value, info
 
 
+    # -- refinement of the robust F on its inliers (8-point refit + rank-2 LM, SPEC S43-S45) ----------------------------
+    def fundamental_refine(self, xy1, xy2, mask, F_in, max_iters=10):
+        """Returns (status, F(3x3), HRefineInfo); raises on anything other than PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n:
+            raise ValueError("xy1, xy2 and mask must have the same length")
+        Fin = np.ascontiguousarray(F_in, np.float64).reshape(9)
+        F = np.zeros(9, np.float64)
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_fundamental_refine(self._h, _p(xy1), _p(xy2), n, _p(mask), _p(Fin), max_iters, _p(F),
+                                                  C.byref(info)))
+        return rc, F.reshape(3, 3), info
+
+    def fundamental_refine_dev(self, view, dmask_ptr, dFin_ptr, max_iters, dFout_ptr, dinfo_ptr=None):
+        """Device form over a PointsView; dinfo_ptr (32 bytes, H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_fundamental_refine_dev(self._h, C.byref(view), C.c_void_p(dmask_ptr), C.c_void_p(dFin_ptr),
+                                               max_iters, C.c_void_p(dFout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def ransac_fundamental_refined(self, xy1, xy2, iters, thresh_px, seed, max_iters=10, hyp_begin=0, kind=PM_ERR_SAMPSON):
+        """RANSAC-F + refinement, one synchronisation: (status, F(3x3), mask, n_inliers, best_key, HRefineInfo)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        F = np.zeros(9, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_ransac_fundamental_refined(self._h, _p(xy1), _p(xy2), n, C.byref(prm), max_iters, _p(F),
+                                                          _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
+        return rc, F.reshape(3, 3), mask[:n], ninl.value, key.value, info
+
     # -- robust 2D affine / similarity (cv::estimateAffine2D / estimateAffinePartial2D, SPEC S26-S30) -------------------
     # model: PM_AFFINE_FULL (6 DOF) or PM_AFFINE_PARTIAL (4 DOF).  A is returned as a 2 x 3 float64 array.
     def ransac_affine(self, xy1, xy2, iters, thresh_px, seed, model=PM_AFFINE_FULL, hyp_begin=0, kind=PM_ERR_REPROJ):
@@ -739,6 +772,44 @@ class Context:
                                              C.c_double(dist), _p(E), _p(R), _p(t), _p(mask), C.byref(ninl), C.byref(ng),
                                              C.byref(key)))
         return rc, E.reshape(3, 3), R.reshape(3, 3), t, mask[:n], ninl.value, ng.value, key.value
+
+    # -- refinement of the relative pose on its inliers (5-parameter LM on the Sampson distance, SPEC S46-S47) -----------
+    def pose_refine(self, xy1, xy2, K, mask, R_in, t_in, max_iters=20):
+        """Returns (status, R(3x3), t(3), E(3x3) of the refined pose, HRefineInfo); raises on anything other than PM_OK /
+        PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n:
+            raise ValueError("xy1, xy2 and mask must have the same length")
+        Rin = np.ascontiguousarray(R_in, np.float64).reshape(9)
+        tin = np.ascontiguousarray(t_in, np.float64).reshape(3)
+        R, t, E = np.zeros(9, np.float64), np.zeros(3, np.float64), np.zeros(9, np.float64)
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_pose_refine(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), _p(mask), _p(Rin), _p(tin),
+                                           max_iters, _p(R), _p(t), _p(E), C.byref(info)))
+        return rc, R.reshape(3, 3), t, E.reshape(3, 3), info
+
+    def pose_refine_dev(self, view, K, dmask_ptr, dRt_in_ptr, max_iters, dRt_out_ptr, dE_out_ptr=None, dinfo_ptr=None):
+        """Device form over a PointsView; Rt: 12 doubles (R, then t); dE_out_ptr (9 doubles) and dinfo_ptr (32 bytes,
+        H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_pose_refine_dev(self._h, C.byref(view), C.byref(_camera(K)), C.c_void_p(dmask_ptr),
+                                        C.c_void_p(dRt_in_ptr), max_iters, C.c_void_p(dRt_out_ptr), C.c_void_p(dE_out_ptr),
+                                        C.c_void_p(dinfo_ptr)))
+
+    def estimate_pose_refined(self, xy1, xy2, K, iters, thresh_px, seed, max_iters=20, dist=50.0, hyp_begin=0,
+                              kind=PM_ERR_SAMPSON):
+        """RANSAC-E + pose recovery + refinement, one synchronisation: (status, E of the refined pose, R, t, pose mask,
+        n_inliers, n_good, best_key, HRefineInfo)."""
+        xy1, xy2, n = _pair(xy1, xy2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh_px, kind)
+        E, R, t = np.zeros(9, np.float64), np.zeros(9, np.float64), np.zeros(3, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, ng, key = C.c_int(), C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_estimate_pose_refined(self._h, _p(xy1), _p(xy2), n, C.byref(_camera(K)), C.byref(prm),
+                                                     C.c_double(dist), max_iters, _p(E), _p(R), _p(t), _p(mask),
+                                                     C.byref(ninl), C.byref(ng), C.byref(key), C.byref(info)))
+        return rc, E.reshape(3, 3), R.reshape(3, 3), t, mask[:n], ninl.value, ng.value, key.value, info
 
     # -- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P, SPEC S36-S39) -------------------------------------
     # xyz: n x 3 world points, uv: n x 2 pixels; K as for the calibrated pose.  R is returned as 3 x 3, t as 3 float64.

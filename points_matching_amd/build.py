@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libpm_hip.so")
 SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ransac.hip", "ransac_fused.hip", "ransac_shard.hip", "filter_gather.hip",
            "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
-           "pnp_refine.hip", "estimators.cpp", "match_cross.cpp",
+           "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
@@ -35,6 +35,9 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          "ransac_p_fused.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # one 512-thread workgroup holding 28 fp64 partial sums per thread (S40)
          "pnp_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # one 512-thread workgroup each: 45 / 36 fp64 partial sums per thread (S44, S45) and 21 (S47)
+         "fundamental_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "pose_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # the compaction with its three predicates (ratio, midpoint, cross-check S41): none may use scratch
          "filter_gather.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")

@@ -1,8 +1,11 @@
-// estimators.cpp — the C-ABI entry points of the four robust model families of include/pm.h that share one call shape:
+// estimators.cpp — the C-ABI entry points of the robust model families of include/pm.h that share one call shape:
 // the homography (RANSAC-H, ransac_h_fused.hip, refined by homography_refine.hip), the affine / similarity model
 // (RANSAC-A, ransac_a_fused.hip, refitted by affine_refine.hip), the calibrated relative pose (RANSAC-E,
-// essential_solve.hip + ransac_e_fused.hip, followed by recover_pose.hip) and the absolute pose (RANSAC-PnP,
-// pnp_solve.hip + ransac_p_fused.hip, refined by pnp_refine.hip).  Those files hold the kernels and one enqueue each.
+// essential_solve.hip + ransac_e_fused.hip, followed by recover_pose.hip and, on request, pose_refine.hip) and the
+// absolute pose (RANSAC-PnP, pnp_solve.hip + ransac_p_fused.hip, refined by pnp_refine.hip); also the refinement of the
+// fundamental matrix (fundamental_refine.hip; its RANSAC is the one-launch kernel of ransac_fused.hip, whose other entry
+// points live in ransac.hip) and of a relative pose alone (pose_refine.hip).  Those files hold the kernels and one enqueue
+// each.
 // Here: one description per family (Family), every argument check once, and one driver per call shape — run_host for
 // the host-pointer forms (upload, RANSAC and / or the second step on one stream, one readback into pinned memory, one
 // synchronisation), run_dev / refine_dev for the device forms.  The families differ in data and in which launch is
@@ -15,11 +18,11 @@
 namespace pm_ransac {
 namespace {
 
-enum Id { H, A, E, P };
+enum Id { H, A, E, P, F, R };       // R: a relative pose (R, t) to refine, no RANSAC of its own
 
 // One model family.  A sample yields `ids` candidate models (model ids ids * h + j); the minimal solvers of E and P write
 // them `stride` doubles apart with a non-zero flag at offset `flag`.  The second step is LM with max_iters (H, P), the
-// closed-form refit (A) or pose recovery with dist (E).
+// closed-form refit (A) or pose recovery with dist (E), which a third step may follow: LM on the recovered pose.
 struct Family {
     Id id;
     const char* name;           // in messages
@@ -32,9 +35,11 @@ struct Family {
     const char* null_model;     // messages of the null checks
     const char* null_cands;
     int model;                  // A: PM_AFFINE_FULL | PM_AFFINE_PARTIAL
-    int max_iters;              // H, P
+    int max_iters;              // H, P, F, R; E: of the third step
     double dist;                // E
-    bool camera() const { return id == E || id == P; }
+    bool third;                 // E: refine the recovered pose
+    bool lm() const { return id == H || id == P || id == F || id == R || third; }
+    bool camera() const { return id == E || id == P || id == R; }
     bool pose() const { return id == E; }       // the second step maps the model to (R, t, mask, points), not to a model
 };
 
@@ -48,9 +53,17 @@ Family affine(int model)
     const int k = model == PM_AFFINE_FULL ? Traits<FULL>::MIN_PTS : Traits<PARTIAL>::MIN_PTS;
     return Family{A, "A", 6, k, 2, 1, 0, 0, PM_ERR_REPROJ, "hypotheses", "null A", nullptr, model, 0, 0.0};
 }
-Family essential(double dist)
+Family essential(double dist, bool third = false, int max_iters = 0)
 {
-    return Family{E, "E", 9, 5, 2, 10, 10, 9, PM_ERR_SAMPSON, "samples", "null E", "null E or counts", 0, 0, dist};
+    return Family{E, "E", 9, 5, 2, 10, 10, 9, PM_ERR_SAMPSON, "samples", "null E", "null E or counts", 0, max_iters, dist, third};
+}
+Family fundamental(int max_iters)
+{
+    return Family{F, "F", 9, 8, 2, 1, 0, 0, PM_ERR_SAMPSON, "hypotheses", "null F", nullptr, 0, max_iters, 0.0};
+}
+Family relpose(int max_iters)
+{
+    return Family{R, "pose", 12, 5, 2, 1, 0, 0, PM_ERR_SAMPSON, "samples", "null R or t", nullptr, 0, max_iters, 0.0};
 }
 Family pnp(int max_iters)
 {
@@ -99,8 +112,12 @@ int check_args(const Family& f, int steps, const pm_ransac_params* p, const pm_c
         PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
         const int rc = check_range(p, f.ids);
         if (rc != PM_OK) return rc;
-        PM_REQUIRE(p->error_kind == f.error_kind, PM_E_INVALID,
-                   f.error_kind == PM_ERR_SAMPSON ? "error_kind must be PM_ERR_SAMPSON" : "error_kind must be PM_ERR_REPROJ");
+        if (f.id == F)
+            PM_REQUIRE(p->error_kind == PM_ERR_SAMPSON || p->error_kind == PM_ERR_SYM_EPIPOLAR, PM_E_INVALID,
+                       "unknown error_kind");
+        else
+            PM_REQUIRE(p->error_kind == f.error_kind, PM_E_INVALID,
+                       f.error_kind == PM_ERR_SAMPSON ? "error_kind must be PM_ERR_SAMPSON" : "error_kind must be PM_ERR_REPROJ");
         if (f.id == P)
             PM_REQUIRE(p->thresh_px > 0.0f && std::isfinite(p->thresh_px), PM_E_INVALID, "thresh_px must be finite and > 0");
     }
@@ -114,7 +131,7 @@ int check_args(const Family& f, int steps, const pm_ransac_params* p, const pm_c
         PM_REQUIRE(*thr > 0.0f && std::isfinite(*thr), PM_E_INVALID, "the normalised threshold must be finite and > 0");
     }
     if (!ransac) PM_REQUIRE(model_in != nullptr, PM_E_INVALID, f.null_model);
-    if ((steps & SECOND) && (f.id == H || f.id == P))
+    if ((steps & SECOND) && f.lm())
         PM_REQUIRE(f.max_iters >= 0 && f.max_iters <= 100, PM_E_INVALID, "max_iters must lie in [0, 100]");
     if ((steps & SECOND) && f.id == E) PM_REQUIRE(f.dist > 0.0, PM_E_INVALID, "dist must be > 0");
     return PM_OK;
@@ -153,6 +170,8 @@ int enqueue_solve(pm_ctx* ctx, const Family& f, const pm_points_view& v, const p
     switch (f.id) {
     case H:
     case A:
+    case F:
+    case R:
         return PM_OK;
     case E: {
         const long long cap_total = static_cast<long long>(v.parts) * v.cap;
@@ -180,6 +199,8 @@ int enqueue_score(pm_ctx* ctx, const Family& f, const pm_points_view& vs, const 
     case A: return ransac_a_enqueue(ctx, f.model, vs, q, d_key, d_model, d_mask, mask_len, d_ninl);
     case E: return ransac_e_enqueue(ctx, vs, q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
     case P: return ransac_p_enqueue(ctx, vs, q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
+    case F: return fused_launch(ctx, vs, q, 0, nullptr, d_key, d_model, d_mask, mask_len, d_ninl, nullptr);
+    case R: break;
     }
     return PM_E_INVALID;
 }
@@ -196,14 +217,17 @@ int enqueue_ransac(pm_ctx* ctx, const Family& f, const pm_points_view& v, const 
     return enqueue_score(ctx, f, vs, &q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
 }
 
-// The second step of the families where it maps a model to a model (pose recovery: recover_pose_enqueue)
+// The second step of the families where it maps a model to a model (pose recovery: recover_pose_enqueue).  d_E: R only,
+// the E of the refined pose (may be null)
 int enqueue_refine(pm_ctx* ctx, const Family& f, const pm_points_view& v, const pm_camera* K, const uint8_t* d_mask,
-                   const double* d_in, double* d_out, pm_h_refine_info* d_info)
+                   const double* d_in, double* d_out, pm_h_refine_info* d_info, double* d_E = nullptr)
 {
     switch (f.id) {
     case H: return homography_refine_enqueue(ctx, v, d_mask, d_in, f.max_iters, d_out, d_info);
     case A: return affine_refine_enqueue(ctx, f.model, v, d_mask, d_in, d_out, d_info);
     case P: return pnp_refine_enqueue(ctx, v, *K, d_mask, d_in, f.max_iters, d_out, d_info);
+    case F: return fundamental_refine_enqueue(ctx, v, d_mask, d_in, f.max_iters, d_out, d_info);
+    case R: return pose_refine_enqueue(ctx, v, *K, d_mask, d_in, f.max_iters, d_out, d_E, d_info);
     case E: break;
     }
     return PM_E_INVALID;
@@ -212,6 +236,7 @@ int enqueue_refine(pm_ctx* ctx, const Family& f, const pm_points_view& v, const 
 // The small results of a host-pointer call: one block on the device and its mirror in pinned memory (mask and points4
 // follow the pinned one), read back as a whole, so each family's block holds what that family writes and no more:
 //   key, count, n_good | info (E: R, t of the pose) | model | E, P: the candidates' keys, the candidates of the sample
+//   | R, and E with a third step: the E of the refined pose | E with a third step: its info
 struct Results {
     unsigned long long* key;
     int32_t *count, *n_good;
@@ -220,13 +245,16 @@ struct Results {
     double* model;
     unsigned long long* keys;
     double* cand;
+    double* E_ref;
+    pm_h_refine_info* info3;
 };
 
-// H 120, A 96, E 1064, P 816
+// H 120, A 96, E 1064 (1168 with a third step), P 816, F 120, R 216
 size_t results_bytes(const Family& f)
 {
     const size_t second = f.pose() ? sizeof(double) * 12 : sizeof(pm_h_refine_info);
-    return 16 + second + sizeof(double) * f.words + (f.ids > 1 ? sizeof(double) * f.ids * (1 + f.stride) : 0);
+    return 16 + second + sizeof(double) * f.words + (f.ids > 1 ? sizeof(double) * f.ids * (1 + f.stride) : 0) +
+           (f.id == R || f.third ? sizeof(double) * 9 : 0) + (f.third ? sizeof(pm_h_refine_info) : 0);
 }
 
 Results results_at(const Family& f, void* base)
@@ -240,6 +268,8 @@ Results results_at(const Family& f, void* base)
     r.model = f.pose() ? r.pose + 12 : reinterpret_cast<double*>(r.info + 1);
     r.keys = reinterpret_cast<unsigned long long*>(r.model + f.words);
     r.cand = reinterpret_cast<double*>(r.keys + f.ids);
+    r.E_ref = f.ids > 1 ? r.cand + f.ids * f.stride : r.model + f.words;
+    r.info3 = reinterpret_cast<pm_h_refine_info*>(r.E_ref + 9);
     return r;
 }
 
@@ -277,6 +307,7 @@ struct HostOut {
     double* cands;              // CANDIDATES: ids * words
     int32_t* counts;            // CANDIDATES: ids
     int* n_models;
+    double* E_ref;              // R: the E of the refined pose
 };
 
 void put_model(const Family& f, const HostOut& out, const double* src)
@@ -302,6 +333,7 @@ void reset_outputs(const Family& f, bool ransac, int n, const double* in, const 
     if (out.cands) memset(out.cands, 0, sizeof(double) * f.ids * f.words);
     if (out.counts) for (int j = 0; j < f.ids; ++j) out.counts[j] = -1;
     if (out.n_models) *out.n_models = 0;
+    if (out.E_ref) memset(out.E_ref, 0, sizeof(double) * 9);
 }
 
 // Driver of every host-pointer form: n correspondences a1 (dim1 floats each), a2 (2 floats each).  RANSAC over p's
@@ -363,7 +395,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     if (!ransac) {
         memcpy(hres.model, in, model_bytes);
         // H and A send the mask before the model, E and P after it
-        const bool mask_first = f.id == H || f.id == A;
+        const bool mask_first = f.id == H || f.id == A || f.id == F;
         if (mask_first) PM_HIP_CHECK(hipMemcpyAsync(dmask, mask_in, mask_bytes, hipMemcpyHostToDevice, ctx->stream));
         PM_HIP_CHECK(hipMemcpyAsync(dres.model, hres.model, model_bytes, hipMemcpyHostToDevice, ctx->stream));
         if (!mask_first && mask_in)
@@ -375,11 +407,14 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     else if (ransac)
         rc = enqueue_ransac(ctx, f, v, K, p, thr, dres.key, dres.model, dmask, n, dres.count);
     if (rc != PM_OK) return rc;
-    if (second && f.pose())
+    if (second && f.pose()) {
         rc = recover_pose_enqueue(ctx, v, *K, dres.model, (ransac || mask_in) ? dmask : nullptr, f.dist, dres.pose,
                                   dres.pose + 9, dmask, n, dres.n_good, dpts);
-    else if (second)
-        rc = enqueue_refine(ctx, f, v, K, dmask, dres.model, dres.model, dres.info);
+        if (rc == PM_OK && f.third)      // on the pose mask, in place
+            rc = pose_refine_enqueue(ctx, v, *K, dmask, dres.pose, f.max_iters, dres.pose, dres.E_ref, dres.info3);
+    } else if (second) {
+        rc = enqueue_refine(ctx, f, v, K, dmask, dres.model, dres.model, dres.info, f.id == R ? dres.E_ref : nullptr);
+    }
     if (rc != PM_OK) return rc;
     PM_HIP_CHECK(hipMemcpyAsync(hres.key, dres.key, res_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (!refit_alone) PM_HIP_CHECK(hipMemcpyAsync(hmask, dmask, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -404,7 +439,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     if (ransac) {
         if (out.best_key) *out.best_key = *hres.key;
         if (out.info)
-            *out.info = second ? *hres.info : pm_h_refine_info{0.0, 0.0, 0, 0, *hres.key ? 1 : 2, 0};
+            *out.info = second ? *(f.third ? hres.info3 : hres.info) : pm_h_refine_info{0.0, 0.0, 0, 0, *hres.key ? 1 : 2, 0};
         if (*hres.key == 0ull) {
             pm::set_error("no valid model (all %s degenerate)", f.unit);
             return PM_E_NO_MODEL;
@@ -414,6 +449,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     } else if (refit_alone) {
         put_model(f, out, hres.model);
         if (out.info) *out.info = *hres.info;
+        if (out.E_ref) memcpy(out.E_ref, hres.E_ref, sizeof(double) * 9);
         if (hres.info->status == 2) {
             pm::set_error("the input %s is zero (no model)", f.name);
             return PM_E_NO_MODEL;
@@ -427,6 +463,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
         }
         if (out.R) memcpy(out.R, hres.pose, sizeof(double) * 9);
         if (out.t) memcpy(out.t, t, sizeof(double) * 3);
+        if (f.third && out.model) memcpy(out.model, hres.E_ref, sizeof(double) * 9);      // the E of the refined pose
         if (out.n_good) *out.n_good = *hres.n_good;
         if (out.points4) memcpy(out.points4, hpts, pts);
     }
@@ -674,6 +711,57 @@ extern "C" int pm_estimate_pose(pm_ctx* ctx, const float* xy1, const float* xy2,
 {
     return run_host(ctx, essential(dist), RANSAC | SECOND, xy1, xy2, n, K, p, nullptr, nullptr, nullptr,
                     HostOut{E, mask, n_inliers, best_key, nullptr, nullptr, R, t, n_good});
+}
+
+extern "C" int pm_estimate_pose_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K,
+                                        const pm_ransac_params* p, double dist, int max_iters, double E[9], double R[9],
+                                        double t[3], uint8_t* mask, int* n_inliers, int* n_good, uint64_t* best_key,
+                                        pm_h_refine_info* info)
+{
+    return run_host(ctx, essential(dist, true, max_iters), RANSAC | SECOND, xy1, xy2, n, K, p, nullptr, nullptr, nullptr,
+                    HostOut{E, mask, n_inliers, best_key, info, nullptr, R, t, n_good});
+}
+
+extern "C" int pm_pose_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K, const uint8_t* mask,
+                              const double R_in[9], const double t_in[3], int max_iters, double R_out[9], double t_out[3],
+                              double E_out[9], pm_h_refine_info* info)
+{
+    HostOut o{R_out, nullptr, nullptr, nullptr, info, t_out};
+    o.E_ref = E_out;
+    return run_host(ctx, relpose(max_iters), SECOND, xy1, xy2, n, K, nullptr, mask, R_in, t_in, o);
+}
+
+extern "C" int pm_pose_refine_dev(pm_ctx* ctx, const pm_points_view* view, const pm_camera* K, const uint8_t* d_mask,
+                                  const double* d_Rt_in, int max_iters, double* d_Rt_out, double* d_E_out,
+                                  pm_h_refine_info* d_info)
+{
+    const Family f = relpose(max_iters);
+    pm_points_view v{};
+    const int rc = second_dev(ctx, f, DevView{view, nullptr}, K, d_mask && d_Rt_in && d_Rt_out, d_Rt_in, &v);
+    if (rc != PM_OK) return rc;
+    return enqueue_refine(ctx, f, v, K, d_mask, d_Rt_in, d_Rt_out, d_info, d_E_out);
+}
+
+// ---- fundamental matrix: refinement (RANSAC-F itself: ransac.hip)
+extern "C" int pm_fundamental_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
+                                     const double F_in[9], int max_iters, double F_out[9], pm_h_refine_info* info)
+{
+    return run_host(ctx, fundamental(max_iters), SECOND, xy1, xy2, n, nullptr, nullptr, mask, F_in, nullptr,
+                    HostOut{F_out, nullptr, nullptr, nullptr, info});
+}
+
+extern "C" int pm_fundamental_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask,
+                                         const double* d_F_in, int max_iters, double* d_F_out, pm_h_refine_info* d_info)
+{
+    return refine_dev(ctx, fundamental(max_iters), DevView{view, nullptr}, nullptr, d_mask, d_F_in, d_F_out, d_info);
+}
+
+extern "C" int pm_ransac_fundamental_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
+                                             const pm_ransac_params* p, int max_iters, double F[9], uint8_t* mask,
+                                             int* n_inliers, uint64_t* best_key, pm_h_refine_info* info)
+{
+    return run_host(ctx, fundamental(max_iters), RANSAC | SECOND, xy1, xy2, n, nullptr, p, nullptr, nullptr, nullptr,
+                    HostOut{F, mask, n_inliers, best_key, info});
 }
 
 // ---- absolute pose

@@ -49,6 +49,13 @@ int recover_pose_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& 
                          double dist, double* d_R, double* d_t, uint8_t* d_mask_out, int mask_len, int* d_n_good,
                          float* d_points4);
 
+// Refinement of the fundamental matrix (S43-S45) and of a relative pose (S46-S47) on their inliers: one workgroup each
+// over the raw view; d_E_out (the E of the refined pose) may be null.
+int fundamental_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const uint8_t* d_mask, const double* d_F_in,
+                               int max_iters, double* d_F_out, pm_h_refine_info* d_info);
+int pose_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K, const uint8_t* d_mask,
+                        const double* d_Rt_in, int max_iters, double* d_Rt_out, double* d_E_out, pm_h_refine_info* d_info);
+
 // Absolute pose.  pnp_solve_enqueue solves samples [hyp_begin, hyp_end) of p into d_cand (80 doubles per sample) from the
 // one-part view v (xy1 = world points, 3 floats each; xy2 = pixels); ransac_p_enqueue scores model ids [q->hyp_begin,
 // q->hyp_end) (4 per sample, d_cand at the first) over the same view (carves its slots like ransac_h_enqueue).
