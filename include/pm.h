@@ -208,7 +208,11 @@ int pm_bf_knn_l2_u8_ratio_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uin
  * is 1.6-2.9 us shorter and is taken; PM_OPT_FILTER_FUSION pins either form.
  * Graph capture: the matcher and the compaction calls (pm_bf_knn_l2_*, pm_filter_*_gather_dev) pass a per-call epoch
  * as a kernel argument and therefore return PM_E_UNSUPPORTED on a stream that is capturing (a replay would reuse the
- * epoch); enqueue them directly — a replay measured slower than direct launches anyway. */
+ * epoch); enqueue them directly — a replay measured slower than direct launches anyway.
+ * Limit: the two-launch form ends in pm_filter_ratio_gather_dev and inherits its limit of 1 048 576 query rows per call
+ * (PM_E_UNSUPPORTED above it, after the matcher has run); so do shapes that take the exact kernel.  The fused form on
+ * the MFMA routes has no such limit: its per-context count words grow with nq (one stream synchronisation and a
+ * reallocation when a call needs more than 4096 tiles of 32 queries, 16 on the u8 route, for the first time). */
 int pm_bf_knn_l2_ratio_dev(pm_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt, int dim, int flags,
                            float ratio, const float* d_kp1_xy, const float* d_kp2_xy, pm_match* d_knn,
                            pm_match* d_good, float* d_xy1, float* d_xy2, int32_t* d_n_good);
@@ -264,13 +268,16 @@ int pm_filter_ratio(const pm_match* knn, int nq, int k, float ratio, pm_match* o
 /* Device-resident fusion of pm_filter_ratio + pm_match_indices + pm_gather_points (main.cpp:49-69,
  * :77-78, :89-91) for batches that stay in HBM between the matcher and RANSAC: stable compaction
  * in query order.  d_good: nq records; d_xy1/d_xy2: nq x 2 floats (may be NULL together with the
- * keypoint arrays when only the match list is wanted); *d_n_good: survivor count (device int). */
+ * keypoint arrays when only the match list is wanted); *d_n_good: survivor count (device int).
+ * Limit: at most 1 048 576 query rows per call (4096 blocks of 256 rows share one set of per-context count words);
+ * more returns PM_E_UNSUPPORTED before anything is enqueued and leaves the outputs and the context as they were. */
 int pm_filter_ratio_gather_dev(pm_ctx* ctx, const pm_match* d_knn, int nq, int k, float ratio,
                                const float* d_kp1_xy, const float* d_kp2_xy, pm_match* d_good,
                                float* d_xy1, float* d_xy2, int32_t* d_n_good);
 /* The reference's own strong-match rule (main.cpp:49-69, what pm_filter_midpoint does on the host)
  * in the same device-resident form: record i of d_m is d_m[i*k] (k = 1 for a 1-NN match list);
- * d_minmax (may be NULL) receives minMatch / maxMatch as two doubles (main.cpp:58-59). */
+ * d_minmax (may be NULL) receives minMatch / maxMatch as two doubles (main.cpp:58-59).
+ * Limit: n <= 1 048 576 rows per call, as for pm_filter_ratio_gather_dev (PM_E_UNSUPPORTED above it). */
 int pm_filter_midpoint_gather_dev(pm_ctx* ctx, const pm_match* d_m, int n, int k,
                                   const float* d_kp1_xy, const float* d_kp2_xy, pm_match* d_good,
                                   float* d_xy1, float* d_xy2, int32_t* d_n_good, double* d_minmax);
@@ -291,7 +298,9 @@ int pm_filter_cross(const pm_match* fwd, int nq, int kf, const pm_match* rev, in
  * predicate of the pm_filter_ratio_gather_dev kernel; a trainIdx outside [0, nt) is a drop, never an address).  Output
  * contract of pm_filter_ratio_gather_dev: d_good nq records, d_xy1 / d_xy2 nq x 2 floats (NULL together with the
  * keypoint arrays), *d_n_good the survivor count.  d_xy1 row = d_kp1_xy[i], d_xy2 row = d_kp2_xy[j].  Timed as
- * "filter_cross_gather".  Refused on a capturing stream like the other compaction calls. */
+ * "filter_cross_gather".  Refused on a capturing stream like the other compaction calls.
+ * Limit: nq <= 1 048 576 rows per call, as for pm_filter_ratio_gather_dev (PM_E_UNSUPPORTED above it; nt is not
+ * limited). */
 int pm_filter_cross_gather_dev(pm_ctx* ctx, const pm_match* d_fwd, int nq, int kf, const pm_match* d_rev, int nt, int kr,
                                int cross_flags, float ratio, const float* d_kp1_xy, const float* d_kp2_xy,
                                pm_match* d_good, float* d_xy1, float* d_xy2, int32_t* d_n_good);
@@ -326,7 +335,8 @@ int pm_bf_match_cross_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const ui
 
 /* Multi-GPU glue: concatenates `parts` padded blocks of `stride` points (d_counts[p] valid in
  * block p), e.g. the all-gathered per-rank survivors of a query-row-sharded matcher, into one
- * contiguous correspondence array in part order; *d_n_total = sum of counts. */
+ * contiguous correspondence array in part order; *d_n_total = sum of counts.  A count below 0 is read as 0 and a
+ * count above `stride` as `stride`.  1 <= parts <= 65535 and stride >= 1, else PM_E_INVALID. */
 int pm_concat_points_dev(pm_ctx* ctx, const float* d_xy1_parts, const float* d_xy2_parts,
                          const int32_t* d_counts, int parts, int stride, float* d_xy1,
                          float* d_xy2, int32_t* d_n_total);
