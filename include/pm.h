@@ -333,6 +333,69 @@ int pm_bf_match_cross_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t
 int pm_bf_match_cross_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int bytes,
                                  int cross_flags, float ratio, pm_match* out, int* n_out);
 
+/* ---- guided matching: k-NN restricted by a two-view model (docs/SPEC.md S48-S50) ------------------------------------
+ * The step after the first model estimate (COLMAP's guided matching, ORB-SLAM's search along the epipolar line, the
+ * `mask` argument of cv::BFMatcher::knnMatch): query row i, keypoint d_kp1_xy[i], is matched against the train rows j
+ * whose keypoint d_kp2_xy[j] agrees with the model only — the fp32 inlier test of the RANSAC scorers (S8 / S21) on the
+ * pair (kp1[i], kp2[j]) with threshold tau (pixels) — and the nq x nt mask is never built.  One launch, timed as
+ * "knn_guided"; the matrix cores are not used.
+ *   kind   PM_GUIDE_F_SAMPSON / PM_GUIDE_F_SYM: M is a fundamental matrix, test of PM_ERR_SAMPSON / PM_ERR_SYM_EPIPOLAR;
+ *          PM_GUIDE_H: M is a homography taking image 1 to image 2, test of PM_ERR_REPROJ.  An essential matrix is
+ *          used as F = K^-T E K^-1; there is no affine gate.
+ *   d_M    DEVICE pointer to 9 doubles, row-major, rounded once to float: the d_F of pm_ransac_run_dev /
+ *          pm_fundamental_refine_dev or the d_H of pm_ransac_homography_run_dev / pm_homography_refine_dev, on the same
+ *          stream with no synchronisation in between.  A model with a non-finite entry or with nine zeros (what the
+ *          *_run_dev calls leave behind when they find no model) admits nothing.
+ *   d_out  nq x k records, 1 <= k <= 4: the k nearest ADMITTED rows in the order of the plain matchers (distance, then
+ *          lower trainIdx); rows with fewer than k admitted train rows end in trainIdx = -1, distance = +inf.
+ *          Distances are those of pm_bf_knn_l2_f32 / pm_bf_knn_l2_u8 / pm_bf_knn_hamming_u8, bit for bit (a NaN distance
+ *          is reported as the quiet NaN 0x7FC00000).
+ *   d_n_admitted  (may be NULL) nq int32: the number of train rows the gate admitted for each query.
+ * Keypoint arrays and d_M are 8-byte aligned, float and binary descriptor buffers 4-byte aligned; `bytes` is a multiple
+ * of 4.  A descriptor row the gate did not admit is never read.  PM_E_INVALID: null pointers, k outside [1, 4], unknown
+ * kind, dim < 1, bytes % 4 != 0.  nq == 0: PM_OK, nothing written.  nt == 0: every row is -1 / +inf, d_n_admitted 0.
+ * These calls carry no per-call epoch and may be captured into a graph. */
+enum { PM_GUIDE_F_SAMPSON = 0, PM_GUIDE_F_SYM = 1, PM_GUIDE_H = 2 };
+int pm_bf_knn_guided_l2_f32_dev(pm_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt, int dim,
+                                const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau, int k,
+                                pm_match* d_out, int32_t* d_n_admitted);
+int pm_bf_knn_guided_l2_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim,
+                               const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau, int k,
+                               pm_match* d_out, int32_t* d_n_admitted);
+int pm_bf_knn_guided_hamming_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytes,
+                                    const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau,
+                                    int k, pm_match* d_out, int32_t* d_n_admitted);
+/* One-call guided matching (S50): guided 2-NN into d_knn (nq x 2 records, required), then pm_filter_ratio_gather_dev on
+ * it — the outputs of those two calls, bit for bit, with the output contract of pm_bf_knn_l2_ratio_dev: d_good nq
+ * records, d_xy1 / d_xy2 nq x 2 floats (NULL together when only the match list is wanted), *d_n_good the survivor
+ * count; they feed a pm_points_view {d_xy1, d_xy2, counts = d_n_good}.  A query with a SINGLE admitted train row has no
+ * second neighbour and is dropped by the ratio test like any row without one; callers who want such matches take the
+ * k = 1 list of pm_bf_knn_guided_*_dev.  The compaction carries a per-call epoch: on a capturing stream these calls
+ * return PM_E_UNSUPPORTED before anything is enqueued, and so they do for nq > 1 048 576 (the compaction's limit). */
+int pm_bf_match_guided_l2_f32_dev(pm_ctx* ctx, const float* d_q, int nq, const float* d_t, int nt, int dim,
+                                  const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau,
+                                  float ratio, pm_match* d_knn, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                  int32_t* d_n_good);
+int pm_bf_match_guided_l2_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim,
+                                 const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau,
+                                 float ratio, pm_match* d_knn, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                 int32_t* d_n_good);
+int pm_bf_match_guided_hamming_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int bytes,
+                                      const float* d_kp1_xy, const float* d_kp2_xy, int kind, const double* d_M, float tau,
+                                      float ratio, pm_match* d_knn, pm_match* d_good, float* d_xy1, float* d_xy2,
+                                      int32_t* d_n_good);
+/* Host conveniences (upload, run, download; block like pm_bf_knn_l2_f32): everything in host memory, M nine doubles,
+ * out nq x k records, n_admitted (may be NULL) nq int32. */
+int pm_bf_knn_guided_l2_f32(pm_ctx* ctx, const float* q, int nq, const float* t, int nt, int dim, const float* kp1_xy,
+                            const float* kp2_xy, int kind, const double M[9], float tau, int k, pm_match* out,
+                            int32_t* n_admitted);
+int pm_bf_knn_guided_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int dim, const float* kp1_xy,
+                           const float* kp2_xy, int kind, const double M[9], float tau, int k, pm_match* out,
+                           int32_t* n_admitted);
+int pm_bf_knn_guided_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int bytes,
+                                const float* kp1_xy, const float* kp2_xy, int kind, const double M[9], float tau, int k,
+                                pm_match* out, int32_t* n_admitted);
+
 /* Multi-GPU glue: concatenates `parts` padded blocks of `stride` points (d_counts[p] valid in
  * block p), e.g. the all-gathered per-rank survivors of a query-row-sharded matcher, into one
  * contiguous correspondence array in part order; *d_n_total = sum of counts.  A count below 0 is read as 0 and a

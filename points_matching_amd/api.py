@@ -22,6 +22,9 @@ PM_KNN_HINT_U8 = 8
 PM_KNN_HINT_UNIT_NORM = 16
 PM_CROSS_RATIO_FWD = 1     # cross-check (S41): + ratio test on the forward row
 PM_CROSS_RATIO_REV = 2     # ... on the reverse row
+PM_GUIDE_F_SAMPSON = 0     # guided matching (S48): gate kinds
+PM_GUIDE_F_SYM = 1
+PM_GUIDE_H = 2
 PM_ERR_SAMPSON = 0
 PM_ERR_SYM_EPIPOLAR = 1
 PM_ERR_REPROJ = 2          # robust homography and affine (pm_ransac_homography*, pm_ransac_affine*)
@@ -65,6 +68,9 @@ EXPORTS = [
     "pm_filter_cross", "pm_filter_cross_gather_dev",
     "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
     "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
+    "pm_bf_knn_guided_l2_f32_dev", "pm_bf_knn_guided_l2_u8_dev", "pm_bf_knn_guided_hamming_u8_dev",
+    "pm_bf_match_guided_l2_f32_dev", "pm_bf_match_guided_l2_u8_dev", "pm_bf_match_guided_hamming_u8_dev",
+    "pm_bf_knn_guided_l2_f32", "pm_bf_knn_guided_l2_u8", "pm_bf_knn_guided_hamming_u8",
 ]
 
 
@@ -418,6 +424,75 @@ class Context:
 
     def bf_match_cross_hamming(self, q, t, cross_flags=0, ratio=0.8):
         return self._match_cross_host(lib().pm_bf_match_cross_hamming_u8, q, t, np.uint8, cross_flags, C.c_float(ratio))
+
+    # -- guided matching (SPEC S48-S50): k-NN among the train keypoints a two-view model admits ---------------------
+    def _knn_guided_dev(self, fn, dq_ptr, nq, dt_ptr, nt, width, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, k, dout_ptr, dnadm_ptr):
+        _check(fn(self._h, C.c_void_p(dq_ptr or 0), nq, C.c_void_p(dt_ptr or 0), nt, width, C.c_void_p(dkp1_ptr or 0),
+                  C.c_void_p(dkp2_ptr or 0), kind, C.c_void_p(dM_ptr or 0), C.c_float(tau), k, C.c_void_p(dout_ptr or 0),
+                  C.c_void_p(dnadm_ptr or 0)))
+
+    def bf_knn_guided_l2_dev(self, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, k, dout_ptr,
+                             dnadm_ptr=0):
+        """dM_ptr: DEVICE pointer to 9 doubles (the d_F / d_H of the device estimators); dnadm_ptr may be 0."""
+        self._knn_guided_dev(lib().pm_bf_knn_guided_l2_f32_dev, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr,
+                             tau, k, dout_ptr, dnadm_ptr)
+
+    def bf_knn_guided_l2_u8_dev(self, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, k, dout_ptr,
+                                dnadm_ptr=0):
+        self._knn_guided_dev(lib().pm_bf_knn_guided_l2_u8_dev, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr,
+                             tau, k, dout_ptr, dnadm_ptr)
+
+    def bf_knn_guided_hamming_dev(self, dq_ptr, nq, dt_ptr, nt, nbytes, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, k, dout_ptr,
+                                  dnadm_ptr=0):
+        self._knn_guided_dev(lib().pm_bf_knn_guided_hamming_u8_dev, dq_ptr, nq, dt_ptr, nt, nbytes, dkp1_ptr, dkp2_ptr, kind,
+                             dM_ptr, tau, k, dout_ptr, dnadm_ptr)
+
+    def _match_guided_dev(self, fn, dq_ptr, nq, dt_ptr, nt, width, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, ratio, dknn_ptr,
+                          dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        _check(fn(self._h, C.c_void_p(dq_ptr or 0), nq, C.c_void_p(dt_ptr or 0), nt, width, C.c_void_p(dkp1_ptr or 0),
+                  C.c_void_p(dkp2_ptr or 0), kind, C.c_void_p(dM_ptr or 0), C.c_float(tau), C.c_float(ratio),
+                  C.c_void_p(dknn_ptr or 0), C.c_void_p(dgood_ptr or 0), C.c_void_p(dxy1_ptr or 0), C.c_void_p(dxy2_ptr or 0),
+                  C.c_void_p(dn_ptr or 0)))
+
+    def bf_match_guided_l2_dev(self, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, ratio, dknn_ptr,
+                               dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        """One-call guided matching (S50): guided 2-NN into dknn_ptr, ratio filter, compaction, gather."""
+        self._match_guided_dev(lib().pm_bf_match_guided_l2_f32_dev, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind,
+                               dM_ptr, tau, ratio, dknn_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr)
+
+    def bf_match_guided_l2_u8_dev(self, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, ratio, dknn_ptr,
+                                  dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        self._match_guided_dev(lib().pm_bf_match_guided_l2_u8_dev, dq_ptr, nq, dt_ptr, nt, dim, dkp1_ptr, dkp2_ptr, kind,
+                               dM_ptr, tau, ratio, dknn_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr)
+
+    def bf_match_guided_hamming_dev(self, dq_ptr, nq, dt_ptr, nt, nbytes, dkp1_ptr, dkp2_ptr, kind, dM_ptr, tau, ratio,
+                                    dknn_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr):
+        self._match_guided_dev(lib().pm_bf_match_guided_hamming_u8_dev, dq_ptr, nq, dt_ptr, nt, nbytes, dkp1_ptr, dkp2_ptr,
+                               kind, dM_ptr, tau, ratio, dknn_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr)
+
+    def _knn_guided_host(self, fn, q, t, dtype, kp1, kp2, kind, M, tau, k):
+        q = np.ascontiguousarray(q, dtype)
+        t = np.ascontiguousarray(t, dtype).reshape(-1, q.shape[1])
+        kp1 = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        kp2 = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        if kp1.shape[0] != q.shape[0] or kp2.shape[0] != t.shape[0]:
+            raise ValueError("one keypoint per descriptor row")
+        M = np.ascontiguousarray(M, np.float64).reshape(9)
+        out = np.zeros((q.shape[0], max(k, 1)), MATCH_DTYPE)
+        adm = np.zeros(max(q.shape[0], 1), np.int32)
+        _check(fn(self._h, _p(q), q.shape[0], _p(t), t.shape[0], q.shape[1], _p(kp1), _p(kp2), kind, _p(M), C.c_float(tau), k,
+                  _p(out), _p(adm)))
+        return out, adm[:q.shape[0]]
+
+    def bf_knn_guided_l2(self, q, t, kp1, kp2, kind, M, tau, k):
+        """Guided k-NN of float rows, host arrays (pm_bf_knn_guided_l2_f32): (records nq x k, n_admitted)."""
+        return self._knn_guided_host(lib().pm_bf_knn_guided_l2_f32, q, t, np.float32, kp1, kp2, kind, M, tau, k)
+
+    def bf_knn_guided_l2_u8(self, q, t, kp1, kp2, kind, M, tau, k):
+        return self._knn_guided_host(lib().pm_bf_knn_guided_l2_u8, q, t, np.uint8, kp1, kp2, kind, M, tau, k)
+
+    def bf_knn_guided_hamming(self, q, t, kp1, kp2, kind, M, tau, k):
+        return self._knn_guided_host(lib().pm_bf_knn_guided_hamming_u8, q, t, np.uint8, kp1, kp2, kind, M, tau, k)
 
     def filter_midpoint_gather_dev(self, dm_ptr, n, k, dkp1_ptr, dkp2_ptr, dgood_ptr, dxy1_ptr, dxy2_ptr, dn_ptr,
                                    dminmax_ptr=0):

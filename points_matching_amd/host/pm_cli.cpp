@@ -10,6 +10,7 @@
 //          [--filter midpoint|ratio|cross|cross-ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
+//          [--guided TAU]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --matcher flann: the reference's ACTIVE matcher object (`FlannBasedMatcher matcher;`, main.cpp:44): 4 randomised
@@ -21,6 +22,11 @@
 // --filter cross: mutual nearest neighbours (cv::BFMatcher crossCheck = true, docs/SPEC.md S41-S42): forward and reverse
 // matcher pass + the fused filter in one call; cross-ratio adds the ratio test (--ratio) on the forward row.  Brute-force
 // matcher on one GPU only (float and binary descriptors): with --matcher flann or --gpus / --mgpu it is a usage error.
+// --guided TAU: guided matching (docs/SPEC.md S48-S50) after F is estimated: every query is matched again among the train
+// keypoints within TAU pixels (Sampson) of its epipolar line under that F (guided 2-NN + the ratio test of --ratio, what
+// pm_bf_match_guided_*_dev computes on device buffers), and RANSAC-F (8-point, --iters, --thresh, --seed) runs again on
+// the survivors.  One more stdout line reports both match counts and both inlier counts; everything else is printed as
+// without the option, for the first pass.  Single GPU only.
 // --gpus N (> 1): matcher rows and hypothesis ids are sharded over N GPUs through pm_mgpu_match_ransac (RCCL behind
 // the C ABI); needs --filter ratio --method ransac8 (the sharded form of the path, BASELINE config C4).
 // --print-epilines / --epilines: main.cpp:127-142 — the epipolar lines of the image-1 points in image 2
@@ -163,7 +169,8 @@ int fail(const char* what, int rc)
 int main(int argc, char** argv)
 {
     std::string desc1, desc2, kp1, kp2, filter = "midpoint", fscale = "opencv", method = "7point-lmeds";
-    float ratio = 0.8f, thresh = 1.0f;
+    float ratio = 0.8f, thresh = 1.0f, guided_tau = 0.f;
+    bool guided = false;
     long iters = 10000;
     unsigned long long seed = 0x5EED;
     int device = 0, gpus = 1, canvas_w = 993, canvas_h = 660;       // canvas default: the size of img01/img02
@@ -184,6 +191,7 @@ int main(int argc, char** argv)
         else if (a == "--filter") filter = val("--filter");
         else if (a == "--ratio") ratio = strtof(val("--ratio"), nullptr);
         else if (a == "--iters") { iters = strtol(val("--iters"), nullptr, 0); iters_given = true; }
+        else if (a == "--guided") { guided_tau = strtof(val("--guided"), nullptr); guided = true; }
         else if (a == "--thresh") thresh = strtof(val("--thresh"), nullptr);
         else if (a == "--seed") seed = strtoull(val("--seed"), nullptr, 0);
         else if (a == "--f-scale") fscale = val("--f-scale");
@@ -248,7 +256,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann] [--guided tau_px] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -272,6 +280,10 @@ int main(int argc, char** argv)
         fprintf(stderr, "pm_cli: --gpus N needs --filter ratio --method ransac8\n");
         return 2;
     }
+    if (guided && (!(guided_tau > 0.f) || gpus > 1 || force_mgpu)) {
+        fprintf(stderr, "pm_cli: --guided needs a positive threshold in pixels and a single GPU (no --gpus N, --mgpu)\n");
+        return 2;
+    }
     if (gpus < 1 || canvas_w < 1 || canvas_h < 1) { fprintf(stderr, "pm_cli: bad --gpus / --canvas\n"); return 2; }
     if (matcher != "bf" && matcher != "flann") { fprintf(stderr, "pm_cli: --matcher bf|flann\n"); return 2; }
     if (matcher == "flann" && (d1.dtype != 0 || gpus > 1 || force_mgpu)) {
@@ -284,7 +296,7 @@ int main(int argc, char** argv)
     pm_mgpu* mg = nullptr;
     int rc = PM_OK, est_rc = PM_OK;
     std::vector<pm_match> good(static_cast<size_t>(d1.rows) + 1);
-    int n_good = 0, n_inl = 0;
+    int n_good = 0, n_inl = 0, n_guided = 0, n_guided_inl = 0;
     std::vector<float> xy1, xy2;
     std::vector<uint8_t> mask(static_cast<size_t>(d1.rows) + 1);
     double F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -393,6 +405,32 @@ int main(int argc, char** argv)
     }
     est_rc = rc;                             // the estimator's own status (PM_E_TOO_FEW / PM_E_NO_MODEL are results, not failures)
     t3 = clk::now();
+
+    // ---- guided matching with that F (unit scale, as estimated), then RANSAC-F on its survivors      SPEC S48-S50
+    if (guided) {
+        std::vector<pm_match> knn2(static_cast<size_t>(d1.rows) * 2), good2(static_cast<size_t>(d1.rows) + 1);
+        if (d1.dtype == 0)
+            rc = pm_bf_knn_guided_l2_f32(ctx, d1.f32(), d1.rows, d2.f32(), d2.rows, d1.cols, k1.f32(), k2.f32(), PM_GUIDE_F_SAMPSON,
+                                         F, guided_tau, 2, knn2.data(), nullptr);
+        else
+            rc = pm_bf_knn_guided_hamming_u8(ctx, d1.data.data(), d1.rows, d2.data.data(), d2.rows, d1.cols, k1.f32(), k2.f32(),
+                                             PM_GUIDE_F_SAMPSON, F, guided_tau, 2, knn2.data(), nullptr);
+        if (rc != PM_OK) return fail("guided matcher", rc);
+        rc = pm_filter_ratio(knn2.data(), d1.rows, 2, ratio, good2.data(), &n_guided);
+        if (rc != PM_OK) return fail("guided filter", rc);
+        std::vector<int32_t> qi(n_guided), ti(n_guided);
+        std::vector<float> gxy1(2 * static_cast<size_t>(n_guided) + 2), gxy2(2 * static_cast<size_t>(n_guided) + 2);
+        rc = pm_match_indices(good2.data(), n_guided, qi.data(), ti.data());
+        if (rc == PM_OK) rc = pm_gather_points(k1.f32(), k1.rows, qi.data(), n_guided, gxy1.data());
+        if (rc == PM_OK) rc = pm_gather_points(k2.f32(), k2.rows, ti.data(), n_guided, gxy2.data());
+        if (rc != PM_OK) return fail("guided gather", rc);
+        double F2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::vector<uint8_t> mask2(static_cast<size_t>(n_guided) + 1);
+        uint64_t key2 = 0;
+        rc = pm_ransac_fundamental(ctx, gxy1.data(), gxy2.data(), n_guided, &prm, F2, mask2.data(), &n_guided_inl, &key2);
+        if (rc != PM_OK && rc != PM_E_TOO_FEW && rc != PM_E_NO_MODEL) return fail("pm_ransac_fundamental (guided)", rc);
+        if (rc != PM_OK) n_guided_inl = 0;
+    }
     }
     // like cv::findFundamentalMat, a failed estimate yields the zero matrix
     if (fscale == "opencv") pm_f_scale_f33(F);
@@ -422,6 +460,9 @@ int main(int argc, char** argv)
                        ends[4 * i], ends[4 * i + 1], ends[4 * i + 2], ends[4 * i + 3]);
         if (!epi_ppm.empty() && !write_epiline_ppm(epi_ppm, gray, cols, rows_, ends, n_good)) return 1;
     }
+    if (guided)
+        printf("guided matching: tau = %g px, matches %d -> %d, inliers %d -> %d\n", guided_tau, n_good, n_guided, n_inl,
+               n_guided_inl);
     if (json) {
         auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         double mean_fwd = 0;
