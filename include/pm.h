@@ -67,7 +67,8 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * pm_ctx_timing_get: mean milliseconds and launch count of the named kernel since the last
  * pm_ctx_timing_reset (synchronises the stream).  Names: "knn_l2_prep", "knn_l2_mfma_f16",
  * "knn_l2_mfma", "knn_l2_mfma_u8", "knn_l2_mfma_f16s", "knn_l2_refine", "knn_l2_exact", "knn_hamming_expand", "knn_hamming_mfma_i8",
- * "knn_hamming_refine", "knn_hamming", "knn_hamming_merge", "filter_gather", "filter_cross_gather", "concat_points",
+ * "knn_hamming_refine", "knn_hamming512_expand", "knn_hamming512_mfma_i8", "knn_hamming512_refine", "pad_rows_u8", "knn_hamming",
+ * "knn_hamming_merge", "filter_gather", "filter_cross_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
  * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine". */
@@ -240,19 +241,37 @@ int pm_flann_knn_l2_f32_dev(pm_ctx* ctx, pm_flann_index* ix, const float* d_q, i
  * dimension | point id of a leaf, float cut value}; roots[t] = root record of tree t.  nodes may be NULL (size query). */
 int pm_flann_export(const pm_flann_index* ix, int32_t* n_nodes, int32_t* roots, void* nodes, int32_t cap_nodes);
 
-/* Binary descriptors (ORB-256 = 32 bytes/row): Hamming distance, popcount of XOR.
- * `bytes` must be a multiple of 4.  Replaces main.cpp:46 for BASELINE config C4.  32-byte
- * descriptors with k <= 2 (16-byte-aligned device buffers) run on the matrix cores (+-1 expansion on
- * i8 MFMA + popcount refinement), everything else on the integer VALU scan; same output.
+/* Binary descriptors (ORB-256 = 32 bytes/row, BRISK / FREAK / BRIEF-64 = 64): Hamming distance, popcount of XOR.
+ * `bytes` must be a positive multiple of 4 (other lengths, AKAZE's 61 bytes: pm_pad_rows_u8 below).  Replaces main.cpp:46
+ * for BASELINE config C4.  With k <= 2 two lengths run on the matrix cores (+-1 expansion on i8 MFMA + popcount
+ * refinement): 32-byte descriptors in 16-byte-aligned device buffers (256 bits, 8 k-chunks), and descriptors of 36 .. 64
+ * bytes in any 4-byte-aligned buffers (512 bits, 16 k-chunks: rows are zero-padded to 64 bytes by the expansion launch,
+ * which leaves every distance as it is — SPEC S51).  Everything else (k > 2, bytes < 32, bytes > 64, 32-byte rows in
+ * unaligned buffers) runs on the integer VALU scan; same output on every route.
  * Train-set size regimes of the matrix-core route (same records in all of them): at most 64 splits of whole 128-row tiles;
  * above 8 388 479 rows ((nt + 128) * 256 bytes pass 2 GiB) the +-1 byte copies are staged through registers instead of
  * LDS-DMA; from 2^23 = 8 388 608 rows on the refinement's keys are 64-bit (below: distance << 23 | row); above
  * 33 554 432 rows a split has more than 2^16 candidate ids and the call takes the VALU scan (about 0.34 s for 67 queries at
- * that size against 11 ms one row below).  Scratch: 256 bytes per train row, kept by the context. */
+ * that size against 11 ms one row below).  Scratch: 256 bytes per train row, kept by the context.
+ * The 512-bit route (36 .. 64 bytes) has the same structure with its own limits: scratch 512 bytes per train row (+ 64
+ * for the padded packed copy when bytes < 64 or a buffer is not 16-byte aligned); above 4 194 175 rows ((nt + 128) * 512
+ * bytes pass 2 GiB) the +-1 copies are staged through registers instead of LDS-DMA; the refinement's keys are
+ * distance << 22 | row below 2^22 = 4 194 304 rows (a distance of 512 needs the 10th bit) and 64-bit from there on; above
+ * 33 554 432 rows the call takes the VALU scan, as on the 256-bit route.  Tested (tests/test_knn_hamming_wide_gpu.py):
+ * 4 194 175, 4 194 176, 4 194 303, 4 194 304 and 4 194 400 rows, i.e. both staging forms and both key widths.  NOT tested:
+ * anything larger, in particular the fall-back to the scan above 33 554 432 rows (17 GiB of scratch).
+ * Timing names of the 512-bit route: "knn_hamming512_expand", "knn_hamming512_mfma_i8", "knn_hamming512_refine". */
 int pm_bf_knn_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt,
                          int bytes, int k, pm_match* out);
 int pm_bf_knn_hamming_u8_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt,
                              int bytes, int k, pm_match* d_out);
+
+/* Rows of any byte count for the Hamming matcher: copies n rows of `bytes` bytes into rows of dst_bytes >= bytes bytes
+ * and zeroes the tail of each.  Equal zero padding on both sides of a match leaves every Hamming distance unchanged
+ * (AKAZE's 61-byte M-LDB rows -> 64).  src may have any alignment; src and dst must not overlap.  PM_E_INVALID: a null
+ * pointer with n > 0, bytes < 1, dst_bytes < bytes.  n == 0 is PM_OK.  The _dev form is one launch ("pad_rows_u8"). */
+int pm_pad_rows_u8(const uint8_t* src, int n, int bytes, uint8_t* dst, int dst_bytes);
+int pm_pad_rows_u8_dev(pm_ctx* ctx, const uint8_t* d_src, int n, int bytes, uint8_t* d_dst, int dst_bytes);
 
 /* ---- strong-match filters (the slot of main.cpp:49-69) -------------------------------------
  * Host-side, O(n).  `out` must hold n (resp. nq) records; survivors keep query order. */

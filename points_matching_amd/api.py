@@ -71,6 +71,7 @@ EXPORTS = [
     "pm_bf_knn_guided_l2_f32_dev", "pm_bf_knn_guided_l2_u8_dev", "pm_bf_knn_guided_hamming_u8_dev",
     "pm_bf_match_guided_l2_f32_dev", "pm_bf_match_guided_l2_u8_dev", "pm_bf_match_guided_hamming_u8_dev",
     "pm_bf_knn_guided_l2_f32", "pm_bf_knn_guided_l2_u8", "pm_bf_knn_guided_hamming_u8",
+    "pm_pad_rows_u8", "pm_pad_rows_u8_dev",
 ]
 
 
@@ -233,6 +234,16 @@ def filter_cross(fwd, rev, cross_flags=0, ratio=0.8):
     n = C.c_int()
     _check(lib().pm_filter_cross(_p(fwd), nq, kf, _p(rev), nt, kr, cross_flags, C.c_float(ratio), _p(out), C.byref(n)))
     return out[:n.value].copy()
+
+
+def pad_rows_u8(rows, dst_bytes):
+    """pm_pad_rows_u8: (n, bytes) uint8 rows copied into rows of dst_bytes >= bytes bytes with a zeroed tail (AKAZE's 61
+    bytes -> 64: every Hamming distance is unchanged)."""
+    rows = np.ascontiguousarray(rows, np.uint8)
+    assert rows.ndim == 2
+    out = np.empty((rows.shape[0], int(dst_bytes)), np.uint8)
+    _check(lib().pm_pad_rows_u8(_p(rows), rows.shape[0], rows.shape[1], _p(out), int(dst_bytes)))
+    return out
 
 
 def match_indices(m):
@@ -577,6 +588,9 @@ class Context:
         _check(lib().pm_bf_knn_hamming_u8(self._h, _p(q), q.shape[0], _p(t), t.shape[0], nbytes, k,
                                           _p(out)))
         return out
+
+    def pad_rows_u8_dev(self, dsrc_ptr, n, nbytes, ddst_ptr, dst_bytes):
+        _check(lib().pm_pad_rows_u8_dev(self._h, C.c_void_p(dsrc_ptr or 0), n, nbytes, C.c_void_p(ddst_ptr or 0), dst_bytes))
 
     def bf_knn_hamming_dev(self, dq_ptr, nq, dt_ptr, nt, nbytes, k, dout_ptr):
         _check(lib().pm_bf_knn_hamming_u8_dev(self._h, C.c_void_p(dq_ptr), nq, C.c_void_p(dt_ptr),

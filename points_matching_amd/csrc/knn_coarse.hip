@@ -24,8 +24,11 @@ int launch_coarse_f16(pm_ctx* ctx, const _Float16* Qh, const _Float16* Th, int n
 }
 
 int launch_coarse_i8(pm_ctx* ctx, const void* Qe, const void* Te, int nq, int nq_pad, int nt, int splits,
-                     int tiles_per_split, int* cval, int slots)
+                     int tiles_per_split, int* cval, int slots, int bits)
 {
+    if (bits == I8W_BITS)
+        return launch_rows288<RouteI8W, AblNone>(ctx, "knn_hamming512_mfma_i8", Qe, Te, nullptr, nq, nq_pad, nt, splits,
+                                                 tiles_per_split, 0u, cval, slots, nullptr, 0u, 0);
     return launch_rows288<RouteI8, AblNone>(ctx, "knn_hamming_mfma_i8", Qe, Te, nullptr, nq, nq_pad, nt, splits, tiles_per_split, 0u,
                                    cval, slots, nullptr, 0u, 0);
 }

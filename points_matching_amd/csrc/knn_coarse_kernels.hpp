@@ -376,10 +376,17 @@ struct RouteF16T {
 typedef RouteF16T<128> RouteF16;
 static_assert(RouteF16::NCH == H_NCH && RouteF16::ROW16 == H_ROW16 && RouteF16::LDS_ROW16 == H_LDS_ROW16, "knn_shared.hpp constants");
 
-struct RouteI8 {
-    static constexpr int NCH = I8_NCH;                // 8 data chunks, no seed: pad rows are all-zero (dot = 0)
-    static constexpr int ROW16 = I8_ROW16;
-    static constexpr int LDS_ROW16 = I8_LDS_ROW16;
+// BITS: padded descriptor bits, 256 (ORB) or 512 (BRISK, FREAK, BRIEF-64; AKAZE's 486 bits zero-padded).  512: 16 k-chunks,
+// 512-byte global rows, 528-byte LDS rows (33 slots: odd, and 128 * 33 is a whole number of 1-KiB DMA pieces); the two
+// tile buffers are 135 168 B, one workgroup per CU.  |dot| <= BITS <= 512 fits above I8_SHIFT, and the most negative
+// candidate (-512 << 16) stays above I8_EMPTY.
+template <int BITS>
+struct RouteI8T {
+    static_assert(BITS == 256 || BITS == 512, "descriptor bits padded to 256 or 512");
+    static constexpr int NCH = BITS / 32;             // data chunks, no seed: pad rows are all-zero (dot = 0)
+    static constexpr int ROW16 = BITS / 16;
+    static constexpr int LDS_ROW16 = ROW16 + 1;
+    static_assert(LDS_ROW16 % 2 == 1 && (H_TT * LDS_ROW16) % 64 == 0, "conflict-free rows, whole DMA pieces");
     static constexpr int GPB = 2;                     // groups of 8 rows: the popcount refinement is cheap
     static constexpr bool MERGE = false;              // integer distances tie all the time: a 4-deep merged list would
                                                       // overflow (and force split re-scans) for most queries
@@ -418,6 +425,12 @@ struct RouteI8 {
         for (int i = 0; i < 4; ++i) cl[i] = cl[i] == I8_EMPTY ? I8_EMPTY : (cl[i] | h);
     }
 };
+// the 256-bit route keeps its own type (and with it the kernel symbols of config C4); the 512-bit one is RouteI8T<512>
+struct RouteI8 : RouteI8T<I8_BITS> {};
+static_assert(RouteI8::NCH == I8_NCH && RouteI8::ROW16 == I8_ROW16 && RouteI8::LDS_ROW16 == I8_LDS_ROW16, "knn_shared.hpp constants");
+typedef RouteI8T<I8W_BITS> RouteI8W;
+static_assert(RouteI8W::NCH == I8W_NCH && RouteI8W::ROW16 == I8W_ROW16 && RouteI8W::LDS_ROW16 == 33, "knn_shared.hpp constants");
+static_assert(sizeof(uint4) * 2 * H_TT * RouteI8W::LDS_ROW16 == 135168, "two 512-bit tile buffers: one workgroup per CU");
 
 // Seeded routes (knn_shared.hpp): the accumulators START from the per-row term, read from a per-tile seed array in LDS.
 //   RouteF16S  RouteF16 without the seed chunk: 256-byte rows = 8 k-chunks, every MFMA is algorithmic work;

@@ -18,7 +18,15 @@
 // missed if its sub-list overflowed, which the 4th entry reveals (then that sub-list's rows are
 // scanned).  Rows padding the last 128-row tile are all-zero (dot = 0): groups that contain such a
 // row do not take part in the choice of tau, but are expanded like any other candidate.
+//
+// Descriptors of 33 .. 64 bytes with k <= 2 (BRISK, FREAK, BRIEF-64; AKAZE's 61 bytes once padded to 64) take the
+// same route at 512 bits: rows are zero-padded to 64 bytes — equal zero bits on both sides add nothing to any
+// distance, and they expand to -1 * -1 = +1 per pad bit, so dot = 512 - 2*hamming holds for every length —, the coarse
+// kernel runs 16 k-chunks per block, and the refinement works on 16-word rows.  The expansion launch also writes the
+// padded packed copy the refinement reads (rows shorter than 64 bytes, or buffers that are not 16-byte aligned).
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 
 #include "knn_shared.hpp"
 
@@ -199,28 +207,50 @@ __device__ __forceinline__ uint32_t expand_nibble(uint32_t nib)
 }
 
 // one thread per (row, descriptor word): 32 bits -> 32 bytes.  Rows >= n of the padded copy are zero.
+// NW = words per expanded row (8 or 16).  PACK: the source rows have nw_src <= NW words (and any 4-byte alignment); the
+// words past nw_src are zero bits (-1 bytes on both sides), and the padded packed rows (NW words) of the real rows are
+// written to Qp / Tp for the refinement.
+template <int NW, bool PACK>
 __global__ __launch_bounds__(256) void knn_hamming_expand(const uint32_t* __restrict__ Q, int nq, int nq_pad,
-                                                          const uint32_t* __restrict__ T, int nt, int nt_pad,
-                                                          uint4* __restrict__ Qe, uint4* __restrict__ Te)
+                                                          const uint32_t* __restrict__ T, int nt, int nt_pad, int nw_src,
+                                                          uint4* __restrict__ Qe, uint4* __restrict__ Te,
+                                                          uint32_t* __restrict__ Qp, uint32_t* __restrict__ Tp)
 {
     const int gid = blockIdx.x * 256 + threadIdx.x;
-    const int total_q = nq_pad * I8_NCH;
+    const int total_q = nq_pad * NW;
     const bool is_q = gid < total_q;
     const int e = is_q ? gid : gid - total_q;
-    if (!is_q && e >= nt_pad * I8_NCH) return;
-    const int row = e / I8_NCH, c = e % I8_NCH;
+    if (!is_q && e >= nt_pad * NW) return;
+    const int row = e / NW, c = e % NW;
     const int n = is_q ? nq : nt;
     uint4 lo = uint4{0u, 0u, 0u, 0u}, hi = uint4{0u, 0u, 0u, 0u};
     if (row < n) {
-        const uint32_t w = (is_q ? Q : T)[static_cast<size_t>(row) * 8 + c];
+        uint32_t w;
+        if constexpr (PACK) {
+            w = c < nw_src ? (is_q ? Q : T)[static_cast<size_t>(row) * nw_src + c] : 0u;
+            (is_q ? Qp : Tp)[static_cast<size_t>(row) * NW + c] = w;
+        } else {
+            w = (is_q ? Q : T)[static_cast<size_t>(row) * NW + c];
+        }
         lo = uint4{expand_nibble(w & 15u), expand_nibble((w >> 4) & 15u), expand_nibble((w >> 8) & 15u),
                    expand_nibble((w >> 12) & 15u)};
         hi = uint4{expand_nibble((w >> 16) & 15u), expand_nibble((w >> 20) & 15u), expand_nibble((w >> 24) & 15u),
                    expand_nibble(w >> 28)};
     }
-    uint4* dst = (is_q ? Qe : Te) + static_cast<size_t>(row) * I8_ROW16 + 2 * c;
+    uint4* dst = (is_q ? Qe : Te) + static_cast<size_t>(row) * (2 * NW) + 2 * c;
     dst[0] = lo;
     dst[1] = hi;
+}
+
+// pm_pad_rows_u8_dev: one thread per destination byte (the source may have any alignment)
+__global__ __launch_bounds__(256) void pad_rows_u8_kernel(const uint8_t* __restrict__ src, long long total, int bytes,
+                                                          uint8_t* __restrict__ dst, int dst_bytes)
+{
+    const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= total) return;
+    const long long row = i / dst_bytes;
+    const int c = static_cast<int>(i - row * dst_bytes);
+    dst[i] = c < bytes ? src[row * bytes + c] : static_cast<uint8_t>(0);
 }
 
 using pm::wave_min_u64;
@@ -228,15 +258,20 @@ using pm::wave_min_u32;
 
 // (distance, row) keys: 32-bit (distance << 23 | row) while the train set has fewer than 2^23 rows
 // (distance <= 256), 64-bit otherwise.  Half the VALU work of the one-wave-per-query refinement is
-// key handling, so the narrow form matters.
-struct Key32 {
+// key handling, so the narrow form matters.  16-word rows reach distance 512 (a query that is the complement of a
+// train row): << 23 would wrap that to key 0, so their narrow key is distance << 22 | row, below 2^22 rows
+// (512 << 22 = 2^31: still below NONE).
+template <int SHIFT>
+struct Key32T {
     typedef uint32_t type;
     static constexpr type NONE = 0xFFFFFFFFu;
-    static __device__ __forceinline__ type make(int d, int row) { return (static_cast<uint32_t>(d) << 23) | static_cast<uint32_t>(row); }
-    static __device__ __forceinline__ int dist(type k) { return static_cast<int>(k >> 23); }
-    static __device__ __forceinline__ int row(type k) { return static_cast<int>(k & 0x7FFFFFu); }
+    static __device__ __forceinline__ type make(int d, int row) { return (static_cast<uint32_t>(d) << SHIFT) | static_cast<uint32_t>(row); }
+    static __device__ __forceinline__ int dist(type k) { return static_cast<int>(k >> SHIFT); }
+    static __device__ __forceinline__ int row(type k) { return static_cast<int>(k & ((1u << SHIFT) - 1u)); }
     static __device__ __forceinline__ type wave_min(type k) { return wave_min_u32(k); }
 };
+typedef Key32T<23> Key32;
+typedef Key32T<22> Key32W;
 struct Key64 {
     typedef unsigned long long type;
     static constexpr type NONE = ~0ull;
@@ -256,14 +291,33 @@ struct Best2 {
     }
 };
 
-__device__ __forceinline__ int hamming256(const uint4 q0, const uint4 q1, const uint32_t* __restrict__ T, int row)
+// a descriptor of NW words (8 or 16) as NW / 4 sixteen-byte vectors
+template <int NW>
+struct Desc {
+    uint4 v[NW / 4];
+    __device__ __forceinline__ void load(const uint32_t* __restrict__ P, int row)
+    {
+        const uint4* pr = reinterpret_cast<const uint4*>(P + static_cast<size_t>(row) * NW);
+#pragma unroll
+        for (int i = 0; i < NW / 4; ++i) v[i] = pr[i];
+    }
+};
+template <int NW>
+__device__ __forceinline__ int hamming_desc(const Desc<NW>& q, const Desc<NW>& t)
 {
-    const uint4* tr = reinterpret_cast<const uint4*>(T + static_cast<size_t>(row) * 8);
-    const uint4 t0 = tr[0], t1 = tr[1];
-    const int d = __builtin_popcount(q0.x ^ t0.x) + __builtin_popcount(q0.y ^ t0.y) + __builtin_popcount(q0.z ^ t0.z) +
-                  __builtin_popcount(q0.w ^ t0.w) + __builtin_popcount(q1.x ^ t1.x) + __builtin_popcount(q1.y ^ t1.y) +
-                  __builtin_popcount(q1.z ^ t1.z) + __builtin_popcount(q1.w ^ t1.w);
+    int d = 0;
+#pragma unroll
+    for (int i = 0; i < NW / 4; ++i)
+        d += __builtin_popcount(q.v[i].x ^ t.v[i].x) + __builtin_popcount(q.v[i].y ^ t.v[i].y) +
+             __builtin_popcount(q.v[i].z ^ t.v[i].z) + __builtin_popcount(q.v[i].w ^ t.v[i].w);
     return d;
+}
+template <int NW>
+__device__ __forceinline__ int hamming_row(const Desc<NW>& q, const uint32_t* __restrict__ T, int row)
+{
+    Desc<NW> t;
+    t.load(T, row);
+    return hamming_desc<NW>(q, t);
 }
 
 // All rows of one sub-list's lane stream (split, lane half hh): LANES lanes, U rows per lane and pass with the 2 x U loads
@@ -271,30 +325,26 @@ __device__ __forceinline__ int hamming256(const uint4 q0, const uint4 q1, const 
 // took one row per lane and pass, i.e. tiles_per_split serial memory round trips of ~1k cycles each — at config C4 (64
 // tiles per split) ~25 us for the handful of queries per launch that need it, which was most of the kernel's 31 us: a
 // kernel lasts as long as its slowest wave.
-template <int U, int LANES, typename K>
-__device__ __forceinline__ void scan_sublist(Best2<typename K::type>& best, const uint4 q0, const uint4 q1,
+template <int U, int LANES, int NW, typename K>
+__device__ __forceinline__ void scan_sublist(Best2<typename K::type>& best, const Desc<NW>& qd,
                                              const uint32_t* __restrict__ T, int nt, int split, int hh, int tiles_per_split, int l)
 {
     const int n = tiles_per_split * 64;
     for (int base = 0; base < n; base += LANES * U) {
         int row[U];
         bool ok[U];
-        uint4 t0[U], t1[U];
+        Desc<NW> t[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int idx = base + u * LANES + l;
             const int tile = idx >> 6, rem = idx & 63;
             row[u] = (split * tiles_per_split + tile) * H_TT + 32 * (rem >> 4) + 8 * ((rem >> 2) & 3) + 4 * hh + (rem & 3);
             ok[u] = idx < n && row[u] < nt;
-            const uint4* tr = reinterpret_cast<const uint4*>(T + static_cast<size_t>(ok[u] ? row[u] : 0) * 8);
-            t0[u] = tr[0];
-            t1[u] = tr[1];
+            t[u].load(T, ok[u] ? row[u] : 0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int d = __builtin_popcount(q0.x ^ t0[u].x) + __builtin_popcount(q0.y ^ t0[u].y) + __builtin_popcount(q0.z ^ t0[u].z) +
-                          __builtin_popcount(q0.w ^ t0[u].w) + __builtin_popcount(q1.x ^ t1[u].x) + __builtin_popcount(q1.y ^ t1[u].y) +
-                          __builtin_popcount(q1.z ^ t1[u].z) + __builtin_popcount(q1.w ^ t1[u].w);
+            const int d = hamming_desc<NW>(qd, t[u]);
             if (ok[u]) best.insert(K::make(d, row[u]));
         }
     }
@@ -305,26 +355,26 @@ __device__ __forceinline__ void scan_sublist(Best2<typename K::type>& best, cons
 // dependent passes — most of the kernel's time at config C4 although < 0.3 % of the queries need it.  Phase A of the
 // kernels only RECORDS the sub-lists (HmScan in LDS); here every thread scans its share for one owner at a time and leaves
 // its two best keys in LDS, from where the owner's lanes merge them.  NOWN owners per workgroup, LPO lanes per owner.
-template <int NOWN, int MAXSUB, typename K>
+template <int NOWN, int MAXSUB, int NW, typename K>
 struct HmScan {
-    uint4 qw[NOWN][2];                                       // the owner's descriptor (first member: 16-byte aligned)
+    Desc<NW> qw[NOWN];                                       // the owner's descriptor (first member: 16-byte aligned)
     typename K::type keys[256][2];
     int nsub[NOWN];
     int sub[NOWN][MAXSUB];
 };
-template <int NOWN, int MAXSUB, int LPO, typename K>
-__device__ __forceinline__ void wg_scan_phase(HmScan<NOWN, MAXSUB, K>& hs, Best2<typename K::type>& best, int owner, int l,
+template <int NOWN, int MAXSUB, int LPO, int NW, typename K>
+__device__ __forceinline__ void wg_scan_phase(HmScan<NOWN, MAXSUB, NW, K>& hs, Best2<typename K::type>& best, int owner, int l,
                                               const uint32_t* __restrict__ T, int nt, int tiles_per_split)
 {
     __syncthreads();                                         // every owner's record is complete
     for (int w = 0; w < NOWN; ++w) {
         const int n = hs.nsub[w];                            // workgroup-uniform
         if (n == 0) continue;
-        const uint4 q0 = hs.qw[w][0], q1 = hs.qw[w][1];
+        const Desc<NW> qd = hs.qw[w];
         Best2<typename K::type> tb{K::NONE, K::NONE};
         for (int j = 0; j < n; ++j) {
             const int sb = hs.sub[w][j];
-            scan_sublist<4, 256, K>(tb, q0, q1, T, nt, sb >> 1, sb & 1, tiles_per_split, static_cast<int>(threadIdx.x));
+            scan_sublist<4, 256, NW, K>(tb, qd, T, nt, sb >> 1, sb & 1, tiles_per_split, static_cast<int>(threadIdx.x));
         }
         hs.keys[threadIdx.x][0] = tb.a;
         hs.keys[threadIdx.x][1] = tb.b;
@@ -346,20 +396,21 @@ __device__ __forceinline__ void wg_scan_phase(HmScan<NOWN, MAXSUB, K>& hs, Best2
 constexpr int HR_MAXE = 8;          // entries per lane: slots <= 512
 // NE = entries per lane actually needed (ceil(slots / 64) rounded up to 1, 2, 4 or 8): the per-entry
 // work below is unrolled NE times, and with few splits (C4: 32 slots) NE = 1 instead of 8
-template <int NE, typename K>
+// NW = words per row of Q and T (8, or 16 on the 512-bit route: the coarse distance is then (512 - dot) / 2)
+template <int NE, int NW, typename K>
 __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __restrict__ Q, const uint32_t* __restrict__ T,
                                                           int nq, int nt, int k, const int* __restrict__ cand,
                                                           int slots, int tiles_per_split, int shift,
                                                           pm_match* __restrict__ out)
 {
     __shared__ int clist[4][64 * NE];
-    __shared__ __attribute__((aligned(16))) HmScan<4, 16 * NE, K> hs;      // (a query has slots / 4 <= 16 * NE sub-lists)
+    __shared__ __attribute__((aligned(16))) HmScan<4, 16 * NE, NW, K> hs;      // (a query has slots / 4 <= 16 * NE sub-lists)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = blockIdx.x * 4 + wave;
     const bool live = q < nq;                                // (dead waves shadow the last query: the workgroup has barriers)
     const int qc = live ? q : nq - 1;
-    const uint4* qr = reinterpret_cast<const uint4*>(Q + static_cast<size_t>(qc) * 8);
-    const uint4 q0 = qr[0], q1 = qr[1];
+    Desc<NW> qd;
+    qd.load(Q, qc);
     const int gmask = (1 << shift) - 1;
 
     int v[NE], dc[NE];
@@ -368,7 +419,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __rest
     for (int i = 0; i < NE; ++i) {
         const int e = lane + 64 * i;
         v[i] = e < slots ? cand[static_cast<size_t>(qc) * slots + e] : I8_EMPTY;
-        dc[i] = v[i] == I8_EMPTY ? 0x7FFFFFF0 : ((I8_BITS - (v[i] >> shift)) >> 1);      // coarse (= exact) distance
+        dc[i] = v[i] == I8_EMPTY ? 0x7FFFFFF0 : ((32 * NW - (v[i] >> shift)) >> 1);      // coarse (= exact) distance
         const int gid2 = v[i] & gmask, gid = gid2 >> 1, split = e >> 3;
         const int last = (split * tiles_per_split + (gid >> 3)) * H_TT + 32 * ((gid >> 1) & 3) + 16 * (gid & 1) +
                          4 * (gid2 & 1) + 11;
@@ -376,7 +427,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __rest
     }
     // tau = k-th smallest distance over the entries whose rows are all real (k distinct rows lie within
     // tau); fewer than k such entries (tiny train sets): tau = "everything"
-    // (keys: distance << 16 | entry index, distances <= 256 or the 0x7FFF sentinel, entries < 512)
+    // (keys: distance << 16 | entry index, distances <= 512 or the 0x7FFF sentinel, entries < 512)
     unsigned lastk = 0u;
     int tau = 0;
     for (int c = 0; c < k; ++c) {
@@ -413,7 +464,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __rest
         }
     }
     if (lane == 0) hs.nsub[wave] = live ? nfull : 0;
-    if (lane == 0) { hs.qw[wave][0] = q0; hs.qw[wave][1] = q1; }
+    if (lane == 0) hs.qw[wave] = qd;
     // the list entries were written by other lanes of this wave: LDS stores before the loads, explicitly
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -426,10 +477,10 @@ __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __rest
             const int s8 = t & 7;
             const int row = (split * tiles_per_split + (gid >> 3)) * H_TT + 32 * ((gid >> 1) & 3) + 16 * (gid & 1) + 4 * hh +
                             8 * (s8 >> 2) + (s8 & 3);
-            if (row < nt) best.insert(K::make(hamming256(q0, q1, T, row), row));
+            if (row < nt) best.insert(K::make(hamming_row<NW>(qd, T, row), row));
         }
     }
-    wg_scan_phase<4, 16 * NE, 64, K>(hs, best, wave, lane, T, nt, tiles_per_split);
+    wg_scan_phase<4, 16 * NE, 64, NW, K>(hs, best, wave, lane, T, nt, tiles_per_split);
     for (int c = 0; c < k; ++c) {
         const typename K::type m = K::wave_min(best.a);
         if (best.a == m && m != K::NONE) { best.a = best.b; best.b = K::NONE; }      // keys are unique rows
@@ -467,22 +518,22 @@ __device__ __forceinline__ unsigned long long row16_min_u64(unsigned long long v
 __device__ __forceinline__ unsigned row16_min(unsigned v) { return row16_min_u32(v); }
 __device__ __forceinline__ unsigned long long row16_min(unsigned long long v) { return row16_min_u64(v); }
 
-template <int NE, typename K>
+template <int NE, int NW, typename K>
 __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __restrict__ Q, const uint32_t* __restrict__ T,
                                                            int nq, int nt, int k, const int* __restrict__ cand,
                                                            int slots, int tiles_per_split, int shift,
                                                            pm_match* __restrict__ out)
 {
     __shared__ int clist[4][4][16 * NE];
-    __shared__ __attribute__((aligned(16))) HmScan<16, 4 * NE, K> hs;      // (a query has slots / 4 <= 4 * NE sub-lists)
+    __shared__ __attribute__((aligned(16))) HmScan<16, 4 * NE, NW, K> hs;      // (a query has slots / 4 <= 4 * NE sub-lists)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int qi = lane >> 4, l = lane & 15;
     const int own = wave * 4 + qi;                           // this row's query inside the workgroup
     const int q = blockIdx.x * 16 + wave * 4 + qi;
     const bool live = q < nq;
     const int qc = live ? q : nq - 1;                        // rows past the last query shadow it (DPP rows stay whole)
-    const uint4* qr = reinterpret_cast<const uint4*>(Q + static_cast<size_t>(qc) * 8);
-    const uint4 q0 = qr[0], q1 = qr[1];
+    Desc<NW> qd;
+    qd.load(Q, qc);
     const int gmask = (1 << shift) - 1;
     auto row_bits = [&](bool p) { return static_cast<unsigned>(__ballot(p) >> (16 * qi)) & 0xFFFFu; };
 
@@ -492,7 +543,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __res
     for (int i = 0; i < NE; ++i) {
         const int e = l + 16 * i;
         v[i] = e < slots ? cand[static_cast<size_t>(qc) * slots + e] : I8_EMPTY;
-        dc[i] = v[i] == I8_EMPTY ? 0x7FFFFFF0 : ((I8_BITS - (v[i] >> shift)) >> 1);
+        dc[i] = v[i] == I8_EMPTY ? 0x7FFFFFF0 : ((32 * NW - (v[i] >> shift)) >> 1);
         const int gid2 = v[i] & gmask, gid = gid2 >> 1, split = e >> 3;
         const int last = (split * tiles_per_split + (gid >> 3)) * H_TT + 32 * ((gid >> 1) & 3) + 16 * (gid & 1) +
                          4 * (gid2 & 1) + 11;
@@ -529,7 +580,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __res
         nfull += __popc(full);
     }
     if (l == 0) hs.nsub[own] = live ? nfull : 0;
-    if (l == 0) { hs.qw[own][0] = q0; hs.qw[own][1] = q1; }
+    if (l == 0) hs.qw[own] = qd;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // candidate groups: 8 rows each, one row per lane, two groups per pass and query
@@ -541,10 +592,10 @@ __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __res
             const int s8 = t & 7;
             const int row = (split * tiles_per_split + (gid >> 3)) * H_TT + 32 * ((gid >> 1) & 3) + 16 * (gid & 1) + 4 * hh +
                             8 * (s8 >> 2) + (s8 & 3);
-            if (row < nt) best.insert(K::make(hamming256(q0, q1, T, row), row));
+            if (row < nt) best.insert(K::make(hamming_row<NW>(qd, T, row), row));
         }
     }
-    wg_scan_phase<16, 4 * NE, 16, K>(hs, best, own, l, T, nt, tiles_per_split);
+    wg_scan_phase<16, 4 * NE, 16, NW, K>(hs, best, own, l, T, nt, tiles_per_split);
     for (int c = 0; c < k; ++c) {
         const typename K::type m = row16_min(best.a);
         if (best.a == m && m != K::NONE) { best.a = best.b; best.b = K::NONE; }      // keys are unique rows
@@ -559,10 +610,15 @@ __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __res
     }
 }
 
-// 256-bit descriptors, k <= 2
-int run_mfma(pm_ctx* ctx, const uint32_t* dq, int nq, const uint32_t* dt, int nt, int k, pm_match* dout, bool wide_keys,
-             bool* done)
+// k <= 2 on the matrix cores.  NW = 8: 256-bit descriptors as they are (16-byte-aligned buffers).  NW = 16: rows of
+// nw_src <= 16 words, zero-padded to 512 bits; `pack`: the expansion launch writes padded packed copies and the
+// refinement reads those (rows shorter than 64 bytes, or buffers that are only 4-byte aligned).
+template <int NW>
+int run_mfma(pm_ctx* ctx, const uint32_t* dq, int nq, const uint32_t* dt, int nt, int nw_src, bool pack, int k, pm_match* dout,
+             bool wide_keys, bool* done)
 {
+    constexpr bool W = NW == 16;
+    constexpr int ROW16 = 2 * NW;                    // 16-byte units per expanded row
     *done = false;
     const int nq_pad = (nq + H_QB - 1) / H_QB * H_QB, nt_pad = (nt + H_TT - 1) / H_TT * H_TT;
     const int nqb = nq_pad / H_QB, ntiles = nt_pad / H_TT;
@@ -575,33 +631,49 @@ int run_mfma(pm_ctx* ctx, const uint32_t* dq, int nq, const uint32_t* dt, int nt
     const int slots = splits * 2 * KNN_C;
     constexpr int shift = I8_SHIFT;
     if (tiles_per_split * (H_TT / 16) * 2 > (1 << shift)) return PM_OK; // > 64k (group, half) ids per split: VALU route
+    if ((static_cast<long long>(nq_pad) + nt_pad) * NW > 0x7FFFFFFFLL) return PM_OK;   // the expansion's thread index is an int
 
     const size_t cb = sizeof(int) * static_cast<size_t>(nq) * slots;
-    const size_t qe = sizeof(uint4) * static_cast<size_t>(nq_pad) * I8_ROW16, te = sizeof(uint4) * static_cast<size_t>(nt_pad) * I8_ROW16;
-    const size_t need = pm::align_up(cb, 256) + pm::align_up(qe, 256) + pm::align_up(te, 256) + 1024;
+    const size_t qe = sizeof(uint4) * static_cast<size_t>(nq_pad) * ROW16, te = sizeof(uint4) * static_cast<size_t>(nt_pad) * ROW16;
+    const size_t qp = pack ? sizeof(uint32_t) * static_cast<size_t>(nq) * NW : 0, tp = pack ? sizeof(uint32_t) * static_cast<size_t>(nt) * NW : 0;
+    const size_t need = pm::align_up(cb, 256) + pm::align_up(qe, 256) + pm::align_up(te, 256) + pm::align_up(qp, 256) +
+                        pm::align_up(tp, 256) + 1024;
     int rc = pm::arena_reserve(ctx, need);
     if (rc != PM_OK) return rc;
     pm::arena_reset(ctx);
     int* cval = static_cast<int*>(pm::arena_take(ctx, cb));
     uint4* Qe = static_cast<uint4*>(pm::arena_take(ctx, qe));
     uint4* Te = static_cast<uint4*>(pm::arena_take(ctx, te));
-    PM_REQUIRE(cval && Qe && Te, PM_E_NOMEM, "scratch arena too small");
+    uint32_t* Qp = pack ? static_cast<uint32_t*>(pm::arena_take(ctx, qp)) : nullptr;
+    uint32_t* Tp = pack ? static_cast<uint32_t*>(pm::arena_take(ctx, tp)) : nullptr;
+    PM_REQUIRE(cval && Qe && Te && (!pack || (Qp && Tp)), PM_E_NOMEM, "scratch arena too small");
     {
-        pm::ScopedKernelTime t(ctx, "knn_hamming_expand");
-        const int total = (nq_pad + nt_pad) * I8_NCH;
-        hipLaunchKernelGGL(knn_hamming_expand, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt,
-                           nt_pad, Qe, Te);
+        pm::ScopedKernelTime t(ctx, W ? "knn_hamming512_expand" : "knn_hamming_expand");
+        const int total = (nq_pad + nt_pad) * NW;
+        bool packed = false;
+        if constexpr (W) {
+            if (pack) {
+                hipLaunchKernelGGL((knn_hamming_expand<NW, true>), dim3((total + 255) / 256), dim3(256), 0, ctx->stream, dq, nq,
+                                   nq_pad, dt, nt, nt_pad, nw_src, Qe, Te, Qp, Tp);
+                packed = true;
+            }
+        }
+        if (!packed)
+            hipLaunchKernelGGL((knn_hamming_expand<NW, false>), dim3((total + 255) / 256), dim3(256), 0, ctx->stream, dq, nq, nq_pad,
+                               dt, nt, nt_pad, nw_src, Qe, Te, Qp, Tp);
         PM_HIP_CHECK(hipGetLastError());
     }
-    rc = launch_coarse_i8(ctx, Qe, Te, nq, nq_pad, nt, splits, tiles_per_split, cval, slots);
+    rc = launch_coarse_i8(ctx, Qe, Te, nq, nq_pad, nt, splits, tiles_per_split, cval, slots, 32 * NW);
     if (rc != PM_OK) return rc;
+    const uint32_t* rq = pack ? Qp : dq;             // what the refinement re-evaluates: rows of NW words
+    const uint32_t* rt = pack ? Tp : dt;
     {
-        pm::ScopedKernelTime t(ctx, "knn_hamming_refine");
+        pm::ScopedKernelTime t(ctx, W ? "knn_hamming512_refine" : "knn_hamming_refine");
 #define PM_HREFINE(NE_, K_)                                                                                      \
-    hipLaunchKernelGGL((knn_hamming_refine<NE_, K_>), dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, dq, dt, nq, nt, k, \
+    hipLaunchKernelGGL((knn_hamming_refine<NE_, NW, K_>), dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, rq, rt, nq, nt, k, \
                        cval, slots, tiles_per_split, shift, dout)
 #define PM_HREFINE4(NE_, K_)                                                                                      \
-    hipLaunchKernelGGL((knn_hamming_refine4<NE_, K_>), dim3((nq + 15) / 16), dim3(256), 0, ctx->stream, dq, dt, nq, nt, k, \
+    hipLaunchKernelGGL((knn_hamming_refine4<NE_, NW, K_>), dim3((nq + 15) / 16), dim3(256), 0, ctx->stream, rq, rt, nq, nt, k, \
                        cval, slots, tiles_per_split, shift, dout)
     // Four queries per wave (round 3) where a query has <= 64 candidate entries; PM_OPT_HAMMING_REFINE = 1 keeps one wave
     // per query.  Config C4, refinement kernel: 31 us (round 2) -> 27 (batched scan loads) -> 22.3 (whole-sub-list scans
@@ -618,7 +690,9 @@ int run_mfma(pm_ctx* ctx, const uint32_t* dq, int nq, const uint32_t* dt, int nt
         else if (slots <= 256) PM_HREFINE(4, K_); \
         else PM_HREFINE(HR_MAXE, K_);       \
     } while (0)
-        if (nt < (1 << 23) && !wide_keys) PM_HREFINE_K(Key32);
+        // narrow keys: distance << 23 | row below 2^23 rows (distance <= 256), distance << 22 | row below 2^22 (<= 512)
+        typedef typename std::conditional<W, Key32W, Key32>::type KeyN;
+        if (nt < (W ? (1 << 22) : (1 << 23)) && !wide_keys) PM_HREFINE_K(KeyN);
         else PM_HREFINE_K(Key64);
 #undef PM_HREFINE_K
 #undef PM_HREFINE4
@@ -649,10 +723,17 @@ extern "C" int pm_bf_knn_hamming_u8_dev(pm_ctx* ctx, const uint8_t* dq, int nq, 
     // PM_OPT_HAMMING_ROUTE (tests / A-B timing): 1 pins the VALU scan, 2 the 64-bit-key refinement of the matrix-core route
     const bool force_valu = ctx->opts[PM_OPT_HAMMING_ROUTE] == 1;
     const bool wide_keys = ctx->opts[PM_OPT_HAMMING_ROUTE] == 2;
-    if (bytes * 8 == I8_BITS && k <= 2 && nt >= 1 && !force_valu &&
-        (reinterpret_cast<uintptr_t>(dq) & 15) == 0 && (reinterpret_cast<uintptr_t>(dt) & 15) == 0) {
+    const bool aligned16 = (reinterpret_cast<uintptr_t>(dq) & 15) == 0 && (reinterpret_cast<uintptr_t>(dt) & 15) == 0;
+    if (bytes * 8 == I8_BITS && k <= 2 && nt >= 1 && !force_valu && aligned16) {
         bool done = false;
-        const int rc = run_mfma(ctx, q32, nq, t32, nt, k, dout, wide_keys, &done);
+        const int rc = run_mfma<8>(ctx, q32, nq, t32, nt, 8, false, k, dout, wide_keys, &done);
+        if (rc != PM_OK || done) return rc;
+    }
+    // 33 .. 64 bytes: the 512-bit route on rows zero-padded to 64 bytes.  (Shorter rows stay on the scan: padding
+    // them to the 256-bit route has not been measured faster.)
+    if (bytes * 8 > I8_BITS && bytes * 8 <= I8W_BITS && k <= 2 && nt >= 1 && !force_valu) {
+        bool done = false;
+        const int rc = run_mfma<16>(ctx, q32, nq, t32, nt, nw, !(nw == 16 && aligned16), k, dout, wide_keys, &done);
         if (rc != PM_OK || done) return rc;
     }
     if (k == 1) return run_passes<1>(ctx, q32, nq, t32, nt, nw, k, dout);
@@ -696,4 +777,32 @@ extern "C" int pm_bf_knn_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const
     (void)hipFree(dt);
     (void)hipFree(dout);
     return rc;
+}
+
+extern "C" int pm_pad_rows_u8(const uint8_t* src, int n, int bytes, uint8_t* dst, int dst_bytes)
+{
+    PM_REQUIRE(n >= 0 && bytes >= 1 && dst_bytes >= bytes, PM_E_INVALID, "need n >= 0, bytes >= 1, dst_bytes >= bytes");
+    PM_REQUIRE(n == 0 || (src && dst), PM_E_INVALID, "null source/destination pointer");
+    for (int r = 0; r < n; ++r) {
+        uint8_t* d = dst + static_cast<size_t>(r) * dst_bytes;
+        std::memcpy(d, src + static_cast<size_t>(r) * bytes, static_cast<size_t>(bytes));
+        std::memset(d + bytes, 0, static_cast<size_t>(dst_bytes - bytes));
+    }
+    return PM_OK;
+}
+
+extern "C" int pm_pad_rows_u8_dev(pm_ctx* ctx, const uint8_t* d_src, int n, int bytes, uint8_t* d_dst, int dst_bytes)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_REQUIRE(n >= 0 && bytes >= 1 && dst_bytes >= bytes, PM_E_INVALID, "need n >= 0, bytes >= 1, dst_bytes >= bytes");
+    PM_REQUIRE(n == 0 || (d_src && d_dst), PM_E_INVALID, "null source/destination pointer");
+    if (n == 0) return PM_OK;
+    const long long total = static_cast<long long>(n) * dst_bytes;
+    PM_REQUIRE((total + 255) / 256 <= 0x7FFFFFFFLL, PM_E_UNSUPPORTED, "more than 2^39 destination bytes");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    pm::ScopedKernelTime t(ctx, "pad_rows_u8");
+    hipLaunchKernelGGL(pad_rows_u8_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream, d_src, total,
+                       bytes, d_dst, dst_bytes);
+    PM_HIP_CHECK(hipGetLastError());
+    return PM_OK;
 }

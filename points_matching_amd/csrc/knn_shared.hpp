@@ -40,6 +40,11 @@ constexpr int I8_LDS_ROW16 = 17;        // 272-byte LDS rows: 16 rows of a lane 
 constexpr int I8_GROUP_ROWS = 8;
 constexpr int I8_SHIFT = 16;             // candidate = (dot << 16) | group id, |dot| <= 256
 constexpr int I8_EMPTY = static_cast<int>(0x80000000u);   // an unfilled list entry
+// ... and its 512-bit form (descriptors of 33 .. 64 bytes, zero-padded to 64): 512-byte rows = 16 chunks, same groups,
+// same candidate layout (|dot| <= 512)
+constexpr int I8W_BITS = 512;
+constexpr int I8W_NCH = 16;
+constexpr int I8W_ROW16 = 32;
 
 // Seeded routes (round 3): the per-row term -||t||^2/2 no longer rides a k-chunk of its own through the matrix pipe; it
 // STARTS the accumulators.  A 32-row block's 32 seeds are kept in the order of the 32x32 C/D layout ("seed order":
@@ -113,7 +118,8 @@ int launch_coarse_f16(pm_ctx* ctx, const _Float16* Qh, const _Float16* Th, int n
 
 // Enqueue the i8-MFMA coarse pass of the Hamming matcher on the expanded +-1 copies.  A candidate
 // is (dot << I8_SHIFT) | group id, dot = 256 - 2*hamming.
+// bits: 256 (timed as knn_hamming_mfma_i8) or 512 (knn_hamming512_mfma_i8, dot = 512 - 2*hamming).
 int launch_coarse_i8(pm_ctx* ctx, const void* Qe, const void* Te, int nq, int nq_pad, int nt, int splits,
-                     int tiles_per_split, int* cval, int slots);
+                     int tiles_per_split, int* cval, int slots, int bits = I8_BITS);
 
 }  // namespace pm_knn

@@ -267,6 +267,18 @@ int main(int argc, char** argv)
         return 1;
     }
     }
+    // uint8 descriptors whose column count is no multiple of 4 (AKAZE: 61): both files are zero-padded to the next
+    // multiple before every Hamming call (plain, cross, guided) — equal zero bytes on both sides leave every distance as it is
+    if (d1.dtype == 1 && d1.cols % 4 != 0) {
+        const int padded = (d1.cols + 3) / 4 * 4;
+        for (Matrix* m : {&d1, &d2}) {
+            std::vector<unsigned char> wide(static_cast<size_t>(m->rows) * padded);
+            const int r = pm_pad_rows_u8(m->data.data(), m->rows, m->cols, wide.data(), padded);
+            if (r != PM_OK) { fprintf(stderr, "pm_cli: pm_pad_rows_u8 failed: %s\n", pm_last_error()); return 1; }
+            m->data.swap(wide);
+            m->cols = padded;
+        }
+    }
     const bool want_ratio = filter == "ratio";
     if (method != "ransac8" && method != "7point-lmeds") { fprintf(stderr, "pm_cli: --method ransac8|7point-lmeds\n"); return 2; }
     const bool want_cross = filter == "cross" || filter == "cross-ratio";
