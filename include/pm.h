@@ -63,6 +63,13 @@ int  pm_ctx_destroy(pm_ctx* ctx);
  * stream.  Lets a caller time the kernels with events on its own stream. */
 int  pm_ctx_set_stream(pm_ctx* ctx, void* hip_stream);
 int  pm_ctx_synchronize(pm_ctx* ctx);
+/* Device buffers for callers without a HIP runtime of their own (a plain-C host that wants the _dev entry points):
+ * hipMalloc / hipFree on the context's device, and copies that are ordered behind the work already enqueued on the
+ * context's stream and block until done.  pm_device_free synchronises the stream first; a NULL pointer is PM_OK. */
+int  pm_device_alloc(pm_ctx* ctx, size_t bytes, void** d_out);
+int  pm_device_free(pm_ctx* ctx, void* d_ptr);
+int  pm_device_upload(pm_ctx* ctx, void* d_dst, const void* src, size_t bytes);
+int  pm_device_download(pm_ctx* ctx, void* dst, const void* d_src, size_t bytes);
 /* Per-kernel timing with hipEvents on the context's stream.  enable!=0 starts collecting.
  * pm_ctx_timing_get: mean milliseconds and launch count of the named kernel since the last
  * pm_ctx_timing_reset (synchronises the stream).  Names: "knn_l2_prep", "knn_l2_mfma_f16",
@@ -71,7 +78,8 @@ int  pm_ctx_synchronize(pm_ctx* ctx);
  * "knn_hamming_merge", "filter_gather", "filter_cross_gather", "concat_points",
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
- * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine". */
+ * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine", "feat_blur", "feat_decimate",
+ * "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather". */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
@@ -131,7 +139,9 @@ enum {
     PM_OPT_KNN_SUPERTILE  = 20, /* u8 coarse kernel, two-buffer form, 8-row groups: 128-row tiles per LDS buffer and per
                                    workgroup barrier, 1 = one (default), 2 = two, 3 = four; timed as knn_l2_mfma_u8,
                                    knn_l2_mfma_u8_s2, knn_l2_mfma_u8_s4 (measured, not faster: DESIGN.md 2.1)        */
-    PM_OPT_COUNT_         = 21
+    PM_OPT_FEAT_CAPACITY  = 21, /* pm_detect_describe[_dev]: candidate (DoG extremum) capacity of a run, 1 .. 2^28; 0 = automatic:
+                                   max(65536, 8 * max_kp).  See the overflow rule at pm_detect_describe_dev                */
+    PM_OPT_COUNT_         = 22
 };
 int  pm_ctx_set_option(pm_ctx* ctx, int option, int value);
 int  pm_ctx_get_option(pm_ctx* ctx, int option, int* value);
@@ -952,6 +962,48 @@ int pm_mgpu_batch_run(pm_mgpu* mg, int n_lanes, int max_n1, int max_n2, int dim,
                       float ratio, int knn_flags, const pm_ransac_params* p, pm_pair_result* results, pm_match* good,
                       uint8_t* masks);
 int pm_mgpu_batch_set_option(pm_mgpu* mg, int option, int value);   /* pm_ctx_set_option on every context of mg */
+
+/* ---- feature front end (replaces main.cpp:22-26 detect and main.cpp:36-40 compute) — docs/SPEC.md S53-S57 -------------
+ * Difference-of-Gaussian keypoints and 128-D gradient descriptors from 8-bit grey pixels, on the device: the HIP port of
+ * the host extractor behind `pm_cli --img1 --img2` (Lowe's scheme: 3 scales per octave, sigma0 1.6, contrast and edge
+ * tests, dominant orientation, 4x4x8 histogram, normalise -> clip 0.2 -> renormalise -> x512 -> 0..255).  Keypoints, their
+ * order and every Gaussian level equal the host extractor's bit for bit; descriptors equal it except where the device's
+ * atan2f or fp64 exp differs from the host's in the last bit (rare rows, one element off by one).
+ *   d_img      h rows of `stride` >= w bytes, row-major.
+ *   max_kp     the strongest max_kp extrema are described: |response| descending, ties in scan order (octave, level,
+ *              y, x ascending).  Every output array holds max_kp rows.
+ *   contrast, edge_r   the host's defaults are 0.03 and 10.
+ *   d_kp_xy    n x 2 float, input-image pixels.        d_desc_u8   n x 128 bytes (feeds pm_bf_knn_l2_u8*_dev; may be NULL).
+ *   d_desc_f32 n x 128 u8-valued floats (may be NULL). d_meta      n x 4 float {sigma in input pixels, dominant angle in
+ *   radians, |DoG response|, octave} (may be NULL).    d_n         device int32: the number of rows written.
+ * Rows keep the selection order; rows whose patch leaves the image or whose descriptor has no energy are dropped.
+ * w < 32 or h < 32: PM_OK, *d_n = 0.  More than 100 000 000 pixels: PM_E_UNSUPPORTED.
+ * Candidate capacity.  Extrema are appended to a buffer of bounded capacity (PM_OPT_FEAT_CAPACITY; default
+ * max(65536, 8 * max_kp), at most 2^28 like the option); the device counter keeps counting past it.  When an image
+ * has more extrema than that, the _dev form writes *d_n = -1 and NO rows (never a subset): raise the option and call
+ * again.  The blocking form reads the counter, grows the buffer to the need and runs again by itself (it allocates
+ * and frees its device copy of the image and its output block on every call); *n_out is written only after every row
+ * has arrived.
+ * The _dev form enqueues on the context's stream and does not synchronise (the context's feature buffer grows on the
+ * first call and when a larger image or capacity comes: one stream synchronisation and a reallocation).  Both forms
+ * return PM_E_UNSUPPORTED on a capturing stream before anything is allocated, like the matcher.
+ * Timing names: "feat_blur", "feat_decimate", "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather". */
+int pm_detect_describe_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast,
+                           float edge_r, float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta, int32_t* d_n);
+int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast, float edge_r,
+                       float* kp_xy, uint8_t* desc_u8, float* desc_f32, float* meta, int32_t* n_out);
+/* TEST AND INSPECTION SURFACE — pm_detect_level_get and pm_detect_tables exist so that the scale space and the tables can
+ * be pinned separately from the rest (tests/test_features_device_*.py).  They carry NO stability promise: they may change
+ * or go with the kernels' internals, and no other entry point depends on them.
+ * pm_detect_level_get: Gaussian level `level` (0 .. 5) of octave `octave` as the LAST detect call on this context left it;
+ * *w_out x *h_out floats into plane (cap_floats of room; plane may be NULL to ask for the size only).  Synchronises. */
+int pm_detect_level_get(pm_ctx* ctx, int octave, int level, float* plane, int cap_floats, int* w_out, int* h_out);
+/* The host-computed tables the kernels read (S53, S56; no GPU needed): tap_radius[6] and taps[6 * 25] (row 0: the base blur
+ * of octave 0, rows 1 .. 5 the level increments; row i holds 2 * tap_radius[i] + 1 values), ori_weight[3 * 393] (inner level
+ * l, index dx^2 + dy^2), ori_radius[3], desc_radius[3], cos_sin[72] (36 cosines, then 36 sines of the bin-centre angles).
+ * Any pointer may be NULL. */
+int pm_detect_tables(int32_t* tap_radius, double* taps, double* ori_weight, int32_t* ori_radius, int32_t* desc_radius,
+                     double* cos_sin);
 
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference

@@ -72,6 +72,8 @@ EXPORTS = [
     "pm_bf_match_guided_l2_f32_dev", "pm_bf_match_guided_l2_u8_dev", "pm_bf_match_guided_hamming_u8_dev",
     "pm_bf_knn_guided_l2_f32", "pm_bf_knn_guided_l2_u8", "pm_bf_knn_guided_hamming_u8",
     "pm_pad_rows_u8", "pm_pad_rows_u8_dev",
+    "pm_detect_describe_dev", "pm_detect_describe", "pm_detect_level_get", "pm_detect_tables",
+    "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
 
@@ -139,6 +141,7 @@ PM_OPT_RANSAC_FORM = 17
 PM_OPT_RANSAC_WG_IDS = 18
 PM_OPT_HAMMING_REFINE = 19
 PM_OPT_KNN_SUPERTILE = 20
+PM_OPT_FEAT_CAPACITY = 21   # candidate capacity of pm_detect_describe[_dev]; 0 = max(65536, 8 * max_kp)
 
 
 _lib = None
@@ -300,6 +303,18 @@ def epiline_endpoints(lines, cols):
     out = np.zeros((lines.shape[0], 4), np.int32)
     _check(lib().pm_epiline_endpoints(_p(lines), lines.shape[0], cols, _p(out)))
     return out
+
+
+def detect_tables():
+    """pm_detect_tables: the host-computed tables of the feature front end (SPEC S53, S56); no GPU needed."""
+    tap_r = np.zeros(6, np.int32)
+    taps = np.zeros((6, 25), np.float64)
+    ori_w = np.zeros((3, 393), np.float64)
+    rad = np.zeros(3, np.int32)
+    r2 = np.zeros(3, np.int32)
+    cs = np.zeros((2, 36), np.float64)
+    _check(lib().pm_detect_tables(_p(tap_r), _p(taps), _p(ori_w), _p(rad), _p(r2), _p(cs)))
+    return {"tap_radius": tap_r, "taps": taps, "ori_weight": ori_w, "ori_radius": rad, "desc_radius": r2, "cos": cs[0], "sin": cs[1]}
 
 
 # ---- GPU context ------------------------------------------------------------------------------
@@ -537,6 +552,36 @@ class Context:
                                                   C.c_void_p(dn_ptr or 0), C.byref(prm), C.c_void_p(dkey_ptr),
                                                   C.c_void_p(dF_ptr), C.c_void_p(dmask_ptr),
                                                   C.c_void_p(dninl_ptr)))
+
+    # -- feature front end (main.cpp:22-26, :36-40; SPEC S53-S57) -----------------------------------------------------
+    def detect_describe_dev(self, dimg_ptr, w, h, stride, max_kp, dkp_ptr, ddesc_u8_ptr, ddesc_f32_ptr, dmeta_ptr, dn_ptr,
+                            contrast=0.03, edge_r=10.0):
+        """Device pointers; outputs sized for max_kp rows; ddesc_u8_ptr / ddesc_f32_ptr / dmeta_ptr may be 0.  *dn = -1: the
+        candidate buffer overflowed (PM_OPT_FEAT_CAPACITY) and no row was written."""
+        _check(lib().pm_detect_describe_dev(self._h, C.c_void_p(dimg_ptr), w, h, stride, max_kp, C.c_float(contrast),
+                                            C.c_float(edge_r), C.c_void_p(dkp_ptr), C.c_void_p(ddesc_u8_ptr or 0),
+                                            C.c_void_p(ddesc_f32_ptr or 0), C.c_void_p(dmeta_ptr or 0), C.c_void_p(dn_ptr)))
+
+    def detect_describe(self, img, max_kp=4000, contrast=0.03, edge_r=10.0):
+        """8-bit grey image (h, w) -> (kp_xy (n, 2) f32, desc_u8 (n, 128), desc_f32 (n, 128), meta (n, 4)); blocking."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        kp = np.zeros((max_kp, 2), np.float32)
+        du8 = np.zeros((max_kp, 128), np.uint8)
+        df = np.zeros((max_kp, 128), np.float32)
+        meta = np.zeros((max_kp, 4), np.float32)
+        n = C.c_int32()
+        _check(lib().pm_detect_describe(self._h, _p(img), w, h, w, max_kp, C.c_float(contrast), C.c_float(edge_r), _p(kp),
+                                        _p(du8), _p(df), _p(meta), C.byref(n)))
+        return kp[:n.value].copy(), du8[:n.value].copy(), df[:n.value].copy(), meta[:n.value].copy()
+
+    def detect_level(self, octave, level):
+        """Gaussian level of the last detect call on this context (pm_detect_level_get), as an (h, w) float32 array."""
+        w, h = C.c_int(), C.c_int()
+        _check(lib().pm_detect_level_get(self._h, octave, level, None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.float32)
+        _check(lib().pm_detect_level_get(self._h, octave, level, _p(out), out.size, C.byref(w), C.byref(h)))
+        return out
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

@@ -170,6 +170,7 @@ int pm_ctx_destroy(pm_ctx* ctx)
     if (ctx->sync_words) (void)hipFree(ctx->sync_words);
     if (ctx->kf_tile) (void)hipFree(ctx->kf_tile);
     if (ctx->widen) (void)hipFree(ctx->widen);
+    if (ctx->feat) (void)hipFree(ctx->feat);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -187,6 +188,50 @@ int pm_ctx_set_stream(pm_ctx* ctx, void* hip_stream)
 int pm_ctx_synchronize(pm_ctx* ctx)
 {
     PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return PM_OK;
+}
+
+// Device buffers for callers that have no HIP of their own (pm_cli --features device): plain hipMalloc / hipFree and
+// blocking copies ordered behind the context's stream.
+int pm_device_alloc(pm_ctx* ctx, size_t bytes, void** d_out)
+{
+    PM_REQUIRE(ctx != nullptr && d_out != nullptr, PM_E_INVALID, "null argument");
+    *d_out = nullptr;
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    if (hipMalloc(d_out, bytes ? bytes : 1) != hipSuccess) {
+        set_error("hipMalloc(%zu) failed", bytes);
+        return PM_E_NOMEM;
+    }
+    return PM_OK;
+}
+
+int pm_device_free(pm_ctx* ctx, void* d_ptr)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    if (!d_ptr) return PM_OK;
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    PM_HIP_CHECK(hipFree(d_ptr));
+    return PM_OK;
+}
+
+int pm_device_upload(pm_ctx* ctx, void* d_dst, const void* src, size_t bytes)
+{
+    PM_REQUIRE(ctx != nullptr && (bytes == 0 || (d_dst && src)), PM_E_INVALID, "null argument");
+    if (!bytes) return PM_OK;
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    PM_HIP_CHECK(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return PM_OK;
+}
+
+int pm_device_download(pm_ctx* ctx, void* dst, const void* d_src, size_t bytes)
+{
+    PM_REQUIRE(ctx != nullptr && (bytes == 0 || (dst && d_src)), PM_E_INVALID, "null argument");
+    if (!bytes) return PM_OK;
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    PM_HIP_CHECK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PM_OK;
 }
@@ -228,9 +273,9 @@ int pm_ctx_set_option(pm_ctx* ctx, int option, int value)
 {
     PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
     PM_REQUIRE(option >= 1 && option < PM_OPT_COUNT_, PM_E_INVALID, "unknown option");
-    const int vmax = option == PM_OPT_RANSAC_WG_IDS ? 128 : option == PM_OPT_KNN_RING_PROLOGUE ? 8 : option == PM_OPT_KNN_RING ? 6 : (option == PM_OPT_KNN_F16_WAVES || option == PM_OPT_KNN_U8_GROUP || option == PM_OPT_KNN_SUPERTILE) ? 3 : 2;
+    const int vmax = option == PM_OPT_FEAT_CAPACITY ? (1 << 28) : option == PM_OPT_RANSAC_WG_IDS ? 128 : option == PM_OPT_KNN_RING_PROLOGUE ? 8 : option == PM_OPT_KNN_RING ? 6 : (option == PM_OPT_KNN_F16_WAVES || option == PM_OPT_KNN_U8_GROUP || option == PM_OPT_KNN_SUPERTILE) ? 3 : 2;
     PM_REQUIRE(value >= 0 && value <= vmax, PM_E_INVALID,
-               "option value out of range (0 = automatic, 1, 2; KNN_F16_WAVES, KNN_U8_GROUP, KNN_SUPERTILE: .. 3)");
+               "option value out of range (0 = automatic, 1, 2; KNN_F16_WAVES, KNN_U8_GROUP, KNN_SUPERTILE: .. 3; FEAT_CAPACITY: .. 2^28)");
     ctx->opts[option] = value;
     return PM_OK;
 }

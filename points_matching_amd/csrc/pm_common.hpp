@@ -92,6 +92,14 @@ struct pm_ctx {
     // f32 copies of u8 descriptor rows for the shapes pm_bf_knn_l2_u8 hands to the f32 matcher (grow-only)
     float* widen = nullptr;
     size_t widen_cap = 0;
+    // feature front end (features.hip): tables, candidate counter, Gaussian pyramid, candidates and row staging (grow-only;
+    // apart from the arena so that pm_detect_level_get can read the pyramid of the last call), and that call's octave plan
+    char* feat = nullptr;
+    size_t feat_cap = 0;
+    size_t feat_counter_off = 0;
+    int feat_noct = 0;
+    int feat_w[16] = {}, feat_h[16] = {};
+    size_t feat_off[16] = {};              // byte offset of each octave's six planes
 };
 
 namespace pm {

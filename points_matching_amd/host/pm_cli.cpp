@@ -10,9 +10,16 @@
 //          [--filter midpoint|ratio|cross|cross-ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
-//          [--guided TAU]
+//          [--guided TAU] [--features host|device]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
+// --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
+// (pm_detect_describe_dev, docs/SPEC.md S53-S57); keypoints and float rows are downloaded once for the match list and
+// --save-features.  The plain brute-force matcher (--filter midpoint|ratio, one GPU) then reads the u8 descriptor rows where
+// the extractor left them, through DEVICE pointers (pm_bf_knn_l2_u8_dev).  Every other matcher path (--filter cross|cross-ratio,
+// --matcher flann, --gpus N / --mgpu, the second pass of --guided) takes host rows by its interface and is given the
+// downloaded float rows: same values, one upload more.  host (default): the C++ extractor of pm_features.cpp.  Same
+// keypoints either way; descriptors may differ by one in rare elements (pm.h).
 // --matcher flann: the reference's ACTIVE matcher object (`FlannBasedMatcher matcher;`, main.cpp:44): 4 randomised
 // kd-trees, 32 checks (pm_flann_*; approximate, seeded by --seed); bf (default) is the exact matcher of main.cpp:43.
 // NOTE: the default matcher DEVIATES from main.cpp:44 on purpose — the exact matcher is faster on this hardware at every
@@ -174,7 +181,7 @@ int main(int argc, char** argv)
     long iters = 10000;
     unsigned long long seed = 0x5EED;
     int device = 0, gpus = 1, canvas_w = 993, canvas_h = 660;       // canvas default: the size of img01/img02
-    std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint;
+    std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint, features = "host";
     bool extract_only = false;
     int max_kp = 4000;
     bool quiet = false, json = false, iters_given = false, print_epi = false, force_mgpu = false;
@@ -206,6 +213,7 @@ int main(int argc, char** argv)
         else if (a == "--img2") img2_path = val("--img2");
         else if (a == "--img1") img1_path = val("--img1");
         else if (a == "--max-kp") max_kp = atoi(val("--max-kp"));
+        else if (a == "--features") features = val("--features");      // host | device: where --img1/--img2 are extracted
         else if (a == "--save-features") save_prefix = val("--save-features");   // PREFIX_{desc1,desc2,kp1,kp2}.pmm
         else if (a == "--extract-only") extract_only = true;                     // stop after the feature front-end (no GPU needed)
         else if (a == "--canvas") { canvas_w = atoi(val("--canvas")); canvas_h = atoi(val("--canvas")); }
@@ -215,6 +223,21 @@ int main(int argc, char** argv)
     }
     Matrix d1, d2, k1, k2;
     const bool from_images = !img1_path.empty();
+    if (features != "host" && features != "device") { fprintf(stderr, "pm_cli: --features host|device\n"); return 2; }
+    if (features == "device" && !from_images) { fprintf(stderr, "pm_cli: --features device needs --img1 / --img2\n"); return 2; }
+    pm_ctx* feat_ctx = nullptr;                       // --features device: the context that extracted, reused by the matcher
+    void* dev_img[2] = {nullptr, nullptr};
+    void* dev_kp[2] = {nullptr, nullptr};
+    void* dev_u8[2] = {nullptr, nullptr};             // n x 128 descriptor bytes, left on the device for the matcher
+    void* dev_f32[2] = {nullptr, nullptr};
+    void* dev_n[2] = {nullptr, nullptr};
+    auto free_device_features = [&]() {               // the device buffers of --features device, then their context
+        if (!feat_ctx) return;
+        for (int i = 0; i < 2; ++i)
+            for (void** p : {&dev_img[i], &dev_kp[i], &dev_u8[i], &dev_f32[i], &dev_n[i]}) { pm_device_free(feat_ctx, *p); *p = nullptr; }
+        pm_ctx_destroy(feat_ctx);
+        feat_ctx = nullptr;
+    };
     // what the caller knows about float descriptors (pm.h: a hint is verified on the device, a wrong one only costs time).
     // The build-owned extractor of --img1/--img2 writes u8-valued rows, so that path says so unless told otherwise.
     if (knn_hint.empty()) knn_hint = from_images ? "u8" : "auto";
@@ -234,7 +257,42 @@ int main(int argc, char** argv)
             pm_feat::Image im;
             std::string err;
             if (!pm_feat::load_pnm_gray(*paths[i], im, err)) { fprintf(stderr, "pm_cli: %s\n", err.c_str()); return 1; }
-            const pm_feat::Features ft = pm_feat::detect_and_describe(im, max_kp);
+            pm_feat::Features ft;
+            if (features == "device") {
+                // ---- upload, extract on the device, bring back keypoints + float rows (match list, --save-features)
+                int r = feat_ctx ? PM_OK : pm_ctx_create(device, &feat_ctx);
+                if (r != PM_OK) return fail("pm_ctx_create", r);
+                const size_t rows = static_cast<size_t>(max_kp);
+                r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 8, &dev_kp[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 128, &dev_u8[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 512, &dev_f32[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, 4, &dev_n[i]);
+                if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
+                if (r != PM_OK) return fail("device buffers", r);
+                int32_t n = -1;
+                for (int cap = 0; n < 0;) {
+                    r = pm_detect_describe_dev(feat_ctx, static_cast<const uint8_t*>(dev_img[i]), im.w, im.h, im.w, max_kp, 0.03f, 10.0f,
+                                               static_cast<float*>(dev_kp[i]), static_cast<uint8_t*>(dev_u8[i]),
+                                               static_cast<float*>(dev_f32[i]), nullptr, static_cast<int32_t*>(dev_n[i]));
+                    if (r == PM_OK) r = pm_device_download(feat_ctx, &n, dev_n[i], sizeof n);
+                    if (r != PM_OK) return fail("pm_detect_describe_dev", r);
+                    if (n < 0) {                              // more extrema than the candidate buffer holds: double it
+                        if (cap == 0) cap = max_kp > 8192 ? 8 * max_kp : 65536;
+                        if (cap > (1 << 27)) { fprintf(stderr, "pm_cli: too many extrema\n"); return 1; }
+                        cap *= 2;
+                        r = pm_ctx_set_option(feat_ctx, PM_OPT_FEAT_CAPACITY, cap);
+                        if (r != PM_OK) return fail("pm_ctx_set_option", r);
+                    }
+                }
+                ft.n = n;
+                ft.kp_xy.resize(2 * static_cast<size_t>(n));
+                ft.desc.resize(128 * static_cast<size_t>(n));
+                r = pm_device_download(feat_ctx, ft.kp_xy.data(), dev_kp[i], ft.kp_xy.size() * sizeof(float));
+                if (r == PM_OK) r = pm_device_download(feat_ctx, ft.desc.data(), dev_f32[i], ft.desc.size() * sizeof(float));
+                if (r != PM_OK) return fail("download of the features", r);
+            } else
+                ft = pm_feat::detect_and_describe(im, max_kp);
             dm[i]->rows = ft.n; dm[i]->cols = 128; dm[i]->dtype = 0;
             dm[i]->data.assign(reinterpret_cast<const unsigned char*>(ft.desc.data()),
                                reinterpret_cast<const unsigned char*>(ft.desc.data()) + ft.desc.size() * sizeof(float));
@@ -250,13 +308,13 @@ int main(int argc, char** argv)
             for (int i = 0; i < 4; ++i)
                 if (!save_matrix(save_prefix + names[i], *ms[i])) return 1;
         }
-        if (extract_only) return 0;
-        if (d1.rows < 8 || d2.rows < 8) { fprintf(stderr, "pm_cli: too few keypoints\n"); return 1; }
+        if (extract_only) { free_device_features(); return 0; }
+        if (d1.rows < 8 || d2.rows < 8) { fprintf(stderr, "pm_cli: too few keypoints\n"); free_device_features(); return 1; }
     } else {
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann] [--guided tau_px] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann] [--guided tau_px] [--features host|device] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -348,7 +406,8 @@ int main(int argc, char** argv)
         const int r2 = gather_and_list();
         if (r2 != PM_OK) return fail("gather", r2);
     } else {
-    rc = pm_ctx_create(device, &ctx);
+    if (feat_ctx) ctx = feat_ctx;
+    else rc = pm_ctx_create(device, &ctx);
     if (rc != PM_OK) return fail("pm_ctx_create", rc);
     t0 = clk::now();
 
@@ -371,6 +430,15 @@ int main(int argc, char** argv)
         rc = pm_flann_build(ctx, d2.f32(), d2.rows, d2.cols, &fp, &ix);
         if (rc == PM_OK) rc = pm_flann_knn_l2_f32(ctx, ix, d1.f32(), d1.rows, k, knn.data());
         pm_flann_destroy(ix);
+    } else if (dev_u8[0] && dev_u8[1]) {
+        // --features device: the descriptor bytes never left the GPU; same records as the float matcher (pm.h)
+        void* d_knn = nullptr;
+        rc = pm_device_alloc(ctx, knn.size() * sizeof(pm_match), &d_knn);
+        if (rc == PM_OK)
+            rc = pm_bf_knn_l2_u8_dev(ctx, static_cast<const uint8_t*>(dev_u8[0]), d1.rows, static_cast<const uint8_t*>(dev_u8[1]), d2.rows,
+                                     128, k, static_cast<pm_match*>(d_knn));
+        if (rc == PM_OK) rc = pm_device_download(ctx, knn.data(), d_knn, knn.size() * sizeof(pm_match));
+        pm_device_free(ctx, d_knn);
     } else if (d1.dtype == 0)
         rc = pm_bf_knn_l2_f32(ctx, d1.f32(), d1.rows, d2.f32(), d2.rows, d1.cols, k, knn_flags, knn.data());
     else
@@ -488,6 +556,8 @@ int main(int argc, char** argv)
                mean_abs, mean_fwd, ms(t0, t1), ms(t1, t2), ms(t2, t3), F[0], F[1], F[2], F[3], F[4], F[5], F[6],
                F[7], F[8]);
     }
+    if (feat_ctx == ctx) ctx = nullptr;                // one context: destroyed with the feature buffers
+    free_device_features();
     pm_ctx_destroy(ctx);
     pm_mgpu_destroy(mg);
     return 0;
