@@ -1005,6 +1005,30 @@ int pm_detect_level_get(pm_ctx* ctx, int octave, int level, float* plane, int ca
 int pm_detect_tables(int32_t* tap_radius, double* taps, double* ori_weight, int32_t* ori_radius, int32_t* desc_radius,
                      double* cos_sin);
 
+/* ---- binary descriptors on the same front end — docs/SPEC.md S58-S60 -----------------------------------------------------
+ * The keypoints, selection order and dominant orientation of pm_detect_describe*, with a steered BRIEF-style descriptor in
+ * place of the gradient histogram: 256 comparisons of pixels of the keypoint's own Gaussian level at integer offsets taken
+ * from a table pre-rotated to the 36 orientation bins and scaled to the level (S59).  Bit i is 1 where the first pixel of
+ * test i is smaller than the second; byte i >> 3, bit i & 7, least significant first (ORB's convention).
+ *   d_desc_bits  n x 32 bytes: feeds pm_bf_knn_hamming_u8*, pm_bf_match_cross_hamming_u8*, pm_bf_knn_guided_hamming_u8*
+ *                (cols = 32) where it lies.  Required.
+ * Every other argument, the status codes, the w < 32 || h < 32 rule, the capture refusal, the candidate capacity with
+ * *d_n = -1 and no rows on overflow, and the blocking form's grow-and-retry are those of pm_detect_describe*.  A row is
+ * dropped only where its patch leaves the image (the same border rule: the offsets stay within the descriptor radius);
+ * there is no energy rule, so the rows of pm_detect_describe* are a subsequence of these, with equal keypoints and meta.
+ * Given the same orientation bin the 32 bytes equal the host extractor's (`pm_cli --descriptor bits`) exactly; the bin can
+ * differ only where the device's atan2f differs from the host's in the last bit.  pm_detect_level_get works after these
+ * calls too.  Timing names: as above, with "feat_describe_bits" and "feat_gather_bits" in place of "feat_describe" and
+ * "feat_gather". */
+int pm_detect_describe_bits_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast,
+                                float edge_r, float* d_kp_xy, uint8_t* d_desc_bits, float* d_meta, int32_t* d_n);
+int pm_detect_describe_bits(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast, float edge_r,
+                            float* kp_xy, uint8_t* desc_bits, float* meta, int32_t* n_out);
+/* TEST AND INSPECTION SURFACE (no stability promise, no GPU needed): base1024 = the 256 tests (x1, y1, x2, y2) of S58 as
+ * int8, row-major; steered110592 = the int8 offsets (dx1, dy1, dx2, dy2) of S59, shape [3 levels][36 bins][256 tests][4].
+ * Either pointer may be NULL. */
+int pm_detect_bits_table(int8_t* base1024, int8_t* steered110592);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

@@ -73,6 +73,7 @@ EXPORTS = [
     "pm_bf_knn_guided_l2_f32", "pm_bf_knn_guided_l2_u8", "pm_bf_knn_guided_hamming_u8",
     "pm_pad_rows_u8", "pm_pad_rows_u8_dev",
     "pm_detect_describe_dev", "pm_detect_describe", "pm_detect_level_get", "pm_detect_tables",
+    "pm_detect_describe_bits_dev", "pm_detect_describe_bits", "pm_detect_bits_table",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -315,6 +316,14 @@ def detect_tables():
     cs = np.zeros((2, 36), np.float64)
     _check(lib().pm_detect_tables(_p(tap_r), _p(taps), _p(ori_w), _p(rad), _p(r2), _p(cs)))
     return {"tap_radius": tap_r, "taps": taps, "ori_weight": ori_w, "ori_radius": rad, "desc_radius": r2, "cos": cs[0], "sin": cs[1]}
+
+
+def detect_bits_table():
+    """pm_detect_bits_table: the 256 tests (256, 4) and their steered offsets (3, 36, 256, 4), int8 (SPEC S58, S59); no GPU needed."""
+    base = np.zeros((256, 4), np.int8)
+    steer = np.zeros((3, 36, 256, 4), np.int8)
+    _check(lib().pm_detect_bits_table(_p(base), _p(steer)))
+    return base, steer
 
 
 # ---- GPU context ------------------------------------------------------------------------------
@@ -574,6 +583,25 @@ class Context:
         _check(lib().pm_detect_describe(self._h, _p(img), w, h, w, max_kp, C.c_float(contrast), C.c_float(edge_r), _p(kp),
                                         _p(du8), _p(df), _p(meta), C.byref(n)))
         return kp[:n.value].copy(), du8[:n.value].copy(), df[:n.value].copy(), meta[:n.value].copy()
+
+    def detect_describe_bits_dev(self, dimg_ptr, w, h, stride, max_kp, dkp_ptr, ddesc_bits_ptr, dmeta_ptr, dn_ptr, contrast=0.03,
+                                 edge_r=10.0):
+        """The binary form (SPEC S58-S60): ddesc_bits_ptr holds max_kp x 32 bytes; dmeta_ptr may be 0; *dn as above."""
+        _check(lib().pm_detect_describe_bits_dev(self._h, C.c_void_p(dimg_ptr), w, h, stride, max_kp, C.c_float(contrast),
+                                                 C.c_float(edge_r), C.c_void_p(dkp_ptr), C.c_void_p(ddesc_bits_ptr),
+                                                 C.c_void_p(dmeta_ptr or 0), C.c_void_p(dn_ptr)))
+
+    def detect_describe_bits(self, img, max_kp=4000, contrast=0.03, edge_r=10.0):
+        """8-bit grey image (h, w) -> (kp_xy (n, 2) f32, desc_bits (n, 32) u8, meta (n, 4)); blocking."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        kp = np.zeros((max_kp, 2), np.float32)
+        bits = np.zeros((max_kp, 32), np.uint8)
+        meta = np.zeros((max_kp, 4), np.float32)
+        n = C.c_int32()
+        _check(lib().pm_detect_describe_bits(self._h, _p(img), w, h, w, max_kp, C.c_float(contrast), C.c_float(edge_r), _p(kp),
+                                             _p(bits), _p(meta), C.byref(n)))
+        return kp[:n.value].copy(), bits[:n.value].copy(), meta[:n.value].copy()
 
     def detect_level(self, octave, level):
         """Gaussian level of the last detect call on this context (pm_detect_level_get), as an (h, w) float32 array."""

@@ -11,6 +11,8 @@
 //   feat_describe  one workgroup per kept keypoint: orientation histogram, 4x4x8 descriptor, ordered fp64 sums
 //   feat_compact   one workgroup: exclusive scan of the row flags, the count (or -1 when the candidate buffer overflowed)
 //   feat_gather    rows to their final places
+// The binary form (S58-S60, pm_detect_describe_bits*) runs feat_describe_bits and feat_gather_bits in place of feat_describe
+// and feat_gather: the same orientation, then 256 pixel comparisons at offsets from a table steered to the orientation bin.
 // Every kernel reads the candidate counter itself: nothing of the call depends on a host round trip.
 #include <algorithm>
 #include <cmath>
@@ -81,6 +83,67 @@ const FeatTables& tables()
             f.sn[b] = std::sin(theta);
         }
         return f;
+    }();
+    return t;
+}
+
+// ---- S58 / S59: the 256 lattice tests and their offsets steered to the 36 bins and scaled to the three inner levels
+constexpr int NBITS = 256;
+struct BitsTables {
+    int8_t base[NBITS][4];             // x1, y1, x2, y2
+    int8_t steer[3][36][NBITS][4];     // dx1, dy1, dx2, dy2
+};
+constexpr size_t STEER_BYTES = sizeof(int8_t) * 3 * 36 * NBITS * 4;
+constexpr size_t STEER_OFF = (sizeof(FeatTables) + 255) / 256 * 256;      // behind FeatTables in the feature buffer
+
+const BitsTables& bits_tables()
+{
+    static const BitsTables t = [] {
+        BitsTables b;
+        memset(&b, 0, sizeof b);
+        // splitmix64; a coordinate is the sum of three draws in -5 .. 5.  host/pm_features.cpp (bits_pattern) holds the second
+        // C++ statement of this construction, on purpose: the host extractor is the specification and does not call into this
+        // library.  tests/test_features_bits_cpu.py pins both against the numpy statement (this one through
+        // pm_detect_bits_table, the host's through the rows of `pm_cli --descriptor bits`).
+        unsigned long long state = 0x504D4249545331ULL;
+        auto coord = [&]() {
+            int v = 0;
+            for (int k = 0; k < 3; ++k) {
+                state += 0x9E3779B97F4A7C15ULL;
+                unsigned long long z = state;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+                z ^= z >> 31;
+                v += static_cast<int>((z >> 33) % 11) - 5;
+            }
+            return v;
+        };
+        for (int n = 0; n < NBITS;) {
+            const int c[4] = {coord(), coord(), coord(), coord()};          // braces: evaluated left to right
+            if (c[0] * c[0] + c[1] * c[1] > 225 || c[2] * c[2] + c[3] * c[3] > 225) continue;
+            if (c[0] == c[2] && c[1] == c[3]) continue;
+            bool seen = false;
+            for (int i = 0; i < n && !seen; ++i) {
+                const int8_t* o = b.base[i];
+                seen = (o[0] == c[0] && o[1] == c[1] && o[2] == c[2] && o[3] == c[3]) ||
+                       (o[0] == c[2] && o[1] == c[3] && o[2] == c[0] && o[3] == c[1]);
+            }
+            if (seen) continue;
+            for (int j = 0; j < 4; ++j) b.base[n][j] = static_cast<int8_t>(c[j]);
+            ++n;
+        }
+        const FeatTables& f = tables();
+        for (int l = 0; l < 3; ++l) {
+            const double s = f.r2[l] / 15.0;
+            for (int k = 0; k < 36; ++k)
+                for (int i = 0; i < NBITS; ++i)
+                    for (int p = 0; p < 4; p += 2) {
+                        const double x = b.base[i][p], y = b.base[i][p + 1];
+                        b.steer[l][k][i][p] = static_cast<int8_t>(std::nearbyint(s * (f.cs[k] * x - f.sn[k] * y)));
+                        b.steer[l][k][i][p + 1] = static_cast<int8_t>(std::nearbyint(s * (f.sn[k] * x + f.cs[k] * y)));
+                    }
+        }
+        return b;
     }();
     return t;
 }
@@ -204,6 +267,61 @@ __global__ __launch_bounds__(256) void feat_rank(const unsigned* counter, unsign
     if (t < n && rank < static_cast<unsigned>(max_kp)) sel[rank] = static_cast<int>(t);
 }
 
+// The orientation histogram of S56, shared by feat_describe and feat_describe_bits (NT threads): per-pixel records into LDS,
+// the lane that owns a bin walks them serially in fp64, lane 0 takes the arg-max of the smoothed histogram.  Leaves theta,
+// cos and sin of the dominant bin in s_par[0 .. 2] and its index in *s_bin (where asked for); ends with a barrier.
+template <int NT>
+__device__ __forceinline__ void feat_orientation(const float* L, int w, int x, int y, int rad, int lev, const FeatTables* tab, int tid,
+                                                 double* s_rec, int* s_key, double* s_hist, double* s_par, int* s_bin)
+{
+    auto at = [&](int yy, int xx) { return L[static_cast<size_t>(yy) * w + xx]; };
+    const int side = 2 * rad + 1, npx = side * side;          // <= 841
+    const int npx4 = (npx + 3) & ~3;
+    for (int p = tid; p < npx4; p += NT) {
+        if (p < npx) {
+            const int dy = p / side - rad, dx = p % side - rad;
+            const float gx = (at(y + dy, x + dx + 1) - at(y + dy, x + dx - 1)) * 0.5f;
+            const float gy = (at(y + dy + 1, x + dx) - at(y + dy - 1, x + dx)) * 0.5f;
+            const float mag = sqrtf(gx * gx + gy * gy);
+            const float ang = atan2f(gy, gx);
+            s_rec[p] = tab->ori_w[lev][dx * dx + dy * dy] * mag;
+            s_key[p] = static_cast<int>((ang + PI_) / (2 * PI_) * 36) % 36;
+        } else {
+            s_rec[p] = 0;
+            s_key[p] = -1;
+        }
+    }
+    __syncthreads();
+    if (tid < 36) {
+        double acc = 0;
+        const int4* k4 = reinterpret_cast<const int4*>(s_key);
+        const double2* m2 = reinterpret_cast<const double2*>(s_rec);
+        for (int p4 = 0; p4 < npx4 / 4; ++p4) {
+            const int4 k = k4[p4];
+            const double2 lo = m2[2 * p4], hi = m2[2 * p4 + 1];
+            acc += k.x == tid ? lo.x : 0.0;
+            acc += k.y == tid ? lo.y : 0.0;
+            acc += k.z == tid ? hi.x : 0.0;
+            acc += k.w == tid ? hi.y : 0.0;
+        }
+        s_hist[tid] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int best = 0;
+        double sm_best = (s_hist[35] + s_hist[0] + s_hist[1]) / 3.0;
+        for (int b = 1; b < 36; ++b) {
+            const double sm = (s_hist[(b + 35) % 36] + s_hist[b] + s_hist[(b + 1) % 36]) / 3.0;
+            if (sm > sm_best) { sm_best = sm; best = b; }
+        }
+        s_par[0] = tab->theta[best];
+        s_par[1] = tab->cs[best];
+        s_par[2] = tab->sn[best];
+        if (s_bin) *s_bin = best;
+    }
+    __syncthreads();
+}
+
 // ---- S56: orientation and descriptor of one keypoint per workgroup of eight waves.  Every histogram bin and every one of
 // the 128 accumulators is an fp64 sum over pixels in (dy, dx) order: the workgroup writes per-pixel records into LDS, then
 // the lane that owns a bin walks the records serially and adds what lands in its bin.  No floating-point atomics.
@@ -258,53 +376,7 @@ __global__ __launch_bounds__(DTHREADS) void feat_describe(const float* pyr, cons
     }
     auto at = [&](int yy, int xx) { return L[static_cast<size_t>(yy) * w + xx]; };
 
-    // orientation histogram
-    {
-        const int side = 2 * rad + 1, npx = side * side;          // <= 841
-        const int npx4 = (npx + 3) & ~3;
-        for (int p = tid; p < npx4; p += DTHREADS) {
-            if (p < npx) {
-                const int dy = p / side - rad, dx = p % side - rad;
-                const float gx = (at(y + dy, x + dx + 1) - at(y + dy, x + dx - 1)) * 0.5f;
-                const float gy = (at(y + dy + 1, x + dx) - at(y + dy - 1, x + dx)) * 0.5f;
-                const float mag = sqrtf(gx * gx + gy * gy);
-                const float ang = atan2f(gy, gx);
-                s_rec[p] = tab->ori_w[lev][dx * dx + dy * dy] * mag;
-                s_key[p] = static_cast<int>((ang + PI_) / (2 * PI_) * 36) % 36;
-            } else {
-                s_rec[p] = 0;
-                s_key[p] = -1;
-            }
-        }
-        __syncthreads();
-        if (tid < 36) {
-            double acc = 0;
-            const int4* k4 = reinterpret_cast<const int4*>(s_key);
-            const double2* m2 = reinterpret_cast<const double2*>(s_rec);
-            for (int p4 = 0; p4 < npx4 / 4; ++p4) {
-                const int4 k = k4[p4];
-                const double2 lo = m2[2 * p4], hi = m2[2 * p4 + 1];
-                acc += k.x == tid ? lo.x : 0.0;
-                acc += k.y == tid ? lo.y : 0.0;
-                acc += k.z == tid ? hi.x : 0.0;
-                acc += k.w == tid ? hi.y : 0.0;
-            }
-            s_hist[tid] = acc;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int best = 0;
-            double sm_best = (s_hist[35] + s_hist[0] + s_hist[1]) / 3.0;
-            for (int b = 1; b < 36; ++b) {
-                const double sm = (s_hist[(b + 35) % 36] + s_hist[b] + s_hist[(b + 1) % 36]) / 3.0;
-                if (sm > sm_best) { sm_best = sm; best = b; }
-            }
-            s_par[0] = tab->theta[best];
-            s_par[1] = tab->cs[best];
-            s_par[2] = tab->sn[best];
-        }
-        __syncthreads();
-    }
+    feat_orientation<DTHREADS>(L, w, x, y, rad, lev, tab, tid, s_rec, s_key, s_hist, s_par, nullptr);
     const double theta = s_par[0], cs = s_par[1], sn = s_par[2], cell = tab->cell[lev];
 
     // 4 x 4 x 8 descriptor
@@ -431,6 +503,61 @@ __global__ __launch_bounds__(DTHREADS) void feat_describe(const float* pyr, cons
     }
 }
 
+// ---- S60: orientation and the 256 steered tests of one keypoint per workgroup of four waves.  The orientation is that of
+// feat_describe (one function); thread i then compares the two pixels of test i on the keypoint's level, a wave's ballot is
+// eight packed bytes (bit i & 7 of byte i >> 3), and lane 0 of each wave stores them.  The offsets stay within r2, so the
+// border rule of feat_describe keeps every read inside the plane; there is no energy rule.
+constexpr int BTHREADS = NBITS;
+__global__ __launch_bounds__(BTHREADS) void feat_describe_bits(const float* pyr, const FeatTables* tab, const int8_t* steer,
+                                                               const unsigned* counter, unsigned cap, int max_kp,
+                                                               const unsigned long long* keys, const int4* info, const int4* geom,
+                                                               const int* sel, float* kp_tmp, unsigned char* desc_tmp, float* meta_tmp,
+                                                               int* valid)
+{
+    __shared__ __attribute__((aligned(16))) double s_rec[ORI_MAX];
+    __shared__ __attribute__((aligned(16))) int s_key[ORI_MAX];
+    __shared__ double s_hist[36];
+    __shared__ double s_par[3];
+    __shared__ int s_bin;
+    const unsigned cnt = *counter;
+    if (cnt > cap) return;
+    const int n_sel = min(static_cast<int>(cnt), max_kp);
+    const int row = blockIdx.x;
+    if (row >= n_sel) return;
+    const int tid = threadIdx.x;
+    const int ci = sel[row];
+    const int4 c4 = info[ci];
+    const int o = c4.x, lev = c4.y - 1, y = c4.z, x = c4.w;
+    const int4 g4 = geom[ci];
+    const int w = g4.x, h = g4.y;
+    const float* L = pyr + ((static_cast<unsigned long long>(static_cast<unsigned>(g4.w)) << 32) | static_cast<unsigned>(g4.z)) +
+                     static_cast<size_t>(c4.y) * w * h;
+    const int rad = tab->rad[lev], r2 = tab->r2[lev];
+    if (y - rad < 1 || x - rad < 1 || y + rad >= h - 1 || x + rad >= w - 1 || y - r2 < 1 || x - r2 < 1 || y + r2 >= h - 1 || x + r2 >= w - 1) {
+        if (tid == 0) valid[row] = 0;
+        return;
+    }
+    feat_orientation<BTHREADS>(L, w, x, y, rad, lev, tab, tid, s_rec, s_key, s_hist, s_par, &s_bin);
+    const int bin = s_bin;
+    const int8_t* t4 = steer + (static_cast<size_t>(lev * 36 + bin) * NBITS + tid) * 4;
+    const int dx1 = t4[0], dy1 = t4[1], dx2 = t4[2], dy2 = t4[3];
+    const float a = L[static_cast<size_t>(y + dy1) * w + (x + dx1)];
+    const float b = L[static_cast<size_t>(y + dy2) * w + (x + dx2)];
+    const unsigned long long bal = __ballot(a < b);
+    if ((tid & 63) == 0) reinterpret_cast<unsigned long long*>(desc_tmp + static_cast<size_t>(row) * 32)[tid >> 6] = bal;
+    if (tid == 0) {
+        const float scale = static_cast<float>(1 << o);
+        kp_tmp[2 * static_cast<size_t>(row)] = x * scale;
+        kp_tmp[2 * static_cast<size_t>(row) + 1] = y * scale;
+        float* mt = meta_tmp + 4 * static_cast<size_t>(row);
+        mt[0] = static_cast<float>(tab->sig[lev] * scale);
+        mt[1] = static_cast<float>(s_par[0]);
+        mt[2] = __uint_as_float(~static_cast<unsigned>(keys[ci] >> 32));
+        mt[3] = static_cast<float>(o);
+        valid[row] = 1;
+    }
+}
+
 // ---- S57: stable compaction of the rows that survived the border and norm skips.  One workgroup scans the flags in row
 // order and publishes the count; on overflow of the candidate buffer the count is -1 and no row is written.
 __global__ __launch_bounds__(1024) void feat_compact(const unsigned* counter, unsigned cap, int max_kp, const int* valid, int* pos, int* d_n)
@@ -484,6 +611,22 @@ __global__ __launch_bounds__(128) void feat_gather(const unsigned* counter, unsi
     if (meta && tid < 4) meta[4 * static_cast<size_t>(dst) + tid] = meta_tmp[4 * static_cast<size_t>(row) + tid];
 }
 
+// 32-byte rows: eight rows per workgroup, one byte per thread
+__global__ __launch_bounds__(256) void feat_gather_bits(const unsigned* counter, unsigned cap, int max_kp, const int* pos, const float* kp_tmp,
+                                                        const unsigned char* desc_tmp, const float* meta_tmp, float* kp_xy,
+                                                        unsigned char* desc_bits, float* meta)
+{
+    const unsigned cnt = *counter;
+    if (cnt > cap) return;
+    const int row = blockIdx.x * 8 + (threadIdx.x >> 5), tid = threadIdx.x & 31;
+    if (row >= min(static_cast<int>(cnt), max_kp)) return;
+    const int dst = pos[row];
+    if (dst < 0) return;
+    desc_bits[static_cast<size_t>(dst) * 32 + tid] = desc_tmp[static_cast<size_t>(row) * 32 + tid];
+    if (tid < 2) kp_xy[2 * static_cast<size_t>(dst) + tid] = kp_tmp[2 * static_cast<size_t>(row) + tid];
+    if (meta && tid < 4) meta[4 * static_cast<size_t>(dst) + tid] = meta_tmp[4 * static_cast<size_t>(row) + tid];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 // The host's octave rule: n_oct from log2 of the shorter side, halving by (w + 1) / 2, stop below 20 pixels.
@@ -503,7 +646,7 @@ int plan_octaves(int w, int h, int* ow, int* oh)
 }
 
 struct Layout {
-    size_t tables, counter, pyr, keys, info, geom, sel, kp, desc, meta, valid, pos, staging, total;
+    size_t tables, steer, counter, pyr, keys, info, geom, sel, kp, desc, meta, valid, pos, staging, total;
 };
 
 // staging: bytes the blocking form asks for behind everything else (its copy of the image and its output block)
@@ -513,6 +656,7 @@ Layout plan_layout(const pm_ctx* ctx, size_t cap, size_t rows, size_t staging)
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = pm::align_up(off + bytes, 256); return o; };
     l.tables = take(sizeof(FeatTables));
+    l.steer = take(STEER_BYTES);                      // == STEER_OFF
     l.counter = take(256);
     size_t px = 0;
     for (int o = 0; o < ctx->feat_noct; ++o) px += static_cast<size_t>(NLEV) * ctx->feat_w[o] * ctx->feat_h[o];
@@ -546,6 +690,7 @@ int feat_reserve(pm_ctx* ctx, size_t bytes)
     ctx->feat_cap = cap;
     // the tables live at the head of the buffer (blocking copy: the stream is idle, and this path runs once per growth)
     PM_HIP_CHECK(hipMemcpy(ctx->feat, &tables(), sizeof(FeatTables), hipMemcpyHostToDevice));
+    PM_HIP_CHECK(hipMemcpy(ctx->feat + STEER_OFF, bits_tables().steer, STEER_BYTES, hipMemcpyHostToDevice));
     return PM_OK;
 }
 
@@ -565,9 +710,10 @@ int plan_and_reserve(pm_ctx* ctx, int w, int h, int max_kp, size_t cap, size_t s
     return feat_reserve(ctx, l->total);
 }
 
-// Everything of S53-S57 on the context's stream.  cap: candidate capacity of this run.
+// Everything of S53-S57 on the context's stream.  cap: candidate capacity of this run.  bits: the binary form (S58-S60), whose
+// n x 32 bytes go to d_desc_u8.
 int detect_enqueue(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast, float edge_r, size_t cap,
-                   size_t staging, float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta, int32_t* d_n)
+                   size_t staging, bool bits, float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta, int32_t* d_n)
 {
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t rows = std::min<size_t>(static_cast<size_t>(max_kp), cap);
@@ -641,7 +787,12 @@ int detect_enqueue(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, 
                            max_kp, keys, sel);
     }
     // S56: orientation + descriptor
-    {
+    if (bits) {
+        pm::ScopedKernelTime timer(ctx, "feat_describe_bits");
+        hipLaunchKernelGGL(feat_describe_bits, dim3(static_cast<unsigned>(rows)), dim3(BTHREADS), 0, s, pyr, tab,
+                           reinterpret_cast<const int8_t*>(base + l.steer), counter, static_cast<unsigned>(cap), max_kp, keys, info, geom,
+                           sel, kp_tmp, desc_tmp, meta_tmp, valid);
+    } else {
         pm::ScopedKernelTime timer(ctx, "feat_describe");
         hipLaunchKernelGGL(feat_describe, dim3(static_cast<unsigned>(rows)), dim3(DTHREADS), 0, s, pyr, tab, counter,
                            static_cast<unsigned>(cap), max_kp, keys, info, geom, sel, kp_tmp, desc_tmp, meta_tmp, valid);
@@ -651,7 +802,11 @@ int detect_enqueue(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, 
         pm::ScopedKernelTime timer(ctx, "feat_compact");
         hipLaunchKernelGGL(feat_compact, dim3(1), dim3(1024), 0, s, counter, static_cast<unsigned>(cap), max_kp, valid, pos, d_n);
     }
-    {
+    if (bits) {
+        pm::ScopedKernelTime timer(ctx, "feat_gather_bits");
+        hipLaunchKernelGGL(feat_gather_bits, dim3(static_cast<unsigned>((rows + 7) / 8)), dim3(256), 0, s, counter,
+                           static_cast<unsigned>(cap), max_kp, pos, kp_tmp, desc_tmp, meta_tmp, d_kp_xy, d_desc_u8, d_meta);
+    } else {
         pm::ScopedKernelTime timer(ctx, "feat_gather");
         hipLaunchKernelGGL(feat_gather, dim3(static_cast<unsigned>(rows)), dim3(128), 0, s, counter, static_cast<unsigned>(cap), max_kp, pos,
                            kp_tmp, desc_tmp, meta_tmp, d_kp_xy, d_desc_u8, d_desc_f32, d_meta);
@@ -671,14 +826,11 @@ int check_args(pm_ctx* ctx, const void* img, int w, int h, int stride, int max_k
     return PM_OK;
 }
 
-}  // namespace
-
-extern "C" int pm_detect_describe_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast,
-                                      float edge_r, float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta,
-                                      int32_t* d_n)
+// The _dev forms: argument checks, the small-image rule, one enqueue.  The entry points check the context and refuse a
+// capturing stream themselves, so that those messages carry their names.
+int detect_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast, float edge_r, bool bits,
+               float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta, int32_t* d_n)
 {
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_REFUSE_CAPTURE(ctx);
     const int rc = check_args(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, d_kp_xy, d_n);
     if (rc != PM_OK) return rc;
     if (w < 32 || h < 32) {
@@ -686,25 +838,25 @@ extern "C" int pm_detect_describe_dev(pm_ctx* ctx, const uint8_t* d_img, int w, 
         PM_HIP_CHECK(hipMemsetAsync(d_n, 0, sizeof(int32_t), ctx->stream));
         return PM_OK;
     }
-    return detect_enqueue(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, default_capacity(ctx, max_kp), 0, d_kp_xy, d_desc_u8,
+    return detect_enqueue(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, default_capacity(ctx, max_kp), 0, bits, d_kp_xy, d_desc_u8,
                           d_desc_f32, d_meta, d_n);
 }
 
-extern "C" int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast, float edge_r,
-                                  float* kp_xy, uint8_t* desc_u8, float* desc_f32, float* meta, int32_t* n_out)
+// The blocking forms: device copy of the image, output block, run, grow and run again on overflow, download.
+int detect_blocking(pm_ctx* ctx, const char* fn, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast, float edge_r,
+                    bool bits, float* kp_xy, uint8_t* desc_u8, float* desc_f32, float* meta, int32_t* n_out)
 {
-    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
-    PM_REFUSE_CAPTURE(ctx);
     int rc = check_args(ctx, img, w, h, stride, max_kp, contrast, edge_r, kp_xy, n_out);
     if (rc != PM_OK) return rc;
     *n_out = 0;
     if (w < 32 || h < 32) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t img_bytes = static_cast<size_t>(h) * stride;
+    const size_t row_u8 = bits ? 32 : 128, row_f32 = bits ? 0 : 512;
     uint8_t* d_img = nullptr;
     char* d_out = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d_img), img_bytes) != hipSuccess) {
-        pm::set_error("%s: hipMalloc of %zu bytes failed", __func__, img_bytes);
+        pm::set_error("%s: hipMalloc of %zu bytes failed", fn, img_bytes);
         return PM_E_NOMEM;
     }
     hipError_t e = hipMemcpy(d_img, img, img_bytes, hipMemcpyHostToDevice);          // blocking, like every copy of this form
@@ -714,15 +866,15 @@ extern "C" int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h,
     // at most two rounds: the counter of an overflowed run is the exact need of the next (same image, same thresholds)
     for (int round = 0; rc == PM_OK && round < 3; ++round) {
         const size_t rows = std::min<size_t>(static_cast<size_t>(max_kp), cap);
-        const size_t o_kp = 256, o_u8 = o_kp + pm::align_up(rows * 8, 256), o_f32 = o_u8 + pm::align_up(rows * 128, 256);
-        const size_t o_meta = o_f32 + pm::align_up(rows * 512, 256), total = o_meta + pm::align_up(rows * 16, 256);
+        const size_t o_kp = 256, o_u8 = o_kp + pm::align_up(rows * 8, 256), o_f32 = o_u8 + pm::align_up(rows * row_u8, 256);
+        const size_t o_meta = o_f32 + pm::align_up(rows * row_f32, 256), total = o_meta + pm::align_up(rows * 16, 256);
         if (hipMalloc(reinterpret_cast<void**>(&d_out), total) != hipSuccess) {
-            pm::set_error("%s: hipMalloc of %zu bytes failed", __func__, total);
+            pm::set_error("%s: hipMalloc of %zu bytes failed", fn, total);
             rc = PM_E_NOMEM;
             break;
         }
-        rc = detect_enqueue(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, cap, 0, reinterpret_cast<float*>(d_out + o_kp),
-                            reinterpret_cast<uint8_t*>(d_out + o_u8), reinterpret_cast<float*>(d_out + o_f32),
+        rc = detect_enqueue(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, cap, 0, bits, reinterpret_cast<float*>(d_out + o_kp),
+                            reinterpret_cast<uint8_t*>(d_out + o_u8), bits ? nullptr : reinterpret_cast<float*>(d_out + o_f32),
                             reinterpret_cast<float*>(d_out + o_meta), reinterpret_cast<int32_t*>(d_out));
         unsigned need = 0;
         if (rc == PM_OK) {
@@ -734,8 +886,8 @@ extern "C" int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h,
         if (rc == PM_OK && n >= 0) {
             const size_t m = static_cast<size_t>(n);
             if (m) e = hipMemcpy(kp_xy, d_out + o_kp, m * 8, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess && desc_u8) e = hipMemcpy(desc_u8, d_out + o_u8, m * 128, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess && desc_f32) e = hipMemcpy(desc_f32, d_out + o_f32, m * 512, hipMemcpyDeviceToHost);
+            if (m && e == hipSuccess && desc_u8) e = hipMemcpy(desc_u8, d_out + o_u8, m * row_u8, hipMemcpyDeviceToHost);
+            if (m && e == hipSuccess && desc_f32) e = hipMemcpy(desc_f32, d_out + o_f32, m * row_f32, hipMemcpyDeviceToHost);
             if (m && e == hipSuccess && meta) e = hipMemcpy(meta, d_out + o_meta, m * 16, hipMemcpyDeviceToHost);
             if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
             else *n_out = n;                                 // only once every row has arrived
@@ -744,15 +896,52 @@ extern "C" int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h,
         (void)hipFree(d_out);
         d_out = nullptr;
         if (rc == PM_OK) {
-            if (need <= cap) { pm::set_error("%s: overflow reported without a larger need", __func__); rc = PM_E_HIP; }
+            if (need <= cap) { pm::set_error("%s: overflow reported without a larger need", fn); rc = PM_E_HIP; }
             cap = need;
         }
     }
-    if (rc == PM_OK && n < 0) { pm::set_error("%s: the candidate buffer overflowed again after growing", __func__); rc = PM_E_HIP; }
+    if (rc == PM_OK && n < 0) { pm::set_error("%s: the candidate buffer overflowed again after growing", fn); rc = PM_E_HIP; }
     (void)hipStreamSynchronize(ctx->stream);
     if (d_out) (void)hipFree(d_out);
     (void)hipFree(d_img);
     return rc;
+}
+
+}  // namespace
+
+extern "C" int pm_detect_describe_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast,
+                                      float edge_r, float* d_kp_xy, uint8_t* d_desc_u8, float* d_desc_f32, float* d_meta,
+                                      int32_t* d_n)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_REFUSE_CAPTURE(ctx);
+    return detect_dev(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, false, d_kp_xy, d_desc_u8, d_desc_f32, d_meta, d_n);
+}
+
+extern "C" int pm_detect_describe(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast, float edge_r,
+                                  float* kp_xy, uint8_t* desc_u8, float* desc_f32, float* meta, int32_t* n_out)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_REFUSE_CAPTURE(ctx);
+    return detect_blocking(ctx, __func__, img, w, h, stride, max_kp, contrast, edge_r, false, kp_xy, desc_u8, desc_f32, meta, n_out);
+}
+
+extern "C" int pm_detect_describe_bits_dev(pm_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int max_kp, float contrast,
+                                           float edge_r, float* d_kp_xy, uint8_t* d_desc_bits, float* d_meta, int32_t* d_n)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_REFUSE_CAPTURE(ctx);
+    PM_REQUIRE(d_desc_bits != nullptr, PM_E_INVALID, "null descriptor pointer");
+    return detect_dev(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, true, d_kp_xy, d_desc_bits, nullptr, d_meta, d_n);
+}
+
+extern "C" int pm_detect_describe_bits(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int max_kp, float contrast,
+                                       float edge_r, float* kp_xy, uint8_t* desc_bits, float* meta, int32_t* n_out)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_REFUSE_CAPTURE(ctx);
+    PM_REQUIRE(desc_bits != nullptr, PM_E_INVALID, "null descriptor pointer");
+    return detect_blocking(ctx, __func__, img, w, h, stride, max_kp, contrast, edge_r, true, kp_xy, desc_bits, nullptr, meta, n_out);
 }
 
 // Test and inspection accessor: Gaussian level `level` of octave `octave` as the LAST detect call on this context left it.
@@ -793,5 +982,14 @@ extern "C" int pm_detect_tables(int32_t* tap_radius, double* taps, double* ori_w
         memcpy(cos_sin, t.cs, sizeof t.cs);
         memcpy(cos_sin + 36, t.sn, sizeof t.sn);
     }
+    return PM_OK;
+}
+
+// The tables of S58 / S59 (no GPU needed): base1024 = 256 tests (x1, y1, x2, y2); steered110592 = [3][36][256][4] offsets.
+extern "C" int pm_detect_bits_table(int8_t* base1024, int8_t* steered110592)
+{
+    const BitsTables& t = bits_tables();
+    if (base1024) memcpy(base1024, t.base, sizeof t.base);
+    if (steered110592) memcpy(steered110592, t.steer, sizeof t.steer);
     return PM_OK;
 }

@@ -10,7 +10,7 @@
 //          [--filter midpoint|ratio|cross|cross-ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
-//          [--guided TAU] [--features host|device]
+//          [--guided TAU] [--features host|device] [--descriptor grad|bits]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -20,6 +20,11 @@
 // --matcher flann, --gpus N / --mgpu, the second pass of --guided) takes host rows by its interface and is given the
 // downloaded float rows: same values, one upload more.  host (default): the C++ extractor of pm_features.cpp.  Same
 // keypoints either way; descriptors may differ by one in rare elements (pm.h).
+// --descriptor bits (with --img1/--img2; default grad): 256-bit steered binary descriptors (docs/SPEC.md S58-S60) in place of
+// the 128-D gradient rows: the descriptor matrices are uint8 with 32 columns, every path below matches them by Hamming
+// distance, and with --features device (pm_detect_describe_bits_dev) the plain matcher reads them through
+// pm_bf_knn_hamming_u8_dev where the extractor left them.  --dump-bits-pattern prints the host extractor's 256 tests
+// (x1 y1 x2 y2 per line) and exits: the test surface that pins the host's copy of the S58 construction.
 // --matcher flann: the reference's ACTIVE matcher object (`FlannBasedMatcher matcher;`, main.cpp:44): 4 randomised
 // kd-trees, 32 checks (pm_flann_*; approximate, seeded by --seed); bf (default) is the exact matcher of main.cpp:43.
 // NOTE: the default matcher DEVIATES from main.cpp:44 on purpose — the exact matcher is faster on this hardware at every
@@ -181,7 +186,7 @@ int main(int argc, char** argv)
     long iters = 10000;
     unsigned long long seed = 0x5EED;
     int device = 0, gpus = 1, canvas_w = 993, canvas_h = 660;       // canvas default: the size of img01/img02
-    std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint, features = "host";
+    std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint, features = "host", descriptor = "grad";
     bool extract_only = false;
     int max_kp = 4000;
     bool quiet = false, json = false, iters_given = false, print_epi = false, force_mgpu = false;
@@ -214,6 +219,13 @@ int main(int argc, char** argv)
         else if (a == "--img1") img1_path = val("--img1");
         else if (a == "--max-kp") max_kp = atoi(val("--max-kp"));
         else if (a == "--features") features = val("--features");      // host | device: where --img1/--img2 are extracted
+        else if (a == "--descriptor") descriptor = val("--descriptor");  // grad | bits: what --img1/--img2 are described with
+        else if (a == "--dump-bits-pattern") {                             // the host extractor's 256 tests of S58, one per line; no GPU
+            signed char pat[256][4];
+            pm_feat::bits_pattern(pat);
+            for (int t = 0; t < 256; ++t) printf("%d %d %d %d\n", pat[t][0], pat[t][1], pat[t][2], pat[t][3]);
+            return 0;
+        }
         else if (a == "--save-features") save_prefix = val("--save-features");   // PREFIX_{desc1,desc2,kp1,kp2}.pmm
         else if (a == "--extract-only") extract_only = true;                     // stop after the feature front-end (no GPU needed)
         else if (a == "--canvas") { canvas_w = atoi(val("--canvas")); canvas_h = atoi(val("--canvas")); }
@@ -225,10 +237,13 @@ int main(int argc, char** argv)
     const bool from_images = !img1_path.empty();
     if (features != "host" && features != "device") { fprintf(stderr, "pm_cli: --features host|device\n"); return 2; }
     if (features == "device" && !from_images) { fprintf(stderr, "pm_cli: --features device needs --img1 / --img2\n"); return 2; }
+    if (descriptor != "grad" && descriptor != "bits") { fprintf(stderr, "pm_cli: --descriptor grad|bits\n"); return 2; }
+    if (descriptor == "bits" && !from_images) { fprintf(stderr, "pm_cli: --descriptor bits needs --img1 / --img2\n"); return 2; }
+    const bool want_bits = descriptor == "bits";
     pm_ctx* feat_ctx = nullptr;                       // --features device: the context that extracted, reused by the matcher
     void* dev_img[2] = {nullptr, nullptr};
     void* dev_kp[2] = {nullptr, nullptr};
-    void* dev_u8[2] = {nullptr, nullptr};             // n x 128 descriptor bytes, left on the device for the matcher
+    void* dev_u8[2] = {nullptr, nullptr};             // n x 128 (bits: n x 32) descriptor bytes, left on the device for the matcher
     void* dev_f32[2] = {nullptr, nullptr};
     void* dev_n[2] = {nullptr, nullptr};
     auto free_device_features = [&]() {               // the device buffers of --features device, then their context
@@ -265,18 +280,23 @@ int main(int argc, char** argv)
                 const size_t rows = static_cast<size_t>(max_kp);
                 r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
                 if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 8, &dev_kp[i]);
-                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 128, &dev_u8[i]);
-                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 512, &dev_f32[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * (want_bits ? 32 : 128), &dev_u8[i]);
+                if (r == PM_OK && !want_bits) r = pm_device_alloc(feat_ctx, rows * 512, &dev_f32[i]);
                 if (r == PM_OK) r = pm_device_alloc(feat_ctx, 4, &dev_n[i]);
                 if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
                 if (r != PM_OK) return fail("device buffers", r);
                 int32_t n = -1;
                 for (int cap = 0; n < 0;) {
-                    r = pm_detect_describe_dev(feat_ctx, static_cast<const uint8_t*>(dev_img[i]), im.w, im.h, im.w, max_kp, 0.03f, 10.0f,
-                                               static_cast<float*>(dev_kp[i]), static_cast<uint8_t*>(dev_u8[i]),
-                                               static_cast<float*>(dev_f32[i]), nullptr, static_cast<int32_t*>(dev_n[i]));
+                    if (want_bits)
+                        r = pm_detect_describe_bits_dev(feat_ctx, static_cast<const uint8_t*>(dev_img[i]), im.w, im.h, im.w, max_kp, 0.03f,
+                                                        10.0f, static_cast<float*>(dev_kp[i]), static_cast<uint8_t*>(dev_u8[i]), nullptr,
+                                                        static_cast<int32_t*>(dev_n[i]));
+                    else
+                        r = pm_detect_describe_dev(feat_ctx, static_cast<const uint8_t*>(dev_img[i]), im.w, im.h, im.w, max_kp, 0.03f, 10.0f,
+                                                   static_cast<float*>(dev_kp[i]), static_cast<uint8_t*>(dev_u8[i]),
+                                                   static_cast<float*>(dev_f32[i]), nullptr, static_cast<int32_t*>(dev_n[i]));
                     if (r == PM_OK) r = pm_device_download(feat_ctx, &n, dev_n[i], sizeof n);
-                    if (r != PM_OK) return fail("pm_detect_describe_dev", r);
+                    if (r != PM_OK) return fail(want_bits ? "pm_detect_describe_bits_dev" : "pm_detect_describe_dev", r);
                     if (n < 0) {                              // more extrema than the candidate buffer holds: double it
                         if (cap == 0) cap = max_kp > 8192 ? 8 * max_kp : 65536;
                         if (cap > (1 << 27)) { fprintf(stderr, "pm_cli: too many extrema\n"); return 1; }
@@ -287,15 +307,22 @@ int main(int argc, char** argv)
                 }
                 ft.n = n;
                 ft.kp_xy.resize(2 * static_cast<size_t>(n));
-                ft.desc.resize(128 * static_cast<size_t>(n));
+                if (want_bits) ft.bits.resize(32 * static_cast<size_t>(n));
+                else ft.desc.resize(128 * static_cast<size_t>(n));
                 r = pm_device_download(feat_ctx, ft.kp_xy.data(), dev_kp[i], ft.kp_xy.size() * sizeof(float));
-                if (r == PM_OK) r = pm_device_download(feat_ctx, ft.desc.data(), dev_f32[i], ft.desc.size() * sizeof(float));
+                if (r == PM_OK && want_bits) r = pm_device_download(feat_ctx, ft.bits.data(), dev_u8[i], ft.bits.size());
+                if (r == PM_OK && !want_bits) r = pm_device_download(feat_ctx, ft.desc.data(), dev_f32[i], ft.desc.size() * sizeof(float));
                 if (r != PM_OK) return fail("download of the features", r);
             } else
-                ft = pm_feat::detect_and_describe(im, max_kp);
-            dm[i]->rows = ft.n; dm[i]->cols = 128; dm[i]->dtype = 0;
-            dm[i]->data.assign(reinterpret_cast<const unsigned char*>(ft.desc.data()),
-                               reinterpret_cast<const unsigned char*>(ft.desc.data()) + ft.desc.size() * sizeof(float));
+                ft = pm_feat::detect_and_describe(im, max_kp, 0.03f, 10.0f, want_bits ? pm_feat::DESC_BITS : pm_feat::DESC_GRAD);
+            if (want_bits) {
+                dm[i]->rows = ft.n; dm[i]->cols = 32; dm[i]->dtype = 1;
+                dm[i]->data = ft.bits;
+            } else {
+                dm[i]->rows = ft.n; dm[i]->cols = 128; dm[i]->dtype = 0;
+                dm[i]->data.assign(reinterpret_cast<const unsigned char*>(ft.desc.data()),
+                                   reinterpret_cast<const unsigned char*>(ft.desc.data()) + ft.desc.size() * sizeof(float));
+            }
             km[i]->rows = ft.n; km[i]->cols = 2; km[i]->dtype = 0;
             km[i]->data.assign(reinterpret_cast<const unsigned char*>(ft.kp_xy.data()),
                                reinterpret_cast<const unsigned char*>(ft.kp_xy.data()) + ft.kp_xy.size() * sizeof(float));
@@ -314,7 +341,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann] [--guided tau_px] [--features host|device] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -434,7 +461,10 @@ int main(int argc, char** argv)
         // --features device: the descriptor bytes never left the GPU; same records as the float matcher (pm.h)
         void* d_knn = nullptr;
         rc = pm_device_alloc(ctx, knn.size() * sizeof(pm_match), &d_knn);
-        if (rc == PM_OK)
+        if (rc == PM_OK && want_bits)
+            rc = pm_bf_knn_hamming_u8_dev(ctx, static_cast<const uint8_t*>(dev_u8[0]), d1.rows, static_cast<const uint8_t*>(dev_u8[1]),
+                                          d2.rows, 32, k, static_cast<pm_match*>(d_knn));
+        else if (rc == PM_OK)
             rc = pm_bf_knn_l2_u8_dev(ctx, static_cast<const uint8_t*>(dev_u8[0]), d1.rows, static_cast<const uint8_t*>(dev_u8[1]), d2.rows,
                                      128, k, static_cast<pm_match*>(d_knn));
         if (rc == PM_OK) rc = pm_device_download(ctx, knn.data(), d_knn, knn.size() * sizeof(pm_match));

@@ -91,7 +91,41 @@ bool load_pnm_gray(const std::string& path, Image& img, std::string& err)
     return ok;
 }
 
-Features detect_and_describe(const Image& img, int max_kp, float contrast, float edge_r)
+void bits_pattern(signed char out[256][4])
+{
+    // splitmix64; a coordinate is the sum of three draws in -5 .. 5.  csrc/features.hip (bits_tables) states the same
+    // construction for the device table; the two are kept apart on purpose (this file is the specification and links nothing
+    // of the library into the extractor) and are both pinned against numpy by tests/test_features_bits_cpu.py.
+    unsigned long long state = 0x504D4249545331ULL;
+    auto coord = [&]() {
+        int v = 0;
+        for (int k = 0; k < 3; ++k) {
+            state += 0x9E3779B97F4A7C15ULL;
+            unsigned long long z = state;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+            z ^= z >> 31;
+            v += static_cast<int>((z >> 33) % 11) - 5;
+        }
+        return v;
+    };
+    int n = 0;
+    while (n < 256) {
+        const int x1 = coord(), y1 = coord(), x2 = coord(), y2 = coord();
+        if (x1 * x1 + y1 * y1 > 225 || x2 * x2 + y2 * y2 > 225) continue;
+        if (x1 == x2 && y1 == y2) continue;
+        bool seen = false;
+        for (int i = 0; i < n && !seen; ++i)
+            seen = (out[i][0] == x1 && out[i][1] == y1 && out[i][2] == x2 && out[i][3] == y2) ||
+                   (out[i][0] == x2 && out[i][1] == y2 && out[i][2] == x1 && out[i][3] == y1);
+        if (seen) continue;
+        out[n][0] = static_cast<signed char>(x1); out[n][1] = static_cast<signed char>(y1);
+        out[n][2] = static_cast<signed char>(x2); out[n][3] = static_cast<signed char>(y2);
+        ++n;
+    }
+}
+
+Features detect_and_describe(const Image& img, int max_kp, float contrast, float edge_r, DescKind kind)
 {
     Features out;
     if (img.w < 32 || img.h < 32) return out;
@@ -153,8 +187,10 @@ Features detect_and_describe(const Image& img, int max_kp, float contrast, float
     std::stable_sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.mag > b.mag; });
     if (static_cast<int>(cands.size()) > max_kp) cands.resize(max_kp);
 
-    // ---- orientation + 4x4x8 descriptor
+    // ---- orientation + 4x4x8 descriptor (or the 256 steered tests of S58-S60)
     const double PI = 3.14159265358979323846;
+    signed char pattern[256][4];
+    if (kind == DESC_BITS) bits_pattern(pattern);
     for (const Cand& kp : cands) {
         const Plane& L = oct[kp.o][kp.i];
         const double sig = SIGMA0 * std::pow(kf, kp.i);
@@ -182,6 +218,26 @@ Features detect_and_describe(const Image& img, int max_kp, float contrast, float
         const int r2 = static_cast<int>(std::ceil(cell * 2.5 * std::sqrt(2.0))) + 1;
         if (y - r2 < 1 || x - r2 < 1 || y + r2 >= L.h - 1 || x + r2 >= L.w - 1) continue;
         const double c = std::cos(theta), sn = std::sin(theta);
+        if (kind == DESC_BITS) {
+            // S59: the lattice scaled so that its radius 15 lands on r2, rotated by the bin-centre angle, rounded to pixels
+            const double s = r2 / 15.0;
+            unsigned char row[32] = {0};
+            for (int i = 0; i < 256; ++i) {
+                int d[4];
+                for (int p = 0; p < 4; p += 2) {
+                    const double px = pattern[i][p], py = pattern[i][p + 1];
+                    d[p] = static_cast<int>(std::nearbyint(s * (c * px - sn * py)));
+                    d[p + 1] = static_cast<int>(std::nearbyint(s * (sn * px + c * py)));
+                }
+                if (L.at(y + d[1], x + d[0]) < L.at(y + d[3], x + d[2])) row[i >> 3] |= static_cast<unsigned char>(1u << (i & 7));
+            }
+            out.bits.insert(out.bits.end(), row, row + 32);
+            const float scale = static_cast<float>(1 << kp.o);
+            out.kp_xy.push_back(x * scale);
+            out.kp_xy.push_back(y * scale);
+            ++out.n;
+            continue;
+        }
         double desc[4][4][8] = {};
         for (int dy = -r2; dy <= r2; ++dy)
             for (int dx = -r2; dx <= r2; ++dx) {

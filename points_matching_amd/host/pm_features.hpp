@@ -22,14 +22,23 @@ struct Image {               // 8-bit grey, row-major
 
 struct Features {
     std::vector<float> kp_xy;       // n x 2 pixel coordinates (x, y) in the input image
-    std::vector<float> desc;        // n x 128, integer-valued 0..255
+    std::vector<float> desc;        // n x 128, integer-valued 0..255 (DESC_GRAD)
+    std::vector<unsigned char> bits;   // n x 32 bytes (DESC_BITS)
     int n = 0;
 };
+
+// DESC_GRAD: the 4x4x8 gradient histogram.  DESC_BITS (docs/SPEC.md S58-S60): 256 comparisons of pixels of the keypoint's
+// Gaussian level at lattice offsets rotated to the dominant orientation bin and scaled to the level, packed LSB first.
+enum DescKind { DESC_GRAD = 0, DESC_BITS = 1 };
+
+// S58: the 256 tests (x1, y1, x2, y2), a fixed integer construction.
+void bits_pattern(signed char out[256][4]);
 
 // Binary PGM (P5, maxval <= 255) or binary PPM (P6; converted with the ITU-R 601 luma weights PIL's "L" uses).
 bool load_pnm_gray(const std::string& path, Image& img, std::string& err);
 
 // max_kp strongest DoG extrema (by |response|) that survive the tests; deterministic.
-Features detect_and_describe(const Image& img, int max_kp = 4000, float contrast = 0.03f, float edge_r = 10.0f);
+Features detect_and_describe(const Image& img, int max_kp = 4000, float contrast = 0.03f, float edge_r = 10.0f,
+                             DescKind kind = DESC_GRAD);
 
 }  // namespace pm_feat
