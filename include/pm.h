@@ -1029,6 +1029,69 @@ int pm_detect_describe_bits(pm_ctx* ctx, const uint8_t* img, int w, int h, int s
  * Either pointer may be NULL. */
 int pm_detect_bits_table(int8_t* base1024, int8_t* steered110592);
 
+/* ---- sparse optical-flow tracking: pyramidal Lucas-Kanade — docs/SPEC.md S61-S66 ------------------------------------------
+ * The frame-to-frame way to correspondences (cv::calcOpticalFlowPyrLK, cv::cuda::SparsePyrLKOpticalFlow): the points of the
+ * previous frame are tracked into the next one, with sub-pixel positions, no second detection, no descriptors and no k-NN.
+ * Inverse-compositional form on integer samples: every sum is an exact integer sum, so the result is a function of the two
+ * images, the points and the parameters alone (bit for bit the plain-C statement tests/lk_ref.c).  OpenCV's results are
+ * close, not equal: its oscillation rule is not restated and its sampling differs.
+ *
+ * pm_pyramid is an image pyramid on the device (S61: level l + 1 is a 5-tap binomial reduction of level l, (w + 1) / 2 by
+ * (h + 1) / 2 pixels; it exists while l + 1 <= max_level and both sides are at least 16).  It is an object of its own so that
+ * a video loop builds ONE pyramid per frame: frame k's pyramid is the "previous" pyramid of the next call.
+ *   pm_pyramid_create   allocates every level (the only allocation of the tracking path).  PM_E_INVALID: null pointers,
+ *                       max_level outside [0, 7], w or h < 1.  PM_E_UNSUPPORTED: w or h below 16, more than 100 000 000
+ *                       pixels, a capturing stream.
+ *   pm_pyramid_build_dev  d_img: h rows of `stride` >= w bytes on the device.  Enqueues on the context's stream: one copy and
+ *                       one launch per level above 0; does not synchronise.
+ *   pm_pyramid_level_get  TEST AND INSPECTION SURFACE (no stability promise).  Level `level` as the last build left it, *w_out
+ *                       x *h_out bytes into plane (cap bytes of room; plane may be NULL to ask for the size only); level = -1
+ *                       writes the number of levels to *w_out.  Synchronises.
+ * pm_lk_params: every field is checked; anything out of range, unknown flag bits or reserved != 0 is PM_E_INVALID. */
+typedef struct pm_pyramid pm_pyramid;            /* opaque; device memory owned by the object */
+#define PM_LK_USE_INITIAL 1
+typedef struct pm_lk_params {
+    int32_t win_radius;   /* 2 .. 15 (window 2r+1; OpenCV's 21x21 is 10) */
+    int32_t max_level;    /* 0 .. 7; the top level used is min(max_level, levels of the pyramids - 1) */
+    int32_t max_iters;    /* 1 .. 100 (OpenCV: 30) */
+    float   eps;          /* finite, >= 0 (OpenCV: 0.01) */
+    float   min_eig;      /* finite, >= 0, grey-level^2 units (OpenCV: 1e-4) */
+    float   fb_thresh;    /* 0 = no forward-backward check; else finite, > 0, pixels */
+    int32_t flags;        /* PM_LK_USE_INITIAL = 1 */
+    int32_t reserved;     /* 0 */
+} pm_lk_params;
+int pm_pyramid_create(pm_ctx* ctx, int w, int h, int max_level, pm_pyramid** out);
+int pm_pyramid_destroy(pm_pyramid* pyr);
+int pm_pyramid_build_dev(pm_ctx* ctx, pm_pyramid* pyr, const uint8_t* d_img, int stride);
+int pm_pyramid_level_get(pm_ctx* ctx, const pm_pyramid* pyr, int level, uint8_t* plane, int cap, int* w_out, int* h_out);
+/* Tracking, ONE launch ("lk_track": one wave per point; level loop, iterations and the backward track of the
+ * forward-backward check inside it).  Enqueues on the context's stream, allocates nothing, keeps no per-call state.
+ *   d_pts     cap x 2 float, pixels of the previous frame.   d_n   device int32 count, clamped to [0, cap]; NULL = cap.  The
+ *             -1 that pm_detect_describe*_dev writes on overflow counts as 0, so the call chains after it with no host
+ *             round trip.  Rows at or beyond the count are neither read nor written.
+ *   d_init    cap x 2 float initial positions in the next frame: required with PM_LK_USE_INITIAL, NULL without it.
+ *   d_out     cap x 2 float: the last guess, written for EVERY status.   d_status  cap bytes: 1 tracked, 2 left the image
+ *             (non-finite input lands here), 3 flat (eigenvalue or determinant test at level 0), 4 failed the
+ *             forward-backward check.  A point is a correspondence iff its status is 1.
+ *   d_err     mean absolute grey difference of the last window evaluated at level 0, -1 if none (may be NULL).
+ *   d_fb      forward-backward distance in pixels, -1 where no backward track ran (may be NULL).
+ * The gather form adds one launch ("lk_compact") that keeps the status-1 points in input order: d_xy1 (the input points),
+ * d_xy2 (their positions in the next frame), d_src_idx (row in d_pts; may be NULL) and *d_count.  {d_xy1, d_xy2,
+ * counts = d_count, parts = 1, cap} is a pm_points_view for every *_run_dev estimator.  d_out / d_status may be NULL there
+ * (the rows then live in the context's scratch arena, which may grow on the first call: one stream synchronisation).
+ * PM_E_INVALID: null arguments, parameters out of range, reserved != 0, d_init not matching the flag, pyramids of different
+ * shape or level count or of another device, cap < 0.  PM_E_UNSUPPORTED: cap == 0 (n == 0 in the host form), and a
+ * capturing stream (refused before anything is allocated or launched, like the matcher and the feature front end).
+ * pm_track_lk is the blocking host form: host images and points in, host results out; it builds both pyramids and frees
+ * everything it allocated.  Timing names: "lk_pyr_down", "lk_track", "lk_compact". */
+int pm_track_lk_dev(pm_ctx* ctx, const pm_pyramid* prev, const pm_pyramid* next, const float* d_pts, const int32_t* d_n, int cap,
+                    const float* d_init, const pm_lk_params* p, float* d_out, uint8_t* d_status, float* d_err, float* d_fb);
+int pm_track_lk_gather_dev(pm_ctx* ctx, const pm_pyramid* prev, const pm_pyramid* next, const float* d_pts, const int32_t* d_n,
+                           int cap, const float* d_init, const pm_lk_params* p, float* d_xy1, float* d_xy2, int32_t* d_src_idx,
+                           int32_t* d_count, float* d_out, uint8_t* d_status);
+int pm_track_lk(pm_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int w, int h, int stride, const float* pts, int n,
+                const float* init, const pm_lk_params* p, float* out, uint8_t* status, float* err, float* fb);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

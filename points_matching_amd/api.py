@@ -74,6 +74,8 @@ EXPORTS = [
     "pm_pad_rows_u8", "pm_pad_rows_u8_dev",
     "pm_detect_describe_dev", "pm_detect_describe", "pm_detect_level_get", "pm_detect_tables",
     "pm_detect_describe_bits_dev", "pm_detect_describe_bits", "pm_detect_bits_table",
+    "pm_pyramid_create", "pm_pyramid_destroy", "pm_pyramid_build_dev", "pm_pyramid_level_get",
+    "pm_track_lk_dev", "pm_track_lk_gather_dev", "pm_track_lk",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -93,6 +95,19 @@ class PointsView(C.Structure):
     """pm_points_view: `parts` padded blocks of correspondences with device-side counts (include/pm.h)."""
     _fields_ = [("xy1", C.c_void_p), ("xy2", C.c_void_p), ("counts", C.c_void_p), ("parts", C.c_int32),
                 ("cap", C.c_int32), ("pitch_xy", C.c_int64), ("pitch_cnt", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LkParams(C.Structure):
+    """pm_lk_params (include/pm.h, SPEC S61-S66); lk_params() fills it with OpenCV's defaults."""
+    _fields_ = [("win_radius", C.c_int32), ("max_level", C.c_int32), ("max_iters", C.c_int32), ("eps", C.c_float),
+                ("min_eig", C.c_float), ("fb_thresh", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+PM_LK_USE_INITIAL = 1
+
+
+def lk_params(win_radius=10, max_level=3, max_iters=30, eps=0.01, min_eig=1e-4, fb_thresh=0.0, flags=0):
+    return LkParams(win_radius, max_level, max_iters, eps, min_eig, fb_thresh, flags, 0)
 
 
 class Camera(C.Structure):
@@ -611,6 +626,45 @@ class Context:
         _check(lib().pm_detect_level_get(self._h, octave, level, _p(out), out.size, C.byref(w), C.byref(h)))
         return out
 
+    # -- sparse optical-flow tracking (cv::calcOpticalFlowPyrLK; SPEC S61-S66) ------------------------------------------
+    def pyramid(self, w, h, max_level=3):
+        """A device image pyramid (pm_pyramid) for w x h frames; build it with Pyramid.build_dev."""
+        return Pyramid(self, w, h, max_level)
+
+    def track_lk_dev(self, prev, next_, dpts_ptr, dn_ptr, cap, prm, dout_ptr, dstatus_ptr, derr_ptr=None, dfb_ptr=None, dinit_ptr=None):
+        """Device pointers; prev / next_: built Pyramids; dn_ptr (device int32 count) may be None = cap; prm: LkParams."""
+        _check(lib().pm_track_lk_dev(self._h, prev._h, next_._h, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                     C.c_void_p(dinit_ptr or 0), C.byref(prm), C.c_void_p(dout_ptr), C.c_void_p(dstatus_ptr),
+                                     C.c_void_p(derr_ptr or 0), C.c_void_p(dfb_ptr or 0)))
+
+    def track_lk_gather_dev(self, prev, next_, dpts_ptr, dn_ptr, cap, prm, dxy1_ptr, dxy2_ptr, dcount_ptr, dsrc_ptr=None, dout_ptr=None,
+                            dstatus_ptr=None, dinit_ptr=None):
+        """Track and keep the status-1 points in input order: {dxy1, dxy2, dcount, parts 1, cap} is a PointsView."""
+        _check(lib().pm_track_lk_gather_dev(self._h, prev._h, next_._h, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                            C.c_void_p(dinit_ptr or 0), C.byref(prm), C.c_void_p(dxy1_ptr), C.c_void_p(dxy2_ptr),
+                                            C.c_void_p(dsrc_ptr or 0), C.c_void_p(dcount_ptr), C.c_void_p(dout_ptr or 0),
+                                            C.c_void_p(dstatus_ptr or 0)))
+
+    def track_lk(self, img1, img2, pts, prm=None, init=None):
+        """Host form: two 8-bit grey frames (h, w), points (n, 2) -> (out (n, 2) f32, status (n,) u8, err (n,), fb (n,))."""
+        img1 = np.ascontiguousarray(img1, np.uint8)
+        img2 = np.ascontiguousarray(img2, np.uint8)
+        if img1.shape != img2.shape or img1.ndim != 2:
+            raise ValueError("img1 and img2 must be 2-D arrays of one shape")
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        if init is not None:
+            init = np.ascontiguousarray(init, np.float32).reshape(-1, 2)
+            if init.shape[0] != n:
+                raise ValueError("pts and init must have the same length")
+        prm = prm or lk_params()
+        h, w = img1.shape
+        out, status = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        err, fb = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+        _check(lib().pm_track_lk(self._h, _p(img1), _p(img2), w, h, w, _p(pts), n, _p(init), C.byref(prm), _p(out), _p(status),
+                                 _p(err), _p(fb)))
+        return out[:n], status[:n], err[:n], fb[:n]
+
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""
         q = np.ascontiguousarray(q, np.uint8)
@@ -1052,6 +1106,46 @@ class Context:
         """Compacted matches -> PnP rows on the device (uv = keypoint of queryIdx, xyz = map point of trainIdx)."""
         _check(lib().pm_gather_pnp_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dkp_ptr),
                                        n_kp, C.c_void_p(dobj_ptr), n_obj, C.c_void_p(duv_ptr), C.c_void_p(dxyz_ptr)))
+
+
+class Pyramid:
+    """pm_pyramid: the device image pyramid of one frame (SPEC S61).  A video loop keeps one per frame."""
+
+    def __init__(self, ctx, w, h, max_level=3):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.w, self.h = w, h
+        _check(lib().pm_pyramid_create(ctx._h, w, h, max_level, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().pm_pyramid_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def build_dev(self, dimg_ptr, stride=None):
+        """Enqueues the build from a device image of h rows of `stride` (default w) bytes; no synchronisation."""
+        _check(lib().pm_pyramid_build_dev(self._ctx._h, self._h, C.c_void_p(dimg_ptr), self.w if stride is None else stride))
+        return self
+
+    @property
+    def levels(self):
+        n = C.c_int()
+        _check(lib().pm_pyramid_level_get(self._ctx._h, self._h, -1, None, 0, C.byref(n), None))
+        return n.value
+
+    def level(self, l):
+        """Level l as an (h, w) uint8 array (pm_pyramid_level_get; synchronises)."""
+        w, h = C.c_int(), C.c_int()
+        _check(lib().pm_pyramid_level_get(self._ctx._h, self._h, l, None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.uint8)
+        _check(lib().pm_pyramid_level_get(self._ctx._h, self._h, l, _p(out), out.size, C.byref(w), C.byref(h)))
+        return out
 
 
 def _pnp_pair(xyz, uv):

@@ -11,6 +11,7 @@
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
 //          [--guided TAU] [--features host|device] [--descriptor grad|bits]
+//          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -31,6 +32,12 @@
 // size and reproducible (FLANN seeds its trees from C rand()); `--matcher flann` gives the reference's literal flow
 // (FLANN 1-NN -> midpoint filter -> 7-point LMedS).  The image front end (--img1/--img2) is a SIFT-style detector, not
 // the reference's SURF(8000) (main.cpp:22-40): no compatibility with OpenCV's keypoints is claimed.
+// --matcher track (with --img1/--img2 --features device): frame-to-frame correspondences by pyramidal Lucas-Kanade tracking
+// (docs/SPEC.md S61-S66) in place of descriptor matching: keypoints are detected on image 1 only and tracked into image 2 on
+// the device (pm_pyramid_build_dev x 2, pm_track_lk_gather_dev); the gathered pairs feed the chosen estimator (--method) and
+// the rest of the output is as before (a match record holds the keypoint's row as queryIdx, its row among the survivors as
+// trainIdx and distance 0).  --lk-radius (default 10), --lk-levels (3), --lk-fb (forward-backward threshold in pixels,
+// default 0 = off).  Host features, --descriptor bits, --filter, --guided, --gpus / --mgpu are usage errors with it.
 // --filter cross: mutual nearest neighbours (cv::BFMatcher crossCheck = true, docs/SPEC.md S41-S42): forward and reverse
 // matcher pass + the fused filter in one call; cross-ratio adds the ratio test (--ratio) on the forward row.  Brute-force
 // matcher on one GPU only (float and binary descriptors): with --matcher flann or --gpus / --mgpu it is a usage error.
@@ -187,7 +194,9 @@ int main(int argc, char** argv)
     unsigned long long seed = 0x5EED;
     int device = 0, gpus = 1, canvas_w = 993, canvas_h = 660;       // canvas default: the size of img01/img02
     std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint, features = "host", descriptor = "grad";
-    bool extract_only = false;
+    bool extract_only = false, filter_given = false;
+    int lk_radius = 10, lk_levels = 3;
+    float lk_fb = 0.f;
     int max_kp = 4000;
     bool quiet = false, json = false, iters_given = false, print_epi = false, force_mgpu = false;
     for (int i = 1; i < argc; ++i) {
@@ -200,7 +209,10 @@ int main(int argc, char** argv)
         else if (a == "--desc2") desc2 = val("--desc2");
         else if (a == "--kp1") kp1 = val("--kp1");
         else if (a == "--kp2") kp2 = val("--kp2");
-        else if (a == "--filter") filter = val("--filter");
+        else if (a == "--filter") { filter = val("--filter"); filter_given = true; }
+        else if (a == "--lk-radius") lk_radius = atoi(val("--lk-radius"));
+        else if (a == "--lk-levels") lk_levels = atoi(val("--lk-levels"));
+        else if (a == "--lk-fb") lk_fb = strtof(val("--lk-fb"), nullptr);
         else if (a == "--ratio") ratio = strtof(val("--ratio"), nullptr);
         else if (a == "--iters") { iters = strtol(val("--iters"), nullptr, 0); iters_given = true; }
         else if (a == "--guided") { guided_tau = strtof(val("--guided"), nullptr); guided = true; }
@@ -240,6 +252,17 @@ int main(int argc, char** argv)
     if (descriptor != "grad" && descriptor != "bits") { fprintf(stderr, "pm_cli: --descriptor grad|bits\n"); return 2; }
     if (descriptor == "bits" && !from_images) { fprintf(stderr, "pm_cli: --descriptor bits needs --img1 / --img2\n"); return 2; }
     const bool want_bits = descriptor == "bits";
+    const bool track = matcher == "track";
+    if (track && (!from_images || features != "device" || want_bits || filter_given || guided || gpus != 1 || force_mgpu)) {
+        fprintf(stderr, "pm_cli: --matcher track needs --img1 / --img2 --features device and takes no --descriptor bits, --filter, "
+                        "--guided, --gpus N or --mgpu\n");
+        return 2;
+    }
+    if (track && (lk_radius < 2 || lk_radius > 15 || lk_levels < 0 || lk_levels > 7 || !(lk_fb >= 0.f) || !(lk_fb <= 1e6f))) {
+        fprintf(stderr, "pm_cli: --lk-radius 2..15, --lk-levels 0..7, --lk-fb >= 0\n");
+        return 2;
+    }
+    int img_w[2] = {0, 0}, img_h[2] = {0, 0};
     pm_ctx* feat_ctx = nullptr;                       // --features device: the context that extracted, reused by the matcher
     void* dev_img[2] = {nullptr, nullptr};
     void* dev_kp[2] = {nullptr, nullptr};
@@ -273,7 +296,15 @@ int main(int argc, char** argv)
             std::string err;
             if (!pm_feat::load_pnm_gray(*paths[i], im, err)) { fprintf(stderr, "pm_cli: %s\n", err.c_str()); return 1; }
             pm_feat::Features ft;
-            if (features == "device") {
+            img_w[i] = im.w;
+            img_h[i] = im.h;
+            if (track && i == 1) {
+                // ---- the second frame is only uploaded: its positions come from tracking, not from a second detection
+                if (im.w != img_w[0] || im.h != img_h[0]) { fprintf(stderr, "pm_cli: --matcher track needs two images of one size\n"); return 1; }
+                int r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
+                if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
+                if (r != PM_OK) return fail("device buffers", r);
+            } else if (features == "device") {
                 // ---- upload, extract on the device, bring back keypoints + float rows (match list, --save-features)
                 int r = feat_ctx ? PM_OK : pm_ctx_create(device, &feat_ctx);
                 if (r != PM_OK) return fail("pm_ctx_create", r);
@@ -336,12 +367,12 @@ int main(int argc, char** argv)
                 if (!save_matrix(save_prefix + names[i], *ms[i])) return 1;
         }
         if (extract_only) { free_device_features(); return 0; }
-        if (d1.rows < 8 || d2.rows < 8) { fprintf(stderr, "pm_cli: too few keypoints\n"); free_device_features(); return 1; }
+        if (d1.rows < 8 || (!track && d2.rows < 8)) { fprintf(stderr, "pm_cli: too few keypoints\n"); free_device_features(); return 1; }
     } else {
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px]] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -382,7 +413,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (gpus < 1 || canvas_w < 1 || canvas_h < 1) { fprintf(stderr, "pm_cli: bad --gpus / --canvas\n"); return 2; }
-    if (matcher != "bf" && matcher != "flann") { fprintf(stderr, "pm_cli: --matcher bf|flann\n"); return 2; }
+    if (matcher != "bf" && matcher != "flann" && !track) { fprintf(stderr, "pm_cli: --matcher bf|flann|track\n"); return 2; }
     if (matcher == "flann" && (d1.dtype != 0 || gpus > 1 || force_mgpu)) {
         fprintf(stderr, "pm_cli: --matcher flann needs float32 descriptors and a single GPU\n");
         return 2;
@@ -438,6 +469,50 @@ int main(int argc, char** argv)
     if (rc != PM_OK) return fail("pm_ctx_create", rc);
     t0 = clk::now();
 
+    if (track) {
+        // ---- tracking in place of matcher + filter + gather: two pyramids, one track launch, one compaction
+        pm_lk_params lk;
+        lk.win_radius = lk_radius; lk.max_level = lk_levels; lk.max_iters = 30; lk.eps = 0.01f; lk.min_eig = 1e-4f;
+        lk.fb_thresh = lk_fb; lk.flags = 0; lk.reserved = 0;
+        pm_pyramid *py1 = nullptr, *py2 = nullptr;
+        void *d_xy1 = nullptr, *d_xy2 = nullptr, *d_src = nullptr, *d_cnt = nullptr;
+        const size_t rows = static_cast<size_t>(max_kp);
+        int32_t cnt = 0;
+        rc = pm_pyramid_create(ctx, img_w[0], img_h[0], lk_levels, &py1);
+        if (rc == PM_OK) rc = pm_pyramid_create(ctx, img_w[1], img_h[1], lk_levels, &py2);
+        if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 8, &d_xy1);
+        if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 8, &d_xy2);
+        if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 4, &d_src);
+        if (rc == PM_OK) rc = pm_device_alloc(ctx, 4, &d_cnt);
+        if (rc == PM_OK) rc = pm_pyramid_build_dev(ctx, py1, static_cast<const uint8_t*>(dev_img[0]), img_w[0]);
+        if (rc == PM_OK) rc = pm_pyramid_build_dev(ctx, py2, static_cast<const uint8_t*>(dev_img[1]), img_w[1]);
+        if (rc == PM_OK)
+            rc = pm_track_lk_gather_dev(ctx, py1, py2, static_cast<const float*>(dev_kp[0]), static_cast<const int32_t*>(dev_n[0]), max_kp,
+                                        nullptr, &lk, static_cast<float*>(d_xy1), static_cast<float*>(d_xy2), static_cast<int32_t*>(d_src),
+                                        static_cast<int32_t*>(d_cnt), nullptr, nullptr);
+        if (rc == PM_OK) rc = pm_device_download(ctx, &cnt, d_cnt, sizeof cnt);
+        t1 = clk::now();
+        std::vector<int32_t> src(static_cast<size_t>(cnt) + 1);
+        n_good = cnt;
+        xy1.assign(2 * static_cast<size_t>(n_good), 0.f);
+        xy2.assign(2 * static_cast<size_t>(n_good), 0.f);
+        if (rc == PM_OK) rc = pm_device_download(ctx, xy1.data(), d_xy1, xy1.size() * sizeof(float));
+        if (rc == PM_OK) rc = pm_device_download(ctx, xy2.data(), d_xy2, xy2.size() * sizeof(float));
+        if (rc == PM_OK) rc = pm_device_download(ctx, src.data(), d_src, static_cast<size_t>(cnt) * sizeof(int32_t));
+        for (void* p : {d_xy1, d_xy2, d_src, d_cnt}) pm_device_free(ctx, p);
+        pm_pyramid_destroy(py1);
+        pm_pyramid_destroy(py2);
+        if (rc != PM_OK) return fail("tracking", rc);
+        good.resize(n_good);
+        for (int i = 0; i < n_good; ++i) { good[i].queryIdx = src[i]; good[i].trainIdx = i; good[i].imgIdx = 0; good[i].distance = 0.f; }
+        if (!quiet) {
+            const long need = pm_format_match_list(good.data(), n_good, nullptr, 0);
+            std::string text(static_cast<size_t>(need) + 1, '\0');
+            pm_format_match_list(good.data(), n_good, &text[0], text.size());
+            fputs(text.c_str(), stdout);
+        }
+        t2 = clk::now();
+    } else {
     // ---- matcher.match(imageDesc1, imageDesc2, matchePoints, Mat())            main.cpp:42-46
     const int k = want_ratio ? 2 : 1;
     std::vector<pm_match> knn(static_cast<size_t>(d1.rows) * k);
@@ -499,6 +574,7 @@ int main(int argc, char** argv)
     rc = gather_and_list();
     if (rc != PM_OK) return fail("gather", rc);
     t2 = clk::now();
+    }
 
     // ---- cv::findFundamentalMat(...)                                           main.cpp:94-98
     if (method == "7point-lmeds") {
