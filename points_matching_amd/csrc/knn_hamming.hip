@@ -751,32 +751,11 @@ extern "C" int pm_bf_knn_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t qb = static_cast<size_t>(nq) * bytes, tb = static_cast<size_t>(nt) * bytes;
-    const size_t ob = sizeof(pm_match) * static_cast<size_t>(nq) * k;
-    uint8_t *dq = nullptr, *dt = nullptr;
-    pm_match* dout = nullptr;
-    PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dq), qb));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dt), tb ? tb : 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), ob);
-    int rc = PM_OK;
-    if (e != hipSuccess) { pm::set_error("hipMalloc failed: %s", hipGetErrorString(e)); rc = PM_E_NOMEM; }
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && tb) e = hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    }
-    if (rc == PM_OK) rc = pm_bf_knn_hamming_u8_dev(ctx, dq, nq, dt, nt, bytes, k, dout);
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(dq);
-    (void)hipFree(dt);
-    (void)hipFree(dout);
-    return rc;
+    return pm::run_on_staged_rows(ctx, q, static_cast<size_t>(nq) * bytes, t, static_cast<size_t>(nt) * bytes, out,
+                                  sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
+        return pm_bf_knn_hamming_u8_dev(ctx, static_cast<const uint8_t*>(dq), nq, static_cast<const uint8_t*>(dt), nt, bytes, k,
+                                        static_cast<pm_match*>(dout));
+    });
 }
 
 extern "C" int pm_pad_rows_u8(const uint8_t* src, int n, int bytes, uint8_t* dst, int dst_bytes)

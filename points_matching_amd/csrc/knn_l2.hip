@@ -22,6 +22,7 @@
 // Both routes are bit-identical by construction (tests/test_knn_l2_gpu.py asserts it).
 #include <cstdlib>
 
+#include "knn_l2_plan.hpp"
 #include "knn_shared.hpp"
 
 namespace {
@@ -775,7 +776,6 @@ struct KnnGeom {
     float abs_gen;            // ... plus this many units of the SCALED accumulator (flushed subnormals, seed rounding)
     int int_shift;            // u8 route: candidates are ints (w << int_shift) | id and qnorm holds ||q - 128||^2; else 0
 };
-enum { ROUTE_F32 = 0, ROUTE_F16_HINT = 1, ROUTE_AUTO = 2, ROUTE_U8_HINT = 3 };
 
 // position of the r-th (0-based) set bit of m; r < popcount(m)
 __device__ __forceinline__ int nth_set_bit(unsigned long long m, int r)
@@ -1664,196 +1664,56 @@ int kf_prepare(pm_ctx* ctx, int nq, KnnFuse& fz, int queries_per_tile = 32)
     return PM_OK;
 }
 
-// the matcher; `fuse` (k == 2): ratio test + compaction + gather ride the refinement launch (MFMA routes) or follow as
-// pm_filter_ratio_gather_dev (exact kernel)
-// uq / ut != null: the rows are u8 (pm_bf_knn_l2_u8); only the u8 route takes them — the return value 2 tells the caller
-// that this shape needs the f32 path on widened copies (dq / dt are not read in that mode).
-int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt, int dim, int k, int flags, pm_match* dout,
-                   KnnFuse* fuse, const uint8_t* uq = nullptr, const uint8_t* ut = nullptr)
+KnnL2Request knn_l2_request(const pm_ctx* ctx, const void* q, const void* t, bool u8_rows, int nq, int nt, int dim, int k, int flags,
+                            bool fuse)
 {
-    const bool u8in = uq != nullptr;
-    if (u8in) {
-        const bool al = ((reinterpret_cast<uintptr_t>(uq) | reinterpret_cast<uintptr_t>(ut)) & 3) == 0;
-        if (!(k <= 4 && (dim % 4) == 0 && dim <= 128 && nt >= 1 && al)) return 2;
-        flags = PM_KNN_HINT_U8;
-    }
+    KnnL2Request r{};
+    r.nq = nq; r.nt = nt; r.dim = dim; r.k = k; r.flags = flags; r.n_cu = ctx->n_cu;
+    std::memcpy(r.opts, ctx->opts, sizeof(r.opts));
+    r.u8_rows = u8_rows;
+    r.aligned = ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(t)) & (u8_rows ? 3 : 15)) == 0;
+    r.fuse = fuse;
+    return r;
+}
 
-    // the MFMA routes read rows as 16-byte vectors: dim % 4 == 0 AND 16-byte aligned base pointers (anything else
-    // takes the exact kernel, whose loads are scalar unless both hold)
-    // Rows are read as 16-byte vectors when dim % 4 == 0 and the base pointers are 16-byte aligned; the f16 passes (round 3)
-    // also take any other layout (element loads in the prep and refinement kernels: the padded copies do not care) and up
-    // to 256 dimensions (17 k-chunks).  The f32-input pass and the u8 route stay at dim % 4 == 0, dim <= 128.
-    const bool aligned16 = u8in || ((reinterpret_cast<uintptr_t>(dq) | reinterpret_cast<uintptr_t>(dt)) & 15) == 0;
-    const bool vec = (dim % 4) == 0 && aligned16;
-    const bool narrow = vec && dim <= 128;
-    const bool wide16 = !narrow && !(flags & PM_KNN_FORCE_F32) && ctx->opts[PM_OPT_KNN_WIDE] != 1;
-    const bool fast = !(flags & PM_KNN_FORCE_EXACT) && (k <= 2 || (k <= 4 && ctx->opts[PM_OPT_KNN_WIDE] != 1)) && dim <= 256 &&
-                      nt >= 1 && (narrow || wide16) && (dim >= 4 || !vec);
-    if (!fast) {
-        if (u8in) return 2;                                  // (u8 rows have no f32 image here: the caller widens first)
-        const int rx = run_exact(ctx, dq, nq, dt, nt, dim, k, dout);
-        return rx == PM_OK && fuse ? 1 : rx;                 // 1: done, but the caller still has to filter
-    }
-    int route = (flags & PM_KNN_FORCE_F32) ? ROUTE_F32 : ((flags & PM_KNN_HINT_U8) && narrow) ? ROUTE_U8_HINT :
-                (flags & (PM_KNN_HINT_INTEGER | PM_KNN_HINT_U8)) ? ROUTE_F16_HINT : ROUTE_AUTO;
-    const int dp16 = dim <= 128 ? 128 : 256;                 // padded columns of the f16 copies
-    // automatic route: general floats rank on rounded f16 copies too (SPEC S1c); the f32-input pass is enqueued only when
-    // forced (PM_KNN_FORCE_F32) or when PM_OPT_KNN_GENERAL_F16 = 1 keeps it as the automatic route's pass for such data
-    // PM_KNN_HINT_UNIT_NORM: the automatic route's general-float form with its two prep launches in one (knn_l2_prep16u)
-    const bool unit_hint = (flags & PM_KNN_HINT_UNIT_NORM) && route == ROUTE_AUTO;
-    const bool gen32 = route == ROUTE_AUTO && !unit_hint && ctx->opts[PM_OPT_KNN_GENERAL_F16] == 1 && narrow;
-    const bool want32 = route == ROUTE_F32 || gen32, want16 = route != ROUTE_F32;
+KnnGeom knn_geom(const KnnGeomPlan& g, const float* cand)
+{
+    return KnnGeom{cand, g.slots, g.tiles_per_split, g.rows_per_tile, g.lid_mask, g.eps_coef, g.embed_coef, g.eps_coef_gen,
+                   g.abs_gen, g.int_shift};
+}
 
-    // ---- f32 route geometry: 64-row tiles, 128 queries per workgroup, two workgroups per CU.
-    // (A 128-row tile with one workgroup per CU measured 172 us against 153 us at C3.)
-    constexpr int TT = TT32;
-    KnnGeom g32{}, g16{};
-    int splits32 = 1, splits16 = 1, lid_bits32 = 3, lid_bits16 = 4;
-    {
-        const int nqb = (nq + QB - 1) / QB;
-        const int ntiles = (nt + TT - 1) / TT;
-        int splits = (2 * ctx->n_cu + nqb - 1) / nqb;
-        // at most 2048 train rows per split: the id embedded in a candidate costs mantissa bits, and with them
-        // the window widens (more candidates, overflowing lists -> split re-scans): 9-10 id bits at most
-        if (splits < (ntiles + 31) / 32) splits = (ntiles + 31) / 32;
-        if (splits > ntiles) splits = ntiles;
-        if (splits > 64) splits = 64;
-        if (splits < 1) splits = 1;
-        g32.tiles_per_split = (ntiles + splits - 1) / splits;
-        splits32 = (ntiles + g32.tiles_per_split - 1) / g32.tiles_per_split;
-        g32.slots = splits32 * KNN_C;
-        g32.rows_per_tile = TT;
-        // candidate id = (row-group id inside a lane's stream: tile_in_split*(TT/8) + block*4 + group) * 2 + lane half,
-        // in the low mantissa bits
-        while ((1 << lid_bits32) < g32.tiles_per_split * (TT / 8) * 2) ++lid_bits32;
-        g32.lid_mask = (1u << lid_bits32) - 1u;
-        // |coarse - canonical| <= (6*dim + 32) * 2^-24 * (||q||^2 + ||t||^2), plus the id truncation
-        // 2^(bits-23) * (||q||^2 + 2||t||^2); see docs/SPEC.md S1b
-        g32.eps_coef = static_cast<float>((6.0 * dim + 32.0) * 5.9604644775390625e-8 * 1.001);
-        g32.embed_coef = static_cast<float>(static_cast<double>(1u << lid_bits32) * 1.1920928955078125e-7 * 1.01);
-    }
-    // ---- f16 route geometry: 128-row tiles, 256 queries per workgroup (4 waves x 64)
-    // (u8 ring kernel in its 16-wave form, PM_OPT_KNN_F16_WAVES = 3: 512 queries per workgroup)
-    // u8 coarse kernel form (PM_OPT_KNN_RING): 1 two LDS tile buffers, 2 / 3 ring, 4 / 5 register-operand forms (128 queries
-    // per workgroup), 6 register-operand form with a split per WAVE — long sweeps only: taken when every CU stays busy with
-    // splits of at least 8 tiles (1024 rows), else the two-buffer tile kernel runs
-    const bool u8_default_group = ctx->opts[PM_OPT_KNN_U8_GROUP] != 1 && ctx->opts[PM_OPT_KNN_U8_GROUP] != 3;
-    const bool u8_asked = ((flags & PM_KNN_HINT_U8) || u8in) && !(flags & PM_KNN_FORCE_F32);
-    int u8_form = (u8_asked && u8_default_group) ? ctx->opts[PM_OPT_KNN_RING] : 1;
-    int ws_splits = 0;
-    if (u8_form == 6) {
-        const int ntl = (nt + H_TT - 1) / H_TT, nqb128 = (nq + H_QB - 1) / H_QB * 2;
-        int sp = (8 * ctx->n_cu + nqb128 - 1) / nqb128;                // 8 waves per workgroup, one split each
-        if (sp < (ntl + 15) / 16) sp = (ntl + 15) / 16;
-        if (sp > 64) sp = 64;
-        if (sp > ntl) sp = ntl;
-        if (sp < 1) sp = 1;
-        const int tps = (ntl + sp - 1) / sp;
-        const bool fits = (static_cast<long long>(nt) + 3 * H_TT) * (U8_WIDE_ROW16 * 16) < 0x7FFFFFFFLL;   // 32-bit DMA offsets
-        if (tps >= 8 && tps <= 16 && fits) ws_splits = sp; else u8_form = 1;
-    }
-    if (u8_form == 5 && (static_cast<long long>(nt) + 3 * H_TT) * (U8_WIDE_ROW16 * 16) >= 0x7FFFFFFFLL) u8_form = 1;
-    const int qb_wg = u8_form >= 4 ? 128 : (u8_form >= 2 && ctx->opts[PM_OPT_KNN_F16_WAVES] == 3) ? 512 : H_QB;
-    const int q_unit = qb_wg > H_QB ? qb_wg : H_QB;           // (a multiple of 256 also when workgroups take 128 queries)
-    const int nq_pad = (nq + q_unit - 1) / q_unit * q_unit, nt_pad = (nt + H_TT - 1) / H_TT * H_TT;
-    {
-        const int nqb = nq_pad / qb_wg;
-        const int ntiles = nt_pad / H_TT;
-        // train splits sized for ONE workgroup per CU: with LDS-DMA staging a lone workgroup keeps the matrix pipe as busy as
-        // two co-resident ones did with register staging (C3: 18.9 vs 19.0-21.7 us, 4096 x 4096: 10.0 vs 11.6 us), and half
-        // the splits are half the candidate lists the refinement has to read.  PM_OPT_KNN_WG_PER_CU = 2: two per CU.
-        const int wg_per_cu = ctx->opts[PM_OPT_KNN_WG_PER_CU] == 2 ? 2 : 1;
-        int splits = ws_splits ? ws_splits : (wg_per_cu * ctx->n_cu + nqb - 1) / nqb;
-        if (splits < (ntiles + 15) / 16) splits = (ntiles + 15) / 16;          // <= 2048 rows per split (see above)
-        if (splits > ntiles) splits = ntiles;
-        if (splits > 64) splits = 64;
-        if (splits < 1) splits = 1;
-        g16.tiles_per_split = (ntiles + splits - 1) / splits;
-        splits16 = (ntiles + g16.tiles_per_split - 1) / g16.tiles_per_split;
-        g16.slots = splits16 * KNN_C;
-        g16.rows_per_tile = H_TT;
-        while ((1 << lid_bits16) < g16.tiles_per_split * (H_TT / 8) * 2) ++lid_bits16;
-        g16.lid_mask = (1u << lid_bits16) - 1u;
-        g16.eps_coef = 0.f;           // integer data: the f16 products and f32 sums are exact
-        // general floats through the same kernel (SPEC S1c).  d2a = ||q||^2 - 2w, so the window pays TWICE the error of
-        // w: 2 (2^-10 + 2^-22) ||q|| ||t|| <= 2^-10 (1 + 2^-12) (||q||^2 + ||t||^2) for the two roundings, an eighth on top
-        // for the matrix core's internal summation order, plus the f32 route's term for the accumulation and the norms
-        g16.eps_coef_gen = static_cast<float>(9.765625e-4 * 1.125 + (6.0 * dim + 32.0) * 5.9604644775390625e-8 * 1.001);
-        // ... and, in units of the SCALED accumulator: f16 subnormals flushed on either operand (2 * 2^-14 * 2^10 per
-        // element) and the seed's 1/16 rounding times r / 2 <= 64, both doubled
-        g16.abs_gen = static_cast<float>(dim) / 4.f + 4.f;
-        g16.embed_coef = static_cast<float>(static_cast<double>(1u << lid_bits16) * 1.1920928955078125e-7 * 1.01);
-    }
-    // the seeded forms (round 3) of the two hint routes: LDS-DMA staging only, and the u8 route's integer candidates
-    // leave 9 bits for the id (<= 2048 train rows per split, which the split rule above keeps below 64 splits)
-    const int seeded_opt = ctx->opts[PM_OPT_KNN_SEEDED];
-    if (route == ROUTE_U8_HINT && (lid_bits16 > U8_SHIFT || (static_cast<long long>(nt_pad) + H_TT) * U8_DP >= 0x7FFFFFFFLL ||
-                                   seeded_opt == 1))
-    {
-        if (u8in) return 2;                                     // (u8 rows: the caller widens and takes the f32 entry point)
-        route = ROUTE_F16_HINT;                                 // u8-valued data satisfy the integer premise too
-    }
-    // rows per candidate group of the u8 route: PM_OPT_KNN_U8_GROUP 1 / 2 / 3 = 4 / 8 / 16 (0: 8)
-    const int u8_group = ctx->opts[PM_OPT_KNN_U8_GROUP] == 1 ? 4 : (ctx->opts[PM_OPT_KNN_U8_GROUP] == 3 ? 16 : 8);
-    // u8 refinement: integer re-evaluation on the byte copies (default) or the canonical f32 kernel (4-row groups only)
-    const bool u8_int_refine = !(ctx->opts[PM_OPT_KNN_U8_REFINE] == 1 && u8_group == 4);
-    // (f16 pass: the seeded form measured SLOWER than the seed chunk — C3 21.1 vs 18.7 us, 32k x 32k 199 vs 203 us: the four
-    // C-in reads per block cost what the ninth MFMA cost — so it runs only when PM_OPT_KNN_SEEDED = 2 asks for it)
-    const bool f16s = route == ROUTE_F16_HINT && seeded_opt == 2 && narrow &&
-                      (static_cast<long long>(nt_pad) + H_TT) * (F16S_ROW16 * 16) < 0x7FFFFFFFLL;
-    const bool u8r = route == ROUTE_U8_HINT;
-    if (u8r) {
-        g16.lid_mask = (1u << U8_SHIFT) - 1u;
-        g16.int_shift = U8_SHIFT;
-        g16.embed_coef = 0.f;
-    }
-    if (u8in && !(route == ROUTE_U8_HINT && u8_int_refine)) return 2;
-    if ((want32 && lid_bits32 > 16) || (want16 && lid_bits16 > 16)) {    // > 64k rows per lane stream
-        const int rx = run_exact(ctx, dq, nq, dt, nt, dim, k, dout);
-        return rx == PM_OK && fuse ? 1 : rx;
-    }
-
-    // scratch: norms, f16 copies, candidate lists.  The arena is carved per call; callers that
-    // interleave calls on one context are serialised by the stream.
-    const size_t c32 = want32 ? sizeof(float) * static_cast<size_t>(nq) * g32.slots : 0;
-    const size_t c16 = want16 ? sizeof(float) * static_cast<size_t>(nq) * g16.slots : 0;
-    const size_t rowb = u8r ? U8_DP : sizeof(_Float16) * (f16s ? H_DP : dp16 + 16);   // bytes per row of the coarse copies
-    const size_t qh = want16 ? rowb * static_cast<size_t>(nq_pad) : 0;
-    const int t_wide = (u8r && u8_form >= 5) ? 1 : 0;            // 144-byte train rows with the seeds in the pad slots (knn_u8_rega)
-    const size_t th = want16 ? (t_wide ? static_cast<size_t>(U8_WIDE_ROW16) * 16 : rowb) * static_cast<size_t>(nt_pad) : 0;
-    const size_t sdb = (u8r || f16s) ? 4 * static_cast<size_t>(nt_pad + H_TT) : 0;       // seeds (+ one tile of slack)
-    // u8 route, two-buffer coarse form (the only one that reads it): the query copy in B-fragment order too
-    const size_t qfb = (u8r && u8_form <= 1) ? qh : 0;
-    const size_t pkb = fuse ? sizeof(unsigned long long) * static_cast<size_t>(nq) : 0;
-    const size_t need = pm::align_up(sizeof(float) * nq, 256) + pm::align_up(sizeof(float) * nt, 256) +
-                        pm::align_up(c32, 256) + pm::align_up(c16, 256) + pm::align_up(qh, 256) + pm::align_up(th, 256) +
-                        pm::align_up(sdb, 256) + pm::align_up(pkb, 256) + pm::align_up(qfb, 256) + 2048;
-    int rc = pm::arena_reserve(ctx, need);
+// The launch half of the matcher: obeys a KNN_MATRIX plan (knn_l2_plan.hpp) and decides nothing.  `fuse` (the plan was made
+// with fuse = true): ratio test + compaction + gather ride the refinement launch.  uq / ut != null: the rows are u8
+// (dq / dt are not read in that mode).  The arena is carved per call; callers that interleave calls on one context are
+// serialised by the stream.
+int knn_l2_enqueue(pm_ctx* ctx, const KnnL2Plan& p, const float* dq, int nq, const float* dt, int nt, int dim, int k,
+                   pm_match* dout, const KnnFuse* fuse, const uint8_t* uq = nullptr, const uint8_t* ut = nullptr)
+{
+    PM_REFUSE_CAPTURE(ctx);
+    int rc = pm::arena_reserve(ctx, p.need);
     if (rc != PM_OK) return rc;
     pm::arena_reset(ctx);
-    float* qnorm = static_cast<float*>(pm::arena_take(ctx, sizeof(float) * nq));
-    float* tnorm = static_cast<float*>(pm::arena_take(ctx, sizeof(float) * nt));
-    float* cval32 = want32 ? static_cast<float*>(pm::arena_take(ctx, c32)) : nullptr;
-    float* cval16 = want16 ? static_cast<float*>(pm::arena_take(ctx, c16)) : nullptr;
-    _Float16* Qh = want16 ? static_cast<_Float16*>(pm::arena_take(ctx, qh)) : nullptr;
-    _Float16* Th = want16 ? static_cast<_Float16*>(pm::arena_take(ctx, th)) : nullptr;
-    void* seeds = sdb ? pm::arena_take(ctx, sdb) : nullptr;
-    void* Qf = qfb ? pm::arena_take(ctx, qfb) : nullptr;
-    PM_REQUIRE(qnorm && tnorm && (!want32 || cval32) && (!want16 || (cval16 && Qh && Th)) && (!sdb || seeds) && (!qfb || Qf),
+    float* qnorm = static_cast<float*>(pm::arena_take(ctx, p.qnorm_bytes));
+    float* tnorm = static_cast<float*>(pm::arena_take(ctx, p.tnorm_bytes));
+    float* cval32 = p.want32 ? static_cast<float*>(pm::arena_take(ctx, p.c32)) : nullptr;
+    float* cval16 = p.want16 ? static_cast<float*>(pm::arena_take(ctx, p.c16)) : nullptr;
+    _Float16* Qh = p.want16 ? static_cast<_Float16*>(pm::arena_take(ctx, p.qh)) : nullptr;
+    _Float16* Th = p.want16 ? static_cast<_Float16*>(pm::arena_take(ctx, p.th)) : nullptr;
+    void* seeds = p.sdb ? pm::arena_take(ctx, p.sdb) : nullptr;
+    void* Qf = p.qfb ? pm::arena_take(ctx, p.qfb) : nullptr;
+    PM_REQUIRE(qnorm && tnorm && (!p.want32 || cval32) && (!p.want16 || (cval16 && Qh && Th)) && (!p.sdb || seeds) && (!p.qfb || Qf),
                PM_E_NOMEM, "scratch arena too small");
     KnnFuse fz{};
     if (fuse) {
         fz = *fuse;
-        fz.pk = static_cast<unsigned long long*>(pm::arena_take(ctx, pkb));
+        fz.pk = static_cast<unsigned long long*>(pm::arena_take(ctx, p.pkb));
         PM_REQUIRE(fz.pk != nullptr, PM_E_NOMEM, "scratch arena too small");
-        rc = kf_prepare(ctx, nq, fz, (u8r && u8_int_refine) ? 16 : 32);      // (refine8: one count per 16-query workgroup)
+        rc = kf_prepare(ctx, nq, fz, p.kf_tile);
         if (rc != PM_OK) return rc;
     }
-    g32.cand = cval32;
-    g16.cand = cval16;
+    const KnnGeom g32 = knn_geom(p.g32, cval32), g16 = knn_geom(p.g16, cval16);
 
     unsigned long long* stats = ctx->knn_stats;          // persistent, epoch-tagged: never cleared
-    PM_REFUSE_CAPTURE(ctx);
     if (++ctx->knn_epoch == 0u) {              // 2^32 calls: restart the epoch tags
         PM_HIP_CHECK(hipMemsetAsync(stats, 0, 32, ctx->stream));
         ctx->knn_epoch = 1u;
@@ -1864,116 +1724,132 @@ int knn_l2_enqueue(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt
         diag = ctx->knn_diag_words;
         PM_HIP_CHECK(hipMemsetAsync(diag, 0, 12, ctx->stream));
     }
+    const int nq_pad = p.nq_pad, nt_pad = p.nt_pad, t_wide = p.t_wide, route = p.route;
     {
         pm::ScopedKernelTime t(ctx, "knn_l2_prep");
-        if (u8in)
-            hipLaunchKernelGGL(knn_l2_prep8_u8, dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, uq, nq, nq_pad, ut, nt,
-                               nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), t_wide, static_cast<uint2*>(Qf));
-        else if (u8r && ctx->opts[PM_OPT_KNN_PREP_ROWS] != 1)      // 16 rows per workgroup: matcher call 23.5 -> 22.2 us at C3, 15.1 -> 14.2 at C2
-            hipLaunchKernelGGL(knn_l2_prep8<1>, dim3(nq_pad / 16 + nt_pad / 16), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt,
-                               nt, nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), stats, epoch, t_wide, static_cast<uint2*>(Qf));
-        else if (u8r)
-            hipLaunchKernelGGL(knn_l2_prep8<4>, dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt,
-                               nt, nt_pad, dim, qnorm, tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th),
-                               static_cast<int*>(seeds), stats, epoch, t_wide, static_cast<uint2*>(Qf));
-        else if (f16s)
-            hipLaunchKernelGGL((knn_l2_prep16<true, 128, true>), dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq,
-                               nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm, Qh, Th, static_cast<float*>(seeds), stats, epoch);
-        else if (unit_hint) {
+        const dim3 grid(p.prep_grid);
+#define PM_PREP_DP_AL(LAUNCH_)                                                                                            \
+    do {                                                                                                                  \
+        if (p.dp16 == 128) { if (p.vec) LAUNCH_(128, true); else LAUNCH_(128, false); }                                   \
+        else { if (p.vec) LAUNCH_(256, true); else LAUNCH_(256, false); }                                                 \
+    } while (0)
 #define PM_PREP16U(DP_, AL_)                                                                                              \
-    hipLaunchKernelGGL((knn_l2_prep16u<DP_, AL_>), dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, \
-                       nt, nt_pad, dim, qnorm, tnorm, Qh, Th, stats, epoch)
-            if (dp16 == 128) { if (vec) PM_PREP16U(128, true); else PM_PREP16U(128, false); }
-            else { if (vec) PM_PREP16U(256, true); else PM_PREP16U(256, false); }
-#undef PM_PREP16U
-        }
-        else if (want16) {
+    hipLaunchKernelGGL((knn_l2_prep16u<DP_, AL_>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm,   \
+                       tnorm, Qh, Th, stats, epoch)
 #define PM_PREP16(DP_, AL_)                                                                                               \
-    hipLaunchKernelGGL((knn_l2_prep16<false, DP_, AL_>), dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq,    \
-                       nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm, Qh, Th, nullptr, stats, epoch)
-            if (dp16 == 128) { if (vec) PM_PREP16(128, true); else PM_PREP16(128, false); }
-            else { if (vec) PM_PREP16(256, true); else PM_PREP16(256, false); }
-#undef PM_PREP16
-        }
-        else
-            hipLaunchKernelGGL(knn_l2_prep, dim3((nq + 63) / 64 + (nt + 63) / 64), dim3(256), 0, ctx->stream, dq, nq, dt,
-                               nt, dim, qnorm, tnorm, stats, epoch);
-        // automatic route: data that failed the integer premise get f16-ROUNDED scaled copies instead (the train scale
-        // needs the norm maximum of the pass above, hence a launch of its own; it returns at once for integer data)
-        if (route == ROUTE_AUTO && !gen32 && !unit_hint) {
+    hipLaunchKernelGGL((knn_l2_prep16<false, DP_, AL_>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim,    \
+                       qnorm, tnorm, Qh, Th, nullptr, stats, epoch)
 #define PM_PREP16G(DP_, AL_)                                                                                              \
-    hipLaunchKernelGGL((knn_l2_prep16g<DP_, AL_>), dim3(nq_pad / 64 + nt_pad / 64), dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, \
-                       nt, nt_pad, dim, qnorm, tnorm, Qh, Th, stats, epoch)
-            if (dp16 == 128) { if (vec) PM_PREP16G(128, true); else PM_PREP16G(128, false); }
-            else { if (vec) PM_PREP16G(256, true); else PM_PREP16G(256, false); }
-#undef PM_PREP16G
+    hipLaunchKernelGGL((knn_l2_prep16g<DP_, AL_>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm,   \
+                       tnorm, Qh, Th, stats, epoch)
+        switch (p.prep) {
+        case KNN_PREP_U8ROWS:
+            hipLaunchKernelGGL(knn_l2_prep8_u8, grid, dim3(256), 0, ctx->stream, uq, nq, nq_pad, ut, nt, nt_pad, dim, qnorm, tnorm,
+                               reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), t_wide,
+                               static_cast<uint2*>(Qf));
+            break;
+        case KNN_PREP8_16:
+            hipLaunchKernelGGL(knn_l2_prep8<1>, grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm,
+                               reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), stats, epoch,
+                               t_wide, static_cast<uint2*>(Qf));
+            break;
+        case KNN_PREP8_64:
+            hipLaunchKernelGGL(knn_l2_prep8<4>, grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm,
+                               reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), stats, epoch,
+                               t_wide, static_cast<uint2*>(Qf));
+            break;
+        case KNN_PREP16_SEEDED:
+            hipLaunchKernelGGL((knn_l2_prep16<true, 128, true>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim,
+                               qnorm, tnorm, Qh, Th, static_cast<float*>(seeds), stats, epoch);
+            break;
+        case KNN_PREP16_UNIT: PM_PREP_DP_AL(PM_PREP16U); break;
+        case KNN_PREP16: PM_PREP_DP_AL(PM_PREP16); break;
+        default:
+            hipLaunchKernelGGL(knn_l2_prep, grid, dim3(256), 0, ctx->stream, dq, nq, dt, nt, dim, qnorm, tnorm, stats, epoch);
+            break;
         }
-        else if (gen32)
-            hipLaunchKernelGGL(knn_gen_off, dim3(1), dim3(64), 0, ctx->stream, stats, epoch);
+        if (p.prep_gen == KNN_GEN_PREP16G) PM_PREP_DP_AL(PM_PREP16G);
+        else if (p.prep_gen == KNN_GEN_OFF) hipLaunchKernelGGL(knn_gen_off, dim3(1), dim3(64), 0, ctx->stream, stats, epoch);
+#undef PM_PREP16G
+#undef PM_PREP16
+#undef PM_PREP16U
+#undef PM_PREP_DP_AL
         PM_HIP_CHECK(hipGetLastError());
     }
-    if (u8r) {
-        rc = launch_coarse_u8(ctx, Qh, Qf, Th, static_cast<const int*>(seeds), nq, nq_pad, nt, splits16, g16.tiles_per_split,
-                              reinterpret_cast<int*>(cval16), g16.slots, u8_group, u8_form);
+    if (route == ROUTE_U8_HINT) {
+        rc = launch_coarse_u8(ctx, Qh, Qf, Th, static_cast<const int*>(seeds), nq, nq_pad, nt, p.splits16, g16.tiles_per_split,
+                              reinterpret_cast<int*>(cval16), g16.slots, p.u8_group, p.u8_form);
         if (rc != PM_OK) return rc;
-    } else if (f16s) {
-        rc = launch_coarse_f16s(ctx, Qh, Th, static_cast<const float*>(seeds), nq, nq_pad, nt, splits16, g16.tiles_per_split,
+    } else if (p.f16s) {
+        rc = launch_coarse_f16s(ctx, Qh, Th, static_cast<const float*>(seeds), nq, nq_pad, nt, p.splits16, g16.tiles_per_split,
                                 ~g16.lid_mask, cval16, g16.slots);
         if (rc != PM_OK) return rc;
-    } else if (want16) {
-        rc = launch_coarse_f16(ctx, Qh, Th, nq, nq_pad, nt, splits16, g16.tiles_per_split, ~g16.lid_mask, cval16,
-                               g16.slots, stats, epoch, route == ROUTE_AUTO ? 1 : 0, dp16);
+    } else if (p.want16) {
+        rc = launch_coarse_f16(ctx, Qh, Th, nq, nq_pad, nt, p.splits16, g16.tiles_per_split, ~g16.lid_mask, cval16,
+                               g16.slots, stats, epoch, route == ROUTE_AUTO ? 1 : 0, p.dp16);
         if (rc != PM_OK) return rc;
     }
-    if (want32) {
-        rc = launch_coarse_f32(ctx, dq, nq, dt, nt, dim, tnorm, splits32, g32.tiles_per_split, ~g32.lid_mask, cval32,
+    if (p.want32) {
+        rc = launch_coarse_f32(ctx, dq, nq, dt, nt, dim, tnorm, p.splits32, g32.tiles_per_split, ~g32.lid_mask, cval32,
                                g32.slots, stats, epoch, route == ROUTE_AUTO ? 1 : 0);
         if (rc != PM_OK) return rc;
     }
-    if (u8r && u8_int_refine) {
-        pm::ScopedKernelTime t(ctx, "knn_l2_refine");
+    pm::ScopedKernelTime t(ctx, "knn_l2_refine");
+    if (p.refine8) {
 #define PM_R8K(NS_, GROUP_, KM_, FUSE_)                                                                                    \
     hipLaunchKernelGGL((knn_l2_refine8<NS_, GROUP_, KM_, FUSE_>), dim3((nq + 15) / 16), dim3(256), 0, ctx->stream, dq, dt,  \
                        reinterpret_cast<const uint4*>(Qh), reinterpret_cast<const uint4*>(Th), qnorm, tnorm,               \
                        reinterpret_cast<const int*>(cval16), stats, epoch, diag, nq, nt, dim, k, g16.slots, g16.tiles_per_split, dout, fz, \
                        t_wide ? U8_WIDE_ROW16 : U8_ROW16)
-#define PM_R8(NS_, GROUP_) do { if (fuse) PM_R8K(NS_, GROUP_, 2, true); else if (k <= 2) PM_R8K(NS_, GROUP_, 2, false); else PM_R8K(NS_, GROUP_, 4, false); } while (0)
-#define PM_R8G(NS_) do { if (u8_group == 4) PM_R8(NS_, 4); else if (u8_group == 8) PM_R8(NS_, 8); else PM_R8(NS_, 16); } while (0)
-        if (g16.slots <= 16) PM_R8G(1);                      // slots of a query per lane of its 16-lane row
-        else if (g16.slots <= 32) PM_R8G(2);
-        else if (g16.slots <= 64) PM_R8G(4);
-        else if (g16.slots <= 128) PM_R8G(8);
-        else PM_R8G(16);
+#define PM_R8(NS_, GROUP_) do { if (p.refine_fuse) PM_R8K(NS_, GROUP_, 2, true); else if (p.refine_km == 2) PM_R8K(NS_, GROUP_, 2, false); else PM_R8K(NS_, GROUP_, 4, false); } while (0)
+#define PM_R8G(NS_) do { if (p.refine_group == 4) PM_R8(NS_, 4); else if (p.refine_group == 8) PM_R8(NS_, 8); else PM_R8(NS_, 16); } while (0)
+        switch (p.refine_ns) {
+        case 1: PM_R8G(1); break;
+        case 2: PM_R8G(2); break;
+        case 4: PM_R8G(4); break;
+        case 8: PM_R8G(8); break;
+        default: PM_R8G(16); break;
+        }
 #undef PM_R8G
 #undef PM_R8
 #undef PM_R8K
-        PM_HIP_CHECK(hipGetLastError());
-        return PM_OK;
-    }
-    {
-        pm::ScopedKernelTime t(ctx, "knn_l2_refine");
-        const int max_slots = (want16 ? g16.slots : 0) > (want32 ? g32.slots : 0) ? g16.slots : g32.slots;
+    } else {
 #define PM_REFINE5(VEC_, NS_, FUSE_, GEN_, KM_)                                                                      \
     hipLaunchKernelGGL((knn_l2_refine<VEC_, NS_, FUSE_, GEN_, KM_>), dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, dq, dt,  \
                        qnorm, stats, epoch, diag, nq, nt, dim, k, g16, g32, route, dout, fz)
-#define PM_REFINE4(VEC_, NS_, FUSE_, GEN_) do { if (k <= 2) PM_REFINE5(VEC_, NS_, FUSE_, GEN_, 2); else PM_REFINE5(VEC_, NS_, false, GEN_, 4); } while (0)
-#define PM_REFINE3(NS_, FUSE_, GEN_) do { if (vec) PM_REFINE4(true, NS_, FUSE_, GEN_); else PM_REFINE4(false, NS_, FUSE_, GEN_); } while (0)
-#define PM_REFINE2(NS_, FUSE_) do { if (route == ROUTE_AUTO) PM_REFINE3(NS_, FUSE_, true); else PM_REFINE3(NS_, FUSE_, false); } while (0)
-#define PM_REFINE(NS_) do { if (fuse) PM_REFINE2(NS_, true); else PM_REFINE2(NS_, false); } while (0)
-        if (max_slots <= 64) PM_REFINE(1);
-        else if (max_slots <= 128) PM_REFINE(2);
-        else if (max_slots <= 256) PM_REFINE(4);
-        else PM_REFINE(8);
+#define PM_REFINE4(VEC_, NS_, FUSE_, GEN_) do { if (p.refine_km == 2) PM_REFINE5(VEC_, NS_, FUSE_, GEN_, 2); else PM_REFINE5(VEC_, NS_, false, GEN_, 4); } while (0)
+#define PM_REFINE3(NS_, FUSE_, GEN_) do { if (p.refine_vec) PM_REFINE4(true, NS_, FUSE_, GEN_); else PM_REFINE4(false, NS_, FUSE_, GEN_); } while (0)
+#define PM_REFINE2(NS_, FUSE_) do { if (p.refine_gen) PM_REFINE3(NS_, FUSE_, true); else PM_REFINE3(NS_, FUSE_, false); } while (0)
+#define PM_REFINE(NS_) do { if (p.refine_fuse) PM_REFINE2(NS_, true); else PM_REFINE2(NS_, false); } while (0)
+        switch (p.refine_ns) {
+        case 1: PM_REFINE(1); break;
+        case 2: PM_REFINE(2); break;
+        case 4: PM_REFINE(4); break;
+        default: PM_REFINE(8); break;
+        }
 #undef PM_REFINE5
 #undef PM_REFINE4
 #undef PM_REFINE3
 #undef PM_REFINE2
 #undef PM_REFINE
-        PM_HIP_CHECK(hipGetLastError());
     }
+    PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
+}
+
+// Plan and run one matcher call.  *verdict tells the caller what happened: KNN_MATRIX — done, fused tail included;
+// KNN_EXACT — the exact kernel wrote dout, and a caller that wanted the fused tail still has to filter; KNN_WIDEN (u8 rows
+// only) — nothing ran: the shape needs the f32 matcher on widened copies.
+int knn_l2_run(pm_ctx* ctx, const float* dq, int nq, const float* dt, int nt, int dim, int k, int flags, pm_match* dout,
+               const KnnFuse* fuse, int* verdict, const uint8_t* uq = nullptr, const uint8_t* ut = nullptr)
+{
+    const bool u8 = uq != nullptr;
+    const KnnL2Plan p = knn_l2_plan(knn_l2_request(ctx, u8 ? static_cast<const void*>(uq) : dq, u8 ? static_cast<const void*>(ut) : dt, u8,
+                                                   nq, nt, dim, k, flags, fuse != nullptr));
+    *verdict = p.verdict;
+    if (p.verdict == KNN_EXACT) return run_exact(ctx, dq, nq, dt, nt, dim, k, dout);
+    if (p.verdict == KNN_WIDEN) return PM_OK;
+    return knn_l2_enqueue(ctx, p, dq, nq, dt, nt, dim, k, dout, fuse, uq, ut);
 }
 
 }  // namespace
@@ -1988,7 +1864,9 @@ extern "C" int pm_bf_knn_l2_f32_dev(pm_ctx* ctx, const float* dq, int nq, const 
     PM_REQUIRE(nt == 0 || dt, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return knn_l2_enqueue(ctx, dq, nq, dt, nt, dim, k, flags, dout, nullptr);
+    PM_REFUSE_CAPTURE(ctx);
+    int verdict;
+    return knn_l2_run(ctx, dq, nq, dt, nt, dim, k, flags, dout, nullptr, &verdict);
 }
 
 // main.cpp:46 + :49-69 (ratio form) + :77-78 + :89-91 in one call: 2-NN, ratio test, stable compaction and keypoint
@@ -2005,6 +1883,7 @@ extern "C" int pm_bf_knn_l2_ratio_dev(pm_ctx* ctx, const float* d_q, int nq, con
     PM_REQUIRE((d_kp1_xy == nullptr) == (d_kp2_xy == nullptr), PM_E_INVALID, "give both keypoint arrays or none");
     PM_REQUIRE(d_kp1_xy == nullptr || (d_xy1 && d_xy2), PM_E_INVALID, "null point outputs");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
+    PM_REFUSE_CAPTURE(ctx);
     if (nq == 0) {
         PM_HIP_CHECK(hipMemsetAsync(d_n_good, 0, sizeof(int32_t), ctx->stream));
         return PM_OK;
@@ -2020,15 +1899,15 @@ extern "C" int pm_bf_knn_l2_ratio_dev(pm_ctx* ctx, const float* d_q, int nq, con
     const int fusion = ctx->opts[PM_OPT_FILTER_FUSION];
     const bool u8_hint = (flags & PM_KNN_HINT_U8) && !(flags & (PM_KNN_FORCE_F32 | PM_KNN_FORCE_EXACT));
     const bool separate = fusion == 1 || (fusion == 0 && d_knn != nullptr && !(u8_hint && u8_fused_by_default(nq)));
-    int rc;
+    int rc, verdict;
     if (!separate) {
-        rc = knn_l2_enqueue(ctx, d_q, nq, d_t, nt, dim, 2, flags, d_knn, &fz);
-        if (rc <= 0) return rc;                                      // done (fused) or failed
-        // rc == 1: the exact kernel ran (shape outside the MFMA routes) into d_knn; the filter follows as its own launch
+        rc = knn_l2_run(ctx, d_q, nq, d_t, nt, dim, 2, flags, d_knn, &fz, &verdict);
+        if (rc != PM_OK || verdict == KNN_MATRIX) return rc;         // failed, or done (fused)
+        // the exact kernel ran (shape outside the MFMA routes) into d_knn; the filter follows as its own launch
         return pm_filter_ratio_gather_dev(ctx, d_knn, nq, 2, ratio, d_kp1_xy, d_kp2_xy, d_good, d_xy1, d_xy2, d_n_good);
     }
     PM_REQUIRE(d_knn != nullptr, PM_E_INVALID, "the two-launch form needs d_knn");
-    rc = knn_l2_enqueue(ctx, d_q, nq, d_t, nt, dim, 2, flags, d_knn, nullptr);
+    rc = knn_l2_run(ctx, d_q, nq, d_t, nt, dim, 2, flags, d_knn, nullptr, &verdict);
     if (rc != PM_OK) return rc;
     return pm_filter_ratio_gather_dev(ctx, d_knn, nq, 2, ratio, d_kp1_xy, d_kp2_xy, d_good, d_xy1, d_xy2, d_n_good);
 }
@@ -2068,12 +1947,14 @@ extern "C" int pm_bf_knn_l2_u8_dev(pm_ctx* ctx, const uint8_t* dq, int nq, const
     PM_REQUIRE(nt == 0 || dt, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    int rc = nt >= 1 ? knn_l2_enqueue(ctx, nullptr, nq, nullptr, nt, dim, k, 0, dout, nullptr, dq, dt) : 2;
-    if (rc != 2) return rc;
+    PM_REFUSE_CAPTURE(ctx);
+    int verdict;
+    int rc = knn_l2_run(ctx, nullptr, nq, nullptr, nt, dim, k, 0, dout, nullptr, &verdict, dq, dt);
+    if (rc != PM_OK || verdict != KNN_WIDEN) return rc;
     const float *fq = nullptr, *ft = nullptr;
     rc = u8_widened(ctx, dq, nq, dt, nt, dim, &fq, &ft);
     if (rc != PM_OK) return rc;
-    return knn_l2_enqueue(ctx, fq, nq, ft, nt, dim, k, PM_KNN_HINT_INTEGER, dout, nullptr);
+    return knn_l2_run(ctx, fq, nq, ft, nt, dim, k, PM_KNN_HINT_INTEGER, dout, nullptr, &verdict);
 }
 
 extern "C" int pm_bf_knn_l2_u8_ratio_dev(pm_ctx* ctx, const uint8_t* d_q, int nq, const uint8_t* d_t, int nt, int dim, float ratio,
@@ -2086,6 +1967,7 @@ extern "C" int pm_bf_knn_l2_u8_ratio_dev(pm_ctx* ctx, const uint8_t* d_q, int nq
     PM_REQUIRE((d_kp1_xy == nullptr) == (d_kp2_xy == nullptr), PM_E_INVALID, "give both keypoint arrays or none");
     PM_REQUIRE(d_kp1_xy == nullptr || (d_xy1 && d_xy2), PM_E_INVALID, "null point outputs");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
+    PM_REFUSE_CAPTURE(ctx);
     if (nq == 0) {
         PM_HIP_CHECK(hipMemsetAsync(d_n_good, 0, sizeof(int32_t), ctx->stream));
         return PM_OK;
@@ -2094,8 +1976,9 @@ extern "C" int pm_bf_knn_l2_u8_ratio_dev(pm_ctx* ctx, const uint8_t* d_q, int nq
     if (fusion == 2 || (fusion == 0 && u8_fused_by_default(nq))) {
         KnnFuse fz{};
         fz.ratio = ratio; fz.kp1 = d_kp1_xy; fz.kp2 = d_kp2_xy; fz.good = d_good; fz.xy1 = d_xy1; fz.xy2 = d_xy2; fz.n_out = d_n_good;
-        const int rf = nt >= 1 ? knn_l2_enqueue(ctx, nullptr, nq, nullptr, nt, dim, 2, 0, d_knn, &fz, d_q, d_t) : 2;
-        if (rf != 2) return rf;                              // done (fused) or failed; 2: a shape for the widened f32 path
+        int verdict;
+        const int rf = knn_l2_run(ctx, nullptr, nq, nullptr, nt, dim, 2, 0, d_knn, &fz, &verdict, d_q, d_t);
+        if (rf != PM_OK || verdict != KNN_WIDEN) return rf;  // failed, or done (fused); else a shape for the widened f32 path
     }
     const int rc = pm_bf_knn_l2_u8_dev(ctx, d_q, nq, d_t, nt, dim, 2, d_knn);
     if (rc != PM_OK) return rc;
@@ -2111,32 +1994,11 @@ extern "C" int pm_bf_knn_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t qb = static_cast<size_t>(nq) * dim, tb = static_cast<size_t>(nt) * dim;
-    const size_t ob = sizeof(pm_match) * static_cast<size_t>(nq) * k;
-    uint8_t *dq = nullptr, *dt = nullptr;
-    pm_match* dout = nullptr;
-    int rc = PM_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dq), qb);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dt), tb ? tb : 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), ob);
-    if (e != hipSuccess) { pm::set_error("hipMalloc failed: %s", hipGetErrorString(e)); rc = PM_E_NOMEM; }
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && tb) e = hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    }
-    if (rc == PM_OK) rc = pm_bf_knn_l2_u8_dev(ctx, dq, nq, dt, nt, dim, k, dout);
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(dq);
-    (void)hipFree(dt);
-    (void)hipFree(dout);
-    return rc;
+    return pm::run_on_staged_rows(ctx, q, static_cast<size_t>(nq) * dim, t, static_cast<size_t>(nt) * dim, out,
+                                  sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
+        return pm_bf_knn_l2_u8_dev(ctx, static_cast<const uint8_t*>(dq), nq, static_cast<const uint8_t*>(dt), nt, dim, k,
+                                   static_cast<pm_match*>(dout));
+    });
 }
 
 extern "C" int pm_bf_knn_l2_f32(pm_ctx* ctx, const float* q, int nq, const float* t, int nt, int dim, int k,
@@ -2149,34 +2011,9 @@ extern "C" int pm_bf_knn_l2_f32(pm_ctx* ctx, const float* q, int nq, const float
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    const size_t qb = sizeof(float) * static_cast<size_t>(nq) * dim;
-    const size_t tb = sizeof(float) * static_cast<size_t>(nt) * dim;
-    const size_t ob = sizeof(pm_match) * static_cast<size_t>(nq) * k;
-    float *dq = nullptr, *dt = nullptr;
-    pm_match* dout = nullptr;
-    PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dq), qb));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dt), tb ? tb : 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), ob);
-    int rc = PM_OK;
-    if (e != hipSuccess) {
-        pm::set_error("hipMalloc failed: %s", hipGetErrorString(e));
-        rc = PM_E_NOMEM;
-    }
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && tb) e = hipMemcpyAsync(dt, t, tb, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    }
-    if (rc == PM_OK) rc = pm_bf_knn_l2_f32_dev(ctx, dq, nq, dt, nt, dim, k, flags, dout);
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(dq);
-    (void)hipFree(dt);
-    (void)hipFree(dout);
-    return rc;
+    return pm::run_on_staged_rows(ctx, q, sizeof(float) * static_cast<size_t>(nq) * dim, t, sizeof(float) * static_cast<size_t>(nt) * dim,
+                                  out, sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
+        return pm_bf_knn_l2_f32_dev(ctx, static_cast<const float*>(dq), nq, static_cast<const float*>(dt), nt, dim, k, flags,
+                                    static_cast<pm_match*>(dout));
+    });
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -108,6 +109,12 @@ int arena_reserve(pm_ctx* ctx, size_t bytes);          // ensure capacity (may s
 void arena_reset(pm_ctx* ctx);
 void* arena_take(pm_ctx* ctx, size_t bytes);            // 256-B aligned carve; nullptr if over cap
 int pinned_reserve(pm_ctx* ctx, size_t bytes);
+// Host-pointer form of a matcher around its _dev form: device buffers for the two row sets and the result, the rows
+// copied in, run(d_q, d_t, d_out), the result copied out, the stream synchronised, the buffers freed.  (Hidden: the
+// library's dynamic symbol table stays as it was.)
+__attribute__((visibility("hidden")))
+int run_on_staged_rows(pm_ctx* ctx, const void* q, size_t q_bytes, const void* t, size_t t_bytes, void* out, size_t out_bytes,
+                       const std::function<int(void* d_q, void* d_t, void* d_out)>& run);
 
 // RAII event bracket: records start/stop on ctx->stream when timing is on.
 struct ScopedKernelTime {

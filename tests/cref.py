@@ -1,5 +1,6 @@
-"""Builds one of the plain-C restatements under tests/ (homography_ref.c, homography_refine_ref.c, affine_ref.c) with
-the host C compiler into a temporary directory and loads it with ctypes; each *_ref.py loader does this once, on first
+"""Builds one of the plain-C restatements under tests/ (homography_ref.c, homography_refine_ref.c, affine_ref.c), or a C++
+shim over a host-only header of the library (knn_l2_plan_shim.cpp), with
+the host compiler into a temporary directory and loads it with ctypes; each *_ref.py loader does this once, on first
 use, with its own table of signatures."""
 import ctypes as C
 import os
@@ -11,16 +12,24 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _tmps = []          # the build directories live as long as the process (the libraries stay mapped)
 
 
-def load(name, argtypes, restypes=None):
-    """Compiles tests/<name>.c and returns the CDLL, its functions typed by the two tables (function name -> argtypes,
-    function name -> restype; ctypes' int where none is given)."""
-    cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
-    assert cc, "no host C compiler"
+def load(name, argtypes, restypes=None, include=()):
+    """Compiles tests/<name>.c (or, where there is none, tests/<name>.cpp as C++17 with the `include` directories) and
+    returns the CDLL, its functions typed by the two tables (function name -> argtypes, function name -> restype;
+    ctypes' int where none is given)."""
+    src = os.path.join(HERE, name + ".c")
+    if os.path.exists(src):
+        cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc")
+        std = []
+    else:
+        src += "pp"
+        cc = os.environ.get("CXX") or shutil.which("c++") or shutil.which("g++")
+        std = ["-std=c++17"]
+    assert cc, "no host compiler"
     tmp = tempfile.TemporaryDirectory(prefix=name + "_")
     _tmps.append(tmp)
     so = os.path.join(tmp.name, "lib%s.so" % name)
-    r = subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(HERE, name + ".c"),
-                        "-lm"], capture_output=True, text=True)
+    r = subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC"] + std + ["-I" + d for d in include] +
+                       ["-o", so, src, "-lm"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     L = C.CDLL(so)
     for fn, types in argtypes.items():

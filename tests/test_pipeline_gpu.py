@@ -249,3 +249,77 @@ def test_matcher_and_filter_refuse_a_capturing_stream():
         torch.cuda.synchronize()
         torch.cuda.set_stream(prev)
         c.close()
+
+
+@pytest.mark.filterwarnings("ignore:The CUDA Graph is empty")
+@pytest.mark.parametrize("entry", ["f32", "ratio", "u8", "u8_ratio"])
+def test_first_call_under_capture_is_refused_before_any_side_effect(entry):
+    """Each device entry point of the L2 matcher refuses a capturing stream FIRST: on a fresh context, whose first call
+    would otherwise grow the arena, the look-back words or the widening buffer (allocations, a stream synchronise) and, on
+    the u8 forms with a shape outside the u8 route (33 x 40 rows of 6 bytes), record the widening kernels.  After the
+    capture the same context gives the bytes that a context which never saw a capture gives."""
+    import gc
+    import torch
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream(device=dev)
+    prev = torch.cuda.current_stream(dev)
+    torch.cuda.set_stream(st)
+    u8 = entry.startswith("u8")
+    nq, nt, dim = (33, 40, 6) if u8 else (64, 64, 128)
+    rng = np.random.default_rng(5)
+    if u8:
+        q, t = rng.integers(0, 256, (nq, dim), dtype=np.uint8), rng.integers(0, 256, (nt, dim), dtype=np.uint8)
+        kp1, kp2 = rng.random((nq, 2)).astype(np.float32), rng.random((nt, 2)).astype(np.float32)
+    else:
+        w = synth.pair_workload(nq, nt, dim, seed=5, kind="sift")
+        q, t, kp1, kp2 = (np.ascontiguousarray(w[k]) for k in ("q", "t", "kp1", "kp2"))
+    d_q, d_t, d_kp1, d_kp2 = (torch.from_numpy(a).to(dev) for a in (q, t, kp1, kp2))
+    out = {"knn": torch.zeros((nq, 2, 4), dtype=torch.int32, device=dev), "good": torch.zeros((nq, 4), dtype=torch.int32, device=dev),
+           "xy1": torch.zeros((nq, 2), dtype=torch.float32, device=dev), "xy2": torch.zeros((nq, 2), dtype=torch.float32, device=dev),
+           "n": torch.zeros(1, dtype=torch.int32, device=dev)}
+
+    def call(c):
+        tail = (d_kp1.data_ptr(), d_kp2.data_ptr(), out["knn"].data_ptr(), out["good"].data_ptr(), out["xy1"].data_ptr(),
+                out["xy2"].data_ptr(), out["n"].data_ptr())
+        if entry == "f32":
+            c.bf_knn_l2_dev(d_q.data_ptr(), nq, d_t.data_ptr(), nt, dim, 2, out["knn"].data_ptr(), pm.api.PM_KNN_HINT_INTEGER)
+        elif entry == "ratio":
+            c.bf_knn_l2_ratio_dev(d_q.data_ptr(), nq, d_t.data_ptr(), nt, dim, pm.api.PM_KNN_HINT_INTEGER, 0.8, *tail)
+        elif entry == "u8":
+            c.bf_knn_l2_u8_dev(d_q.data_ptr(), nq, d_t.data_ptr(), nt, dim, 2, out["knn"].data_ptr())
+        else:
+            c.bf_knn_l2_u8_ratio_dev(d_q.data_ptr(), nq, d_t.data_ptr(), nt, dim, 0.8, *tail)
+
+    def result(c):
+        for v in out.values():
+            v.zero_()
+        call(c)
+        torch.cuda.synchronize()
+        n = int(out["n"][0])
+        return tuple(out[k].cpu().numpy()[:n if k in ("good", "xy1", "xy2") else None].tobytes() for k in ("knn", "good", "xy1", "xy2")) + (n,)
+
+    contexts = []
+    try:
+        for captured in (False, True):
+            c = pm.Context(0)
+            contexts.append(c)
+            c.set_stream(st.cuda_stream)
+            c.set_option(pm.api.PM_OPT_FILTER_FUSION, 2)         # the fused tail, where the entry point has one
+            if captured:
+                gc.collect()             # no finaliser of an earlier test's context (hipFree) inside the capture
+                g = torch.cuda.CUDAGraph()
+                with pytest.raises(pm.api.PmError) as err:
+                    with torch.cuda.graph(g, stream=st, capture_error_mode="relaxed"):
+                        call(c)
+                assert err.value.status == pm.api.PM_E_UNSUPPORTED and "capturing" in str(err.value)
+                del g
+                torch.cuda.set_stream(st)
+                assert result(c) == base
+            else:
+                base = result(c)
+                assert entry in ("f32", "u8") or base[4] > 0
+    finally:
+        torch.cuda.synchronize()
+        torch.cuda.set_stream(prev)
+        for c in contexts:
+            c.close()
