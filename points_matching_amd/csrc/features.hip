@@ -853,57 +853,44 @@ int detect_blocking(pm_ctx* ctx, const char* fn, const uint8_t* img, int w, int 
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t img_bytes = static_cast<size_t>(h) * stride;
     const size_t row_u8 = bits ? 32 : 128, row_f32 = bits ? 0 : 512;
-    uint8_t* d_img = nullptr;
-    char* d_out = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_img), img_bytes) != hipSuccess) {
-        pm::set_error("%s: hipMalloc of %zu bytes failed", fn, img_bytes);
-        return PM_E_NOMEM;
-    }
-    hipError_t e = hipMemcpy(d_img, img, img_bytes, hipMemcpyHostToDevice);          // blocking, like every copy of this form
-    if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
+    pm::StagedBlock image(ctx, fn);                      // lives across the rounds
+    const size_t o_img = image.add(img_bytes);
+    image.alloc();
+    image.upload(o_img, img, img_bytes);
+    rc = image.sync();
     size_t cap = default_capacity(ctx, max_kp);
     int32_t n = 0;
     // at most two rounds: the counter of an overflowed run is the exact need of the next (same image, same thresholds)
     for (int round = 0; rc == PM_OK && round < 3; ++round) {
         const size_t rows = std::min<size_t>(static_cast<size_t>(max_kp), cap);
-        const size_t o_kp = 256, o_u8 = o_kp + pm::align_up(rows * 8, 256), o_f32 = o_u8 + pm::align_up(rows * row_u8, 256);
-        const size_t o_meta = o_f32 + pm::align_up(rows * row_f32, 256), total = o_meta + pm::align_up(rows * 16, 256);
-        if (hipMalloc(reinterpret_cast<void**>(&d_out), total) != hipSuccess) {
-            pm::set_error("%s: hipMalloc of %zu bytes failed", fn, total);
-            rc = PM_E_NOMEM;
-            break;
-        }
-        rc = detect_enqueue(ctx, d_img, w, h, stride, max_kp, contrast, edge_r, cap, 0, bits, reinterpret_cast<float*>(d_out + o_kp),
-                            reinterpret_cast<uint8_t*>(d_out + o_u8), bits ? nullptr : reinterpret_cast<float*>(d_out + o_f32),
-                            reinterpret_cast<float*>(d_out + o_meta), reinterpret_cast<int32_t*>(d_out));
+        pm::StagedBlock b(ctx, fn);                      // this round's outputs
+        const size_t o_n = b.add(sizeof n), o_kp = b.add(rows * 8), o_u8 = b.add(rows * row_u8), o_f32 = b.add(rows * row_f32);
+        const size_t o_meta = b.add(rows * 16);
+        b.alloc();
+        if (b.rc == PM_OK)
+            b.rc = detect_enqueue(ctx, image.at<uint8_t>(o_img), w, h, stride, max_kp, contrast, edge_r, cap, 0, bits, b.at<float>(o_kp),
+                                  b.at<uint8_t>(o_u8), bits ? nullptr : b.at<float>(o_f32), b.at<float>(o_meta), b.at<int32_t>(o_n));
         unsigned need = 0;
-        if (rc == PM_OK) {
-            e = hipStreamSynchronize(ctx->stream);
-            if (e == hipSuccess) e = hipMemcpy(&n, d_out, sizeof n, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(&need, ctx->feat + ctx->feat_counter_off, sizeof need, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { pm::set_error("reading the counts failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-        }
+        b.download(&n, o_n, sizeof n);
+        if (b.rc == PM_OK)                               // the candidate counter lives in the context's feature buffer
+            b.step(hipMemcpyAsync(&need, ctx->feat + ctx->feat_counter_off, sizeof need, hipMemcpyDeviceToHost, ctx->stream), PM_E_HIP, "D2H copy");
+        rc = b.sync();
         if (rc == PM_OK && n >= 0) {
             const size_t m = static_cast<size_t>(n);
-            if (m) e = hipMemcpy(kp_xy, d_out + o_kp, m * 8, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess && desc_u8) e = hipMemcpy(desc_u8, d_out + o_u8, m * row_u8, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess && desc_f32) e = hipMemcpy(desc_f32, d_out + o_f32, m * row_f32, hipMemcpyDeviceToHost);
-            if (m && e == hipSuccess && meta) e = hipMemcpy(meta, d_out + o_meta, m * 16, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-            else *n_out = n;                                 // only once every row has arrived
+            b.download(kp_xy, o_kp, m * 8);
+            if (desc_u8) b.download(desc_u8, o_u8, m * row_u8);
+            if (desc_f32) b.download(desc_f32, o_f32, m * row_f32);
+            if (meta) b.download(meta, o_meta, m * 16);
+            rc = b.sync();
+            if (rc == PM_OK) *n_out = n;                     // only once every row has arrived
             break;
         }
-        (void)hipFree(d_out);
-        d_out = nullptr;
         if (rc == PM_OK) {
             if (need <= cap) { pm::set_error("%s: overflow reported without a larger need", fn); rc = PM_E_HIP; }
             cap = need;
         }
     }
     if (rc == PM_OK && n < 0) { pm::set_error("%s: the candidate buffer overflowed again after growing", fn); rc = PM_E_HIP; }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (d_out) (void)hipFree(d_out);
-    (void)hipFree(d_img);
     return rc;
 }
 

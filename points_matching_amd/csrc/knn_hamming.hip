@@ -751,7 +751,7 @@ extern "C" int pm_bf_knn_hamming_u8(pm_ctx* ctx, const uint8_t* q, int nq, const
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return pm::run_on_staged_rows(ctx, q, static_cast<size_t>(nq) * bytes, t, static_cast<size_t>(nt) * bytes, out,
+    return pm::StagedBlock::knn(ctx, __func__, q, static_cast<size_t>(nq) * bytes, t, static_cast<size_t>(nt) * bytes, out,
                                   sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
         return pm_bf_knn_hamming_u8_dev(ctx, static_cast<const uint8_t*>(dq), nq, static_cast<const uint8_t*>(dt), nt, bytes, k,
                                         static_cast<pm_match*>(dout));

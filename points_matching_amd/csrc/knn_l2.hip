@@ -1994,7 +1994,7 @@ extern "C" int pm_bf_knn_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return pm::run_on_staged_rows(ctx, q, static_cast<size_t>(nq) * dim, t, static_cast<size_t>(nt) * dim, out,
+    return pm::StagedBlock::knn(ctx, __func__, q, static_cast<size_t>(nq) * dim, t, static_cast<size_t>(nt) * dim, out,
                                   sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
         return pm_bf_knn_l2_u8_dev(ctx, static_cast<const uint8_t*>(dq), nq, static_cast<const uint8_t*>(dt), nt, dim, k,
                                    static_cast<pm_match*>(dout));
@@ -2011,7 +2011,7 @@ extern "C" int pm_bf_knn_l2_f32(pm_ctx* ctx, const float* q, int nq, const float
     PM_REQUIRE(nt == 0 || t, PM_E_INVALID, "null train pointer");
     if (nq == 0) return PM_OK;
     PM_HIP_CHECK(hipSetDevice(ctx->device));
-    return pm::run_on_staged_rows(ctx, q, sizeof(float) * static_cast<size_t>(nq) * dim, t, sizeof(float) * static_cast<size_t>(nt) * dim,
+    return pm::StagedBlock::knn(ctx, __func__, q, sizeof(float) * static_cast<size_t>(nq) * dim, t, sizeof(float) * static_cast<size_t>(nt) * dim,
                                   out, sizeof(pm_match) * static_cast<size_t>(nq) * k, [&](void* dq, void* dt, void* dout) {
         return pm_bf_knn_l2_f32_dev(ctx, static_cast<const float*>(dq), nq, static_cast<const float*>(dt), nt, dim, k, flags,
                                     static_cast<pm_match*>(dout));

@@ -59,34 +59,22 @@ int cross_host(pm_ctx* ctx, const void* q, int nq, const void* t, int nt, size_t
     const size_t qb = static_cast<size_t>(nq) * row_bytes, tb = static_cast<size_t>(nt) * row_bytes;
     const size_t fb = sizeof(pm_match) * static_cast<size_t>(nq) * kf, rb = sizeof(pm_match) * static_cast<size_t>(nt) * kr;
     const size_t gb = sizeof(pm_match) * static_cast<size_t>(nq);
-    // one allocation: [q | t | fwd | rev | good | count], each block 256-byte aligned
-    const size_t o_t = pm::align_up(qb, 256), o_f = o_t + pm::align_up(tb, 256), o_r = o_f + pm::align_up(fb, 256);
-    const size_t o_g = o_r + pm::align_up(rb, 256), o_n = o_g + pm::align_up(gb, 256);
-    char* base = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&base), o_n + 256) != hipSuccess) {
-        pm::set_error("%s: hipMalloc of %zu bytes failed", __func__, o_n + 256);
-        return PM_E_NOMEM;
-    }
-    int rc = PM_OK;
+    pm::StagedBlock b(ctx, __func__);
+    const size_t o_q = b.add(qb), o_t = b.add(tb), o_f = b.add(fb), o_r = b.add(rb), o_g = b.add(gb), o_n = b.add(sizeof(int32_t));
+    int rc = b.alloc();
+    if (rc != PM_OK) return rc;
+    *n_out = 0;                                          // on every failure from here on; n once the rows have arrived
+    b.upload(o_q, q, qb);
+    b.upload(o_t, t, tb);
+    if (b.rc == PM_OK) b.rc = dev(b.at<void>(o_q), b.at<void>(o_t), b.at<pm_match>(o_f), b.at<pm_match>(o_r), b.at<pm_match>(o_g), b.at<int32_t>(o_n));
     int32_t n = 0;
-    hipError_t e = hipSuccess;
-    if (qb) e = hipMemcpyAsync(base, q, qb, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && tb) e = hipMemcpyAsync(base + o_t, t, tb, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    if (rc == PM_OK)
-        rc = dev(base, base + o_t, reinterpret_cast<pm_match*>(base + o_f), reinterpret_cast<pm_match*>(base + o_r),
-                 reinterpret_cast<pm_match*>(base + o_g), reinterpret_cast<int32_t*>(base + o_n));
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(&n, base + o_n, sizeof n, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess && (n < 0 || n > nq)) { pm::set_error("survivor count %d outside [0, %d]", n, nq); rc = PM_E_HIP; }
-        else if (e == hipSuccess && n > 0) e = hipMemcpy(out, base + o_g, sizeof(pm_match) * static_cast<size_t>(n), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(base);
-    *n_out = rc == PM_OK ? n : 0;
+    b.download(&n, o_n, sizeof n);
+    rc = b.sync();                                       // the stream is idle from here to the next download
+    if (rc != PM_OK) return rc;
+    if (n < 0 || n > nq) { pm::set_error("%s: survivor count %d outside [0, %d]", __func__, n, nq); return PM_E_HIP; }
+    b.download(out, o_g, sizeof(pm_match) * static_cast<size_t>(n));
+    rc = b.sync();
+    if (rc == PM_OK) *n_out = n;
     return rc;
 }
 

@@ -38,36 +38,21 @@ int guided_host(pm_ctx* ctx, const void* q, int nq, const void* t, int nt, size_
     const size_t qb = static_cast<size_t>(nq) * row_bytes, tb = static_cast<size_t>(nt) * row_bytes;
     const size_t k1b = sizeof(float) * 2 * static_cast<size_t>(nq), k2b = sizeof(float) * 2 * static_cast<size_t>(nt);
     const size_t ob = sizeof(pm_match) * static_cast<size_t>(nq) * k, nb = sizeof(int32_t) * static_cast<size_t>(nq);
-    const size_t o_t = pm::align_up(qb, 256), o_k1 = o_t + pm::align_up(tb, 256), o_k2 = o_k1 + pm::align_up(k1b, 256);
-    const size_t o_m = o_k2 + pm::align_up(k2b, 256), o_o = o_m + 256, o_n = o_o + pm::align_up(ob, 256);
-    const size_t total = o_n + pm::align_up(nb, 256) + 256;
-    char* base = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&base), total) != hipSuccess) {
-        pm::set_error("%s: hipMalloc of %zu bytes failed", __func__, total);
-        return PM_E_NOMEM;
-    }
-    int rc = PM_OK;
-    hipError_t e = hipMemcpyAsync(base + o_m, M, 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && qb) e = hipMemcpyAsync(base, q, qb, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && tb) e = hipMemcpyAsync(base + o_t, t, tb, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && k1b) e = hipMemcpyAsync(base + o_k1, kp1, k1b, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && k2b) e = hipMemcpyAsync(base + o_k2, kp2, k2b, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) { pm::set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    if (rc == PM_OK)
-        rc = dev(base, base + o_t, reinterpret_cast<const float*>(base + o_k1), reinterpret_cast<const float*>(base + o_k2),
-                 reinterpret_cast<const double*>(base + o_m), reinterpret_cast<pm_match*>(base + o_o),
-                 reinterpret_cast<int32_t*>(base + o_n));
-    if (rc == PM_OK && nq > 0) {
-        e = hipMemcpyAsync(out, base + o_o, ob, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && n_admitted) e = hipMemcpyAsync(n_admitted, base + o_n, nb, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { pm::set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PM_OK) {
-        pm::set_error("%s: stream synchronisation failed", __func__);
-        rc = PM_E_HIP;
-    }
-    (void)hipFree(base);
-    return rc;
+    pm::StagedBlock b(ctx, __func__);
+    const size_t o_q = b.add(qb), o_t = b.add(tb), o_k1 = b.add(k1b), o_k2 = b.add(k2b), o_m = b.add(9 * sizeof(double));
+    const size_t o_o = b.add(ob), o_n = b.add(nb);
+    b.alloc();
+    b.upload(o_m, M, 9 * sizeof(double));
+    b.upload(o_q, q, qb);
+    b.upload(o_t, t, tb);
+    b.upload(o_k1, kp1, k1b);
+    b.upload(o_k2, kp2, k2b);
+    if (b.rc == PM_OK)
+        b.rc = dev(b.at<void>(o_q), b.at<void>(o_t), b.at<float>(o_k1), b.at<float>(o_k2), b.at<double>(o_m), b.at<pm_match>(o_o),
+                   b.at<int32_t>(o_n));
+    b.download(out, o_o, ob);                            // nothing for nq == 0
+    if (n_admitted) b.download(n_admitted, o_n, nb);
+    return b.sync();
 }
 
 }  // namespace

@@ -59,32 +59,39 @@ int pinned_reserve(pm_ctx* ctx, size_t bytes)
     return PM_OK;
 }
 
-int run_on_staged_rows(pm_ctx* ctx, const void* q, size_t q_bytes, const void* t, size_t t_bytes, void* out, size_t out_bytes,
-                       const std::function<int(void* d_q, void* d_t, void* d_out)>& run)
+void StagedBlock::step(hipError_t e, int status, const char* what)
 {
-    void *dq = nullptr, *dt = nullptr, *dout = nullptr;
-    int rc = PM_OK;
-    hipError_t e = hipMalloc(&dq, q_bytes);
-    if (e == hipSuccess) e = hipMalloc(&dt, t_bytes ? t_bytes : 16);
-    if (e == hipSuccess) e = hipMalloc(&dout, out_bytes);
-    if (e != hipSuccess) { set_error("hipMalloc failed: %s", hipGetErrorString(e)); rc = PM_E_NOMEM; }
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(dq, q, q_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && t_bytes) e = hipMemcpyAsync(dt, t, t_bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { set_error("H2D copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    }
-    if (rc == PM_OK) rc = run(dq, dt, dout);
-    if (rc == PM_OK) {
-        e = hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { set_error("D2H copy failed: %s", hipGetErrorString(e)); rc = PM_E_HIP; }
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    (void)hipFree(dq);
-    (void)hipFree(dt);
-    (void)hipFree(dout);
+    if (e == hipSuccess || rc != PM_OK) return;
+    set_error("%s: %s failed (staged block of %zu bytes): %s", who, what, total, hipGetErrorString(e));
+    rc = status;
+}
+
+int StagedBlock::alloc()
+{
+    step(hipMalloc(reinterpret_cast<void**>(&base), total), PM_E_NOMEM, "hipMalloc");
     return rc;
+}
+
+void StagedBlock::upload(size_t off, const void* src, size_t bytes)
+{
+    if (rc == PM_OK && bytes) step(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, ctx->stream), PM_E_HIP, "H2D copy");
+}
+
+void StagedBlock::download(void* dst, size_t off, size_t bytes)
+{
+    if (rc == PM_OK && bytes) step(hipMemcpyAsync(dst, base + off, bytes, hipMemcpyDeviceToHost, ctx->stream), PM_E_HIP, "D2H copy");
+}
+
+int StagedBlock::sync()
+{
+    step(hipStreamSynchronize(ctx->stream), PM_E_HIP, "synchronise");
+    return rc;
+}
+
+StagedBlock::~StagedBlock()
+{
+    if (rc != PM_OK) (void)hipStreamSynchronize(ctx->stream);       // a caller that succeeded left through sync()
+    if (base) (void)hipFree(base);
 }
 
 ScopedKernelTime::ScopedKernelTime(pm_ctx* c, const char* n) : ctx(c), name(n)

@@ -7,12 +7,12 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "pm.h"
+#include "stage_layout.hpp"
 
 namespace pm {
 
@@ -109,12 +109,39 @@ int arena_reserve(pm_ctx* ctx, size_t bytes);          // ensure capacity (may s
 void arena_reset(pm_ctx* ctx);
 void* arena_take(pm_ctx* ctx, size_t bytes);            // 256-B aligned carve; nullptr if over cap
 int pinned_reserve(pm_ctx* ctx, size_t bytes);
-// Host-pointer form of a matcher around its _dev form: device buffers for the two row sets and the result, the rows
-// copied in, run(d_q, d_t, d_out), the result copied out, the stream synchronised, the buffers freed.  (Hidden: the
-// library's dynamic symbol table stays as it was.)
-__attribute__((visibility("hidden")))
-int run_on_staged_rows(pm_ctx* ctx, const void* q, size_t q_bytes, const void* t, size_t t_bytes, void* out, size_t out_bytes,
-                       const std::function<int(void* d_q, void* d_t, void* d_out)>& run);
+// The private device block of a host-pointer entry point around its _dev form (the _dev form resets the arena, so the
+// staged rows cannot live there): add() the parts, alloc(), upload(), rc = the _dev form, download(), sync().  The first
+// failing step sets the status and the message and every later step is skipped.  A caller that succeeded leaves through
+// sync(); after a failure the destructor synchronises the stream before it frees.  (Hidden: the dynamic symbol table stays.)
+struct __attribute__((visibility("hidden"))) StagedBlock : StageLayout {
+    pm_ctx* ctx;
+    const char* who;                                             // the caller's name, for the messages
+    char* base = nullptr;
+    int rc = PM_OK;                                              // the first failure so far
+    StagedBlock(pm_ctx* c, const char* w) : ctx(c), who(w) {}
+    StagedBlock(const StagedBlock&) = delete;
+    ~StagedBlock();
+    int alloc();                                                 // one hipMalloc of `total` bytes; PM_E_NOMEM
+    void upload(size_t off, const void* src, size_t bytes);      // both on ctx->stream, nothing for 0 bytes; PM_E_HIP
+    void download(void* dst, size_t off, size_t bytes);
+    int sync();                                                  // synchronises the stream; returns rc
+    template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+    void step(hipError_t e, int status, const char* what);
+    // A plain matcher's whole sequence around dev(d_q, d_t, d_out).  Three blocks, not one: freeing a device block of 2 MiB
+    // or more costs ~220 us, below that under 1 us (profiles/host_stage_timing.json), and 1 MiB row sets are an everyday shape.
+    template <class Dev> static int knn(pm_ctx* ctx, const char* who, const void* q, size_t qb, const void* t, size_t tb, void* out, size_t ob, Dev dev)
+    {
+        StagedBlock bq(ctx, who), bt(ctx, who), bo(ctx, who);       // destroyed bo, bt, bq: the one that failed synchronises before bq, bt go
+        const size_t o_q = bq.add(qb), o_t = bt.add(tb), o_out = bo.add(ob);
+        if (bq.alloc() != PM_OK || bt.alloc() != PM_OK || bo.alloc() != PM_OK) return PM_E_NOMEM;
+        bq.upload(o_q, q, qb);
+        if (bq.rc == PM_OK) bt.upload(o_t, t, tb);
+        if (bq.rc != PM_OK || bt.rc != PM_OK) return PM_E_HIP;
+        bo.rc = dev(bq.base, bt.base, bo.base);
+        bo.download(out, o_out, ob);
+        return bo.sync();
+    }
+};
 
 // RAII event bracket: records start/stop on ctx->stream when timing is on.
 struct ScopedKernelTime {

@@ -521,42 +521,27 @@ extern "C" int pm_track_lk(pm_ctx* ctx, const uint8_t* img1, const uint8_t* img2
     pm_pyramid *pa = nullptr, *pb = nullptr;
     rc = pm_pyramid_create(ctx, w, h, p->max_level, &pa);
     if (rc == PM_OK) rc = pm_pyramid_create(ctx, w, h, p->max_level, &pb);
-    // one block: the two images, points, initial points, out, err, fb, status
-    const size_t img_b = pm::align_up(static_cast<size_t>(h) * stride, 256), xy_b = pm::align_up(static_cast<size_t>(n) * 8, 256);
-    const size_t f_b = pm::align_up(static_cast<size_t>(n) * 4, 256), s_b = pm::align_up(static_cast<size_t>(n), 256);
-    const size_t o_pts = 2 * img_b, o_init = o_pts + xy_b, o_out = o_init + xy_b, o_err = o_out + xy_b, o_fb = o_err + f_b, o_st = o_fb + f_b;
-    char* d = nullptr;
-    if (rc == PM_OK && hipMalloc(reinterpret_cast<void**>(&d), o_st + s_b) != hipSuccess) {
-        pm::set_error("pm_track_lk: hipMalloc of %zu bytes failed", o_st + s_b);
-        rc = PM_E_NOMEM;
+    if (rc == PM_OK) {                                   // the block is freed before the pyramids are destroyed
+        const size_t img_b = static_cast<size_t>(h) * stride, xy_b = static_cast<size_t>(n) * 8, f_b = static_cast<size_t>(n) * 4;
+        pm::StagedBlock b(ctx, __func__);
+        const size_t o_1 = b.add(img_b), o_2 = b.add(img_b), o_pts = b.add(xy_b), o_init = b.add(xy_b), o_out = b.add(xy_b);
+        const size_t o_err = b.add(f_b), o_fb = b.add(f_b), o_st = b.add(static_cast<size_t>(n));
+        b.alloc();
+        b.upload(o_1, img1, img_b);
+        b.upload(o_2, img2, img_b);
+        b.upload(o_pts, pts, xy_b);
+        if (init) b.upload(o_init, init, xy_b);
+        if (b.rc == PM_OK) b.rc = build_enqueue(ctx, pa, b.at<uint8_t>(o_1), stride);
+        if (b.rc == PM_OK) b.rc = build_enqueue(ctx, pb, b.at<uint8_t>(o_2), stride);
+        if (b.rc == PM_OK)
+            b.rc = pm_track_lk_dev(ctx, pa, pb, b.at<float>(o_pts), nullptr, n, init ? b.at<float>(o_init) : nullptr, p, b.at<float>(o_out),
+                                   b.at<uint8_t>(o_st), b.at<float>(o_err), b.at<float>(o_fb));
+        b.download(out, o_out, xy_b);
+        b.download(status, o_st, static_cast<size_t>(n));
+        if (err) b.download(err, o_err, f_b);
+        if (fb) b.download(fb, o_fb, f_b);
+        rc = b.sync();
     }
-    auto step = [&](hipError_t e, const char* what) {
-        if (rc == PM_OK && e != hipSuccess) {
-            pm::set_error("pm_track_lk: %s failed: %s", what, hipGetErrorString(e));
-            rc = PM_E_HIP;
-        }
-    };
-    if (rc == PM_OK) {                                   // blocking copies, like every host form
-        step(hipMemcpy(d, img1, static_cast<size_t>(h) * stride, hipMemcpyHostToDevice), "H2D copy");
-        step(hipMemcpy(d + img_b, img2, static_cast<size_t>(h) * stride, hipMemcpyHostToDevice), "H2D copy");
-        step(hipMemcpy(d + o_pts, pts, static_cast<size_t>(n) * 8, hipMemcpyHostToDevice), "H2D copy");
-        if (init) step(hipMemcpy(d + o_init, init, static_cast<size_t>(n) * 8, hipMemcpyHostToDevice), "H2D copy");
-    }
-    if (rc == PM_OK) rc = build_enqueue(ctx, pa, reinterpret_cast<const uint8_t*>(d), stride);
-    if (rc == PM_OK) rc = build_enqueue(ctx, pb, reinterpret_cast<const uint8_t*>(d + img_b), stride);
-    if (rc == PM_OK) {
-        track_enqueue(ctx, pa, pb, reinterpret_cast<const float*>(d + o_pts), nullptr, n, init ? reinterpret_cast<const float*>(d + o_init) : nullptr,
-                      p, reinterpret_cast<float*>(d + o_out), reinterpret_cast<uint8_t*>(d + o_st), reinterpret_cast<float*>(d + o_err),
-                      reinterpret_cast<float*>(d + o_fb));
-        step(hipGetLastError(), "launch");
-        step(hipStreamSynchronize(ctx->stream), "synchronise");
-        step(hipMemcpy(out, d + o_out, static_cast<size_t>(n) * 8, hipMemcpyDeviceToHost), "D2H copy");
-        step(hipMemcpy(status, d + o_st, static_cast<size_t>(n), hipMemcpyDeviceToHost), "D2H copy");
-        if (err) step(hipMemcpy(err, d + o_err, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost), "D2H copy");
-        if (fb) step(hipMemcpy(fb, d + o_fb, static_cast<size_t>(n) * 4, hipMemcpyDeviceToHost), "D2H copy");
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    if (d) (void)hipFree(d);
     (void)pm_pyramid_destroy(pa);
     (void)pm_pyramid_destroy(pb);
     return rc;
