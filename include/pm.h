@@ -1092,6 +1092,59 @@ int pm_track_lk_gather_dev(pm_ctx* ctx, const pm_pyramid* prev, const pm_pyramid
 int pm_track_lk(pm_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int w, int h, int stride, const float* pts, int n,
                 const float* init, const pm_lk_params* p, float* out, uint8_t* status, float* err, float* fb);
 
+/* ---- corners to start and replenish tracks: minimum-eigenvalue (Shi-Tomasi) detection — docs/SPEC.md S67-S70 ---------------
+ * The point source of the tracking route (cv::goodFeaturesToTrack with a mask): the strongest corners of level 0 of a built
+ * pm_pyramid that keep a minimum distance from each other and from an existing point set.  No scale space, no descriptors.
+ * The score of a pixel is the smaller eigenvalue of the gradient matrix over its (2r+1)^2 block, from exact integer sums, in
+ * the unit of pm_lk_params.min_eig: at an integer pixel it is bit for bit the value the tracker tests against min_eig at
+ * level 0 for win_radius == block_radius, and the region searched (r+1 <= x <= w-r-3, likewise y) is exactly the set of
+ * integer points whose tracking template stays inside level 0.  A corner found with min_eig = m therefore never comes back
+ * from pm_track_lk* with status 3 at that radius and min_eig <= m.  Candidates are strict 3 x 3 maxima of the score (S68),
+ * ranked by score, ties in scan order (S69), cut at quality * the best score, and taken greedily while no keep point and no
+ * corner taken before lies nearer than min_dist (S70).  The result is a function of the image, the keep points and the
+ * parameters alone (bit for bit the plain-C statement tests/corner_ref.c).
+ *   pm_corners_dev   d_keep: cap_keep x 2 float obstacles at any position (NULL with cap_keep 0); d_n_keep: device int32
+ *             count, clamped to [0, cap_keep], NULL = cap_keep.  A non-finite keep point blocks nothing.  Writes at most
+ *             max_corners rows of d_xy (x, y as floats, integer valued), d_score (may be NULL) and *d_n, in order of
+ *             acceptance.  Enqueues three launches on the context's stream and does not synchronise; scratch comes from the
+ *             context's arena, which may grow on the first call or with a larger capacity (one stream synchronisation).
+ *   pm_corners_replenish_dev   the video-loop form, in place: n = *d_count clamped to [0, cap]; rows [0, n) of d_pts are the
+ *             obstacles; up to min(target, cap) - n corners are appended at rows n .. and *d_count becomes n + m; *d_n_new
+ *             (may be NULL) = m; d_score (may be NULL) holds cap floats and is written at the new rows only.  Chains after
+ *             pm_track_lk_gather_dev (its d_xy2, d_count) with no host round trip, and gives the rows pm_corners_dev gives
+ *             with keep = d_pts[0 .. n).
+ *   pm_corners   the blocking host form: builds level 0 only and frees what it allocated (images below 16 pixels a side are
+ *             PM_E_UNSUPPORTED, as for pm_pyramid_create).
+ * Overflow: when more candidates pass S68 than the capacity, the _dev forms write *d_n = -1 (replenish: *d_n_new = -1, *d_count
+ * unchanged) and no rows, never a subset; pm_corners grows the capacity and runs again by itself.  In the replenish form
+ * *d_n_new is the ONLY overflow signal: with d_n_new == NULL an overflow cannot be told from "no corner found", so a caller
+ * that does not size the capacity for its frames passes the pointer.
+ * Cost: the ranking counts smaller keys, so its work grows with the SQUARE of the candidate count (the selection's with
+ * candidates x accepted corners).  A few thousand candidates, the case of a real frame with a sensible min_eig, cost tens of
+ * microseconds; a large noisy frame with min_eig near 0 can produce millions, and a capacity near its ceiling of 2^24 then
+ * admits a launch of ~1e14 key comparisons, minutes on the device.  Keep min_eig above the noise floor and the capacity near
+ * the default; pm_corners grows the capacity to the exact need, whatever it is.  Scaling with the candidate count has not
+ * been measured.
+ * PM_E_INVALID: null required pointers, a parameter out of range, flags or reserved != 0, max_corners, cap, cap_keep, n_keep
+ * or target < 0, a pyramid of another device.  PM_E_UNSUPPORTED: max_corners == 0, cap == 0 in the replenish form, and a
+ * capturing stream (refused before anything is allocated or launched).  An empty search region gives 0 corners and PM_OK.
+ * Timing names: "corner_extrema", "corner_rank", "corner_select". */
+typedef struct pm_corner_params {
+    int32_t block_radius;  /* 1 .. 15 (OpenCV's blockSize 3 is 1; use the tracker's win_radius to share its eigenvalue) */
+    float   min_eig;       /* finite, >= 0: absolute floor, the unit of pm_lk_params.min_eig */
+    float   quality;       /* 0 .. 1: relative floor against the strongest candidate (OpenCV's qualityLevel); 0 = off */
+    float   min_dist;      /* finite, 0 .. 1e6, pixels */
+    int32_t capacity;      /* candidate capacity of a run; 0 = max(65536, 8 * max_corners); else 1 .. 2^24 */
+    int32_t flags;         /* 0 */
+    int32_t reserved[2];   /* 0 */
+} pm_corner_params;
+int pm_corners_dev(pm_ctx* ctx, const pm_pyramid* pyr, const pm_corner_params* p, const float* d_keep, const int32_t* d_n_keep,
+                   int cap_keep, int max_corners, float* d_xy, float* d_score, int32_t* d_n);
+int pm_corners_replenish_dev(pm_ctx* ctx, const pm_pyramid* pyr, const pm_corner_params* p, float* d_pts, int32_t* d_count,
+                             int cap, int target, float* d_score, int32_t* d_n_new);
+int pm_corners(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, const pm_corner_params* p, const float* keep, int n_keep,
+               int max_corners, float* xy, float* score, int32_t* n_out);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

@@ -76,6 +76,7 @@ EXPORTS = [
     "pm_detect_describe_bits_dev", "pm_detect_describe_bits", "pm_detect_bits_table",
     "pm_pyramid_create", "pm_pyramid_destroy", "pm_pyramid_build_dev", "pm_pyramid_level_get",
     "pm_track_lk_dev", "pm_track_lk_gather_dev", "pm_track_lk",
+    "pm_corners_dev", "pm_corners_replenish_dev", "pm_corners",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -108,6 +109,17 @@ PM_LK_USE_INITIAL = 1
 
 def lk_params(win_radius=10, max_level=3, max_iters=30, eps=0.01, min_eig=1e-4, fb_thresh=0.0, flags=0):
     return LkParams(win_radius, max_level, max_iters, eps, min_eig, fb_thresh, flags, 0)
+
+
+class CornerParams(C.Structure):
+    """pm_corner_params (include/pm.h, SPEC S67-S70); corner_params() fills it."""
+    _fields_ = [("block_radius", C.c_int32), ("min_eig", C.c_float), ("quality", C.c_float), ("min_dist", C.c_float),
+                ("capacity", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def corner_params(block_radius=10, min_eig=1e-4, quality=0.01, min_dist=8.0, capacity=0):
+    """block_radius: use the tracker's win_radius to share its eigenvalue; quality, min_dist: OpenCV's qualityLevel, minDistance."""
+    return CornerParams(block_radius, min_eig, quality, min_dist, capacity, 0, (C.c_int32 * 2)(0, 0))
 
 
 class Camera(C.Structure):
@@ -664,6 +676,36 @@ class Context:
         _check(lib().pm_track_lk(self._h, _p(img1), _p(img2), w, h, w, _p(pts), n, _p(init), C.byref(prm), _p(out), _p(status),
                                  _p(err), _p(fb)))
         return out[:n], status[:n], err[:n], fb[:n]
+
+    # -- corners to start and replenish tracks (cv::goodFeaturesToTrack with a mask; SPEC S67-S70) -------------------------
+    def corners_dev(self, pyr, prm, max_corners, dxy_ptr, dn_ptr, dscore_ptr=None, dkeep_ptr=None, dn_keep_ptr=None, cap_keep=0):
+        """Device pointers; pyr: a built Pyramid (level 0 is read); prm: CornerParams.  dkeep_ptr: cap_keep x 2 float obstacles,
+        dn_keep_ptr their device int32 count (None = cap_keep).  *dn = the number of rows written, -1 on overflow."""
+        _check(lib().pm_corners_dev(self._h, pyr._h, C.byref(prm), C.c_void_p(dkeep_ptr or 0), C.c_void_p(dn_keep_ptr or 0), cap_keep,
+                                    max_corners, C.c_void_p(dxy_ptr), C.c_void_p(dscore_ptr or 0), C.c_void_p(dn_ptr)))
+
+    def corners_replenish_dev(self, pyr, prm, dpts_ptr, dcount_ptr, cap, target, dscore_ptr=None, dn_new_ptr=None):
+        """In place: rows [0, *dcount) of dpts are the obstacles; corners are appended until min(target, cap) rows."""
+        _check(lib().pm_corners_replenish_dev(self._h, pyr._h, C.byref(prm), C.c_void_p(dpts_ptr), C.c_void_p(dcount_ptr), cap, target,
+                                              C.c_void_p(dscore_ptr or 0), C.c_void_p(dn_new_ptr or 0)))
+
+    def corners(self, img, max_corners=1000, prm=None, keep=None, w=None):
+        """Host form: 8-bit grey image (h, w), keep points (n, 2) -> (xy (m, 2) f32, score (m,) f32).  With w given, img holds
+        h rows of img.shape[1] >= w bytes (a row stride) and only the first w columns are the image."""
+        img = np.ascontiguousarray(img, np.uint8)
+        if img.ndim != 2:
+            raise ValueError("img must be a 2-D array")
+        h = img.shape[0]
+        w = img.shape[1] if w is None else w
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, np.float32).reshape(-1, 2)
+        n_keep = 0 if keep is None else keep.shape[0]
+        prm = prm or corner_params()
+        rows = max(max_corners, 1)
+        xy, score, n = np.zeros((rows, 2), np.float32), np.zeros(rows, np.float32), C.c_int32()
+        _check(lib().pm_corners(self._h, _p(img), w, h, img.shape[1], C.byref(prm), _p(keep) if n_keep else None, n_keep, max_corners,
+                                _p(xy), _p(score), C.byref(n)))
+        return xy[:n.value].copy(), score[:n.value].copy()
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

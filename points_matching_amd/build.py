@@ -20,7 +20,8 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "ransac_h_fused.hip", "homography_refine.hip", "ransac_a_fused.hip", "affine_refine.hip",
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
-           "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip"]
+           "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
+           "corners.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -45,7 +46,10 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # feature front end (S53-S57): the descriptor kernel keeps its records in LDS and must not spill
          "features.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # Lucas-Kanade tracking (S61-S66): one wave per point with three int16 planes in LDS; lk_track must not spill
-         "track_lk.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "track_lk.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # Shi-Tomasi corners (S67-S70): corner_extrema holds 60 KiB of LDS planes, corner_select 8 conflict words per thread;
+         # neither may use scratch or spill
+         "corners.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

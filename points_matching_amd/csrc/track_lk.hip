@@ -14,15 +14,7 @@
 #include <algorithm>
 
 #include "pm_common.hpp"
-
-struct pm_pyramid {
-    int device = 0;
-    int w = 0, h = 0, nlev = 0;
-    int lw[8] = {}, lh[8] = {};
-    size_t off[8] = {};                // first byte of each level's tight plane
-    size_t bytes = 0;
-    uint8_t* mem = nullptr;
-};
+#include "pyramid.hpp"
 
 namespace {
 

@@ -11,7 +11,8 @@
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
 //          [--guided TAU] [--features host|device] [--descriptor grad|bits]
-//          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]]
+//          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]
+//                           [--points dog|corners [--corner-dist D] [--corner-quality Q] [--corner-min-eig M]]]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -38,6 +39,11 @@
 // the rest of the output is as before (a match record holds the keypoint's row as queryIdx, its row among the survivors as
 // trainIdx and distance 0).  --lk-radius (default 10), --lk-levels (3), --lk-fb (forward-backward threshold in pixels,
 // default 0 = off).  Host features, --descriptor bits, --filter, --guided, --gpus / --mgpu are usage errors with it.
+// --points corners (with --matcher track; default dog = the detector above): image 1's points are minimum-eigenvalue corners
+// (docs/SPEC.md S67-S70, pm_corners_dev on the first pyramid, block radius = --lk-radius, at most --max-kp of them) in place
+// of the DoG keypoints: no scale space and no descriptors are computed (pm_detect_describe_dev is not called).
+// --corner-dist (minimum distance in pixels, default 8), --corner-quality (relative floor, default 0.01), --corner-min-eig
+// (absolute floor, default 1e-4, the tracker's).  The report keeps its fields: n1 = corners found, n2 = 0.
 // --filter cross: mutual nearest neighbours (cv::BFMatcher crossCheck = true, docs/SPEC.md S41-S42): forward and reverse
 // matcher pass + the fused filter in one call; cross-ratio adds the ratio test (--ratio) on the forward row.  Brute-force
 // matcher on one GPU only (float and binary descriptors): with --matcher flann or --gpus / --mgpu it is a usage error.
@@ -197,6 +203,9 @@ int main(int argc, char** argv)
     bool extract_only = false, filter_given = false;
     int lk_radius = 10, lk_levels = 3;
     float lk_fb = 0.f;
+    std::string points = "dog";
+    bool points_given = false, corner_opt_given = false;
+    float corner_dist = 8.f, corner_quality = 0.01f, corner_min_eig = 1e-4f;
     int max_kp = 4000;
     bool quiet = false, json = false, iters_given = false, print_epi = false, force_mgpu = false;
     for (int i = 1; i < argc; ++i) {
@@ -213,6 +222,10 @@ int main(int argc, char** argv)
         else if (a == "--lk-radius") lk_radius = atoi(val("--lk-radius"));
         else if (a == "--lk-levels") lk_levels = atoi(val("--lk-levels"));
         else if (a == "--lk-fb") lk_fb = strtof(val("--lk-fb"), nullptr);
+        else if (a == "--points") { points = val("--points"); points_given = true; }
+        else if (a == "--corner-dist") { corner_dist = strtof(val("--corner-dist"), nullptr); corner_opt_given = true; }
+        else if (a == "--corner-quality") { corner_quality = strtof(val("--corner-quality"), nullptr); corner_opt_given = true; }
+        else if (a == "--corner-min-eig") { corner_min_eig = strtof(val("--corner-min-eig"), nullptr); corner_opt_given = true; }
         else if (a == "--ratio") ratio = strtof(val("--ratio"), nullptr);
         else if (a == "--iters") { iters = strtol(val("--iters"), nullptr, 0); iters_given = true; }
         else if (a == "--guided") { guided_tau = strtof(val("--guided"), nullptr); guided = true; }
@@ -262,7 +275,18 @@ int main(int argc, char** argv)
         fprintf(stderr, "pm_cli: --lk-radius 2..15, --lk-levels 0..7, --lk-fb >= 0\n");
         return 2;
     }
+    const bool corner_points = points == "corners";
+    if ((points_given || corner_opt_given) && (!track || (points != "dog" && !corner_points) || (corner_opt_given && !corner_points))) {
+        fprintf(stderr, "pm_cli: --points dog|corners needs --matcher track, and the --corner-* options need --points corners\n");
+        return 2;
+    }
+    if (corner_points && (!(corner_dist >= 0.f) || !(corner_dist <= 1e6f) || !(corner_quality >= 0.f) || !(corner_quality <= 1.f) ||
+                          !(corner_min_eig >= 0.f) || !(corner_min_eig <= 3.0e38f))) {
+        fprintf(stderr, "pm_cli: --corner-dist 0..1e6, --corner-quality 0..1, --corner-min-eig >= 0\n");
+        return 2;
+    }
     int img_w[2] = {0, 0}, img_h[2] = {0, 0};
+    pm_pyramid* corner_pyr = nullptr;                 // --points corners: the first frame's pyramid, built before the corners are found
     pm_ctx* feat_ctx = nullptr;                       // --features device: the context that extracted, reused by the matcher
     void* dev_img[2] = {nullptr, nullptr};
     void* dev_kp[2] = {nullptr, nullptr};
@@ -271,6 +295,8 @@ int main(int argc, char** argv)
     void* dev_n[2] = {nullptr, nullptr};
     auto free_device_features = [&]() {               // the device buffers of --features device, then their context
         if (!feat_ctx) return;
+        pm_pyramid_destroy(corner_pyr);
+        corner_pyr = nullptr;
         for (int i = 0; i < 2; ++i)
             for (void** p : {&dev_img[i], &dev_kp[i], &dev_u8[i], &dev_f32[i], &dev_n[i]}) { pm_device_free(feat_ctx, *p); *p = nullptr; }
         pm_ctx_destroy(feat_ctx);
@@ -304,6 +330,37 @@ int main(int argc, char** argv)
                 int r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
                 if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
                 if (r != PM_OK) return fail("device buffers", r);
+            } else if (track && corner_points) {
+                // ---- upload, build the pyramid the tracker will use, find the corners on its level 0; no descriptors
+                int r = pm_ctx_create(device, &feat_ctx);
+                if (r != PM_OK) return fail("pm_ctx_create", r);
+                r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, static_cast<size_t>(max_kp) * 8, &dev_kp[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, 4, &dev_n[i]);
+                if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
+                if (r != PM_OK) return fail("device buffers", r);
+                r = pm_pyramid_create(feat_ctx, im.w, im.h, lk_levels, &corner_pyr);
+                if (r == PM_OK) r = pm_pyramid_build_dev(feat_ctx, corner_pyr, static_cast<const uint8_t*>(dev_img[i]), im.w);
+                if (r != PM_OK) return fail("pyramid of image 1", r);
+                pm_corner_params cp;
+                cp.block_radius = lk_radius; cp.min_eig = corner_min_eig; cp.quality = corner_quality; cp.min_dist = corner_dist;
+                cp.capacity = 0; cp.flags = 0; cp.reserved[0] = cp.reserved[1] = 0;
+                int32_t n = -1;
+                while (n < 0) {
+                    r = pm_corners_dev(feat_ctx, corner_pyr, &cp, nullptr, nullptr, 0, max_kp, static_cast<float*>(dev_kp[i]), nullptr,
+                                       static_cast<int32_t*>(dev_n[i]));
+                    if (r == PM_OK) r = pm_device_download(feat_ctx, &n, dev_n[i], sizeof n);
+                    if (r != PM_OK) return fail("pm_corners_dev", r);
+                    if (n < 0) {                              // more candidates than the buffer holds: double it
+                        if (cp.capacity == 0) cp.capacity = max_kp > 8192 ? 8 * max_kp : 65536;
+                        if (cp.capacity > (1 << 23)) { fprintf(stderr, "pm_cli: too many corner candidates\n"); return 1; }
+                        cp.capacity *= 2;
+                    }
+                }
+                ft.n = n;
+                ft.kp_xy.resize(2 * static_cast<size_t>(n));
+                r = pm_device_download(feat_ctx, ft.kp_xy.data(), dev_kp[i], ft.kp_xy.size() * sizeof(float));
+                if (r != PM_OK) return fail("download of the corners", r);
             } else if (features == "device") {
                 // ---- upload, extract on the device, bring back keypoints + float rows (match list, --save-features)
                 int r = feat_ctx ? PM_OK : pm_ctx_create(device, &feat_ctx);
@@ -372,7 +429,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px]] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -478,13 +535,15 @@ int main(int argc, char** argv)
         void *d_xy1 = nullptr, *d_xy2 = nullptr, *d_src = nullptr, *d_cnt = nullptr;
         const size_t rows = static_cast<size_t>(max_kp);
         int32_t cnt = 0;
-        rc = pm_pyramid_create(ctx, img_w[0], img_h[0], lk_levels, &py1);
+        if (corner_pyr) { py1 = corner_pyr; corner_pyr = nullptr; }   // --points corners built it already
+        else rc = pm_pyramid_create(ctx, img_w[0], img_h[0], lk_levels, &py1);
+        const bool py1_built = rc == PM_OK && corner_points;
         if (rc == PM_OK) rc = pm_pyramid_create(ctx, img_w[1], img_h[1], lk_levels, &py2);
         if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 8, &d_xy1);
         if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 8, &d_xy2);
         if (rc == PM_OK) rc = pm_device_alloc(ctx, rows * 4, &d_src);
         if (rc == PM_OK) rc = pm_device_alloc(ctx, 4, &d_cnt);
-        if (rc == PM_OK) rc = pm_pyramid_build_dev(ctx, py1, static_cast<const uint8_t*>(dev_img[0]), img_w[0]);
+        if (rc == PM_OK && !py1_built) rc = pm_pyramid_build_dev(ctx, py1, static_cast<const uint8_t*>(dev_img[0]), img_w[0]);
         if (rc == PM_OK) rc = pm_pyramid_build_dev(ctx, py2, static_cast<const uint8_t*>(dev_img[1]), img_w[1]);
         if (rc == PM_OK)
             rc = pm_track_lk_gather_dev(ctx, py1, py2, static_cast<const float*>(dev_kp[0]), static_cast<const int32_t*>(dev_n[0]), max_kp,
