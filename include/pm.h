@@ -1145,6 +1145,50 @@ int pm_corners_replenish_dev(pm_ctx* ctx, const pm_pyramid* pyr, const pm_corner
 int pm_corners(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, const pm_corner_params* p, const float* keep, int n_keep,
                int max_corners, float* xy, float* score, int32_t* n_out);
 
+/* ---- describe given points: oriented 256-bit descriptors on a pm_pyramid — docs/SPEC.md S71-S74 ---------------------------
+ * The `compute` half of a corner front end (ORB is "corners + steered BRIEF"): 32 bytes per GIVEN point, so that the corners of
+ * pm_corners* and the tracked points of pm_track_lk* can be matched by appearance with pm_bf_knn_hamming_u8*,
+ * pm_bf_match_cross_hamming_u8* and the guided Hamming matchers (cols = 32), and located against a map through
+ * pm_gather_pnp_dev.  Points are level-0 pixels; on level p->level the centre is the nearest pixel of (x, y) * 2^-level (ties to
+ * even).  A point is INVALID when a coordinate is not finite or beyond 1e6 in magnitude, or when the 35 x 35 square round the
+ * centre leaves the level (17 <= cx <= w_l - 18, likewise cy): its row is 32 zero bytes, valid 0, bin 255.  Otherwise the
+ * orientation bin (0 .. 35, the bin centres of S56) comes from the intensity centroid over the disc of radius 15, as an arg-max
+ * of int64 dot products (S72; a flat patch gives bin 0), and bit i compares the 5 x 5 box sums at the two points of test i of
+ * the S58 pattern steered to that bin (S73, S74; packing as S60).  PM_DESCRIBE_UPRIGHT skips the orientation: the unrotated
+ * pattern, bin 36.  Everything is integer arithmetic: the rows are a function of the level, the points and the flags alone
+ * (bit for bit the plain-C statement tests/describe_ref.c).
+ *   pm_describe_points_dev   n = *d_n clamped to [0, cap], NULL = cap; the -1 that pm_corners_dev / pm_detect_describe*_dev write
+ *             on overflow counts as 0.  Rows [0, n) of d_desc (cap x 32 bytes, any alignment), d_valid and d_bin (cap bytes each,
+ *             either may be NULL) are written; rows at or beyond n are neither read nor written.  One launch on the context's
+ *             stream, no synchronisation — except on a context's FIRST describe call, which uploads the two tables (38 KiB) into
+ *             a context-owned buffer with a blocking copy (one synchronisation, as the feature buffer of pm_detect_describe*).
+ *   pm_describe_points_gather_dev   adds one launch: the valid rows in input order.  d_xy (cap x 2) receives bit copies of their
+ *             input points, d_desc (cap x 32) their rows, d_src_idx (may be NULL) their input row numbers, *d_count their
+ *             number.  d_xy must not overlap d_pts.  The aligned rows live in the context's scratch arena, which may grow on
+ *             the first call or with a larger cap (one stream synchronisation).  Chains after pm_corners_dev (its d_xy, d_n)
+ *             and after pm_track_lk_gather_dev (its d_xy2, d_count); d_desc and *d_count feed the Hamming matchers.
+ *   pm_describe_points   the blocking host form: builds the pyramid up to p->level, runs, downloads, and frees what it
+ *             allocated (images below 16 pixels a side are PM_E_UNSUPPORTED, as for pm_pyramid_create); valid, bin may be NULL.
+ *   pm_describe_points_tables   no GPU needed: cos_sin_q20 = nearbyint(2^20 cos theta_b) for b = 0 .. 35, then the sines;
+ *             steered = int8 [37][256][4] (dx1, dy1, dx2, dy2), row 36 being the S58 pattern.  Either may be NULL.
+ * PM_E_INVALID: null required pointers, level outside 0 .. 7 or not a level of the pyramid, unknown flag bits, reserved != 0,
+ * cap or n < 0, a pyramid of another device.  PM_E_UNSUPPORTED: cap == 0 (n == 0 in the host form), and a capturing stream
+ * (refused first, before anything is allocated, synchronised or launched).
+ * Timing names: "desc_points", "desc_compact". */
+#define PM_DESCRIBE_UPRIGHT 1   /* no orientation: the unrotated pattern, bin 36 */
+typedef struct pm_describe_params {
+    int32_t level;         /* 0 .. levels of the pyramid - 1 */
+    int32_t flags;         /* 0 or PM_DESCRIBE_UPRIGHT */
+    int32_t reserved[2];   /* 0 */
+} pm_describe_params;
+int pm_describe_points_dev(pm_ctx* ctx, const pm_pyramid* pyr, const float* d_pts, const int32_t* d_n, int cap,
+                           const pm_describe_params* p, uint8_t* d_desc, uint8_t* d_valid, uint8_t* d_bin);
+int pm_describe_points_gather_dev(pm_ctx* ctx, const pm_pyramid* pyr, const float* d_pts, const int32_t* d_n, int cap,
+                                  const pm_describe_params* p, float* d_xy, uint8_t* d_desc, int32_t* d_src_idx, int32_t* d_count);
+int pm_describe_points(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride, const float* pts, int n,
+                       const pm_describe_params* p, uint8_t* desc, uint8_t* valid, uint8_t* bin);
+int pm_describe_points_tables(int32_t cos_sin_q20[72], int8_t steered[37 * 256 * 4]);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

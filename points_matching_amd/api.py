@@ -77,6 +77,7 @@ EXPORTS = [
     "pm_pyramid_create", "pm_pyramid_destroy", "pm_pyramid_build_dev", "pm_pyramid_level_get",
     "pm_track_lk_dev", "pm_track_lk_gather_dev", "pm_track_lk",
     "pm_corners_dev", "pm_corners_replenish_dev", "pm_corners",
+    "pm_describe_points_dev", "pm_describe_points_gather_dev", "pm_describe_points", "pm_describe_points_tables",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -120,6 +121,19 @@ class CornerParams(C.Structure):
 def corner_params(block_radius=10, min_eig=1e-4, quality=0.01, min_dist=8.0, capacity=0):
     """block_radius: use the tracker's win_radius to share its eigenvalue; quality, min_dist: OpenCV's qualityLevel, minDistance."""
     return CornerParams(block_radius, min_eig, quality, min_dist, capacity, 0, (C.c_int32 * 2)(0, 0))
+
+
+class DescribeParams(C.Structure):
+    """pm_describe_params (include/pm.h, SPEC S71-S74); describe_params() fills it."""
+    _fields_ = [("level", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+PM_DESCRIBE_UPRIGHT = 1
+
+
+def describe_params(level=0, flags=0):
+    """level: the pyramid level the points are described on; flags: 0 or PM_DESCRIBE_UPRIGHT."""
+    return DescribeParams(level, flags, (C.c_int32 * 2)(0, 0))
 
 
 class Camera(C.Structure):
@@ -351,6 +365,15 @@ def detect_bits_table():
     steer = np.zeros((3, 36, 256, 4), np.int8)
     _check(lib().pm_detect_bits_table(_p(base), _p(steer)))
     return base, steer
+
+
+def describe_points_tables():
+    """pm_describe_points_tables: (cos_sin_q20 (72,) int32 = C[0..35] then S[0..35], steered (37, 256, 4) int8) of SPEC S72, S73;
+    no GPU needed."""
+    q20 = np.zeros(72, np.int32)
+    steer = np.zeros((37, 256, 4), np.int8)
+    _check(lib().pm_describe_points_tables(_p(q20), _p(steer)))
+    return q20, steer
 
 
 # ---- GPU context ------------------------------------------------------------------------------
@@ -706,6 +729,34 @@ class Context:
         _check(lib().pm_corners(self._h, _p(img), w, h, img.shape[1], C.byref(prm), _p(keep) if n_keep else None, n_keep, max_corners,
                                 _p(xy), _p(score), C.byref(n)))
         return xy[:n.value].copy(), score[:n.value].copy()
+
+    # -- describe given points: oriented 256-bit descriptors on a pyramid level (SPEC S71-S74) -----------------------------
+    def describe_points_dev(self, pyr, dpts_ptr, dn_ptr, cap, prm, ddesc_ptr, dvalid_ptr=None, dbin_ptr=None):
+        """Device pointers; pyr: a built Pyramid; dn_ptr (device int32 count) may be None = cap; prm: DescribeParams.  Writes
+        rows [0, n) of ddesc (cap x 32 bytes), dvalid and dbin (cap bytes each, either may be None)."""
+        _check(lib().pm_describe_points_dev(self._h, pyr._h, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap, C.byref(prm),
+                                            C.c_void_p(ddesc_ptr), C.c_void_p(dvalid_ptr or 0), C.c_void_p(dbin_ptr or 0)))
+
+    def describe_points_gather_dev(self, pyr, dpts_ptr, dn_ptr, cap, prm, dxy_ptr, ddesc_ptr, dcount_ptr, dsrc_ptr=None):
+        """Describe and keep the valid rows in input order: dxy (cap x 2), ddesc (cap x 32) and *dcount feed the Hamming matchers."""
+        _check(lib().pm_describe_points_gather_dev(self._h, pyr._h, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap, C.byref(prm),
+                                                   C.c_void_p(dxy_ptr), C.c_void_p(ddesc_ptr), C.c_void_p(dsrc_ptr or 0),
+                                                   C.c_void_p(dcount_ptr)))
+
+    def describe_points(self, img, pts, prm=None, w=None):
+        """Host form: 8-bit grey image (h, w), points (n, 2) in level-0 pixels -> (desc (n, 32) u8, valid (n,) u8, bin (n,) u8).
+        With w given, img holds h rows of img.shape[1] >= w bytes (a row stride)."""
+        img = np.ascontiguousarray(img, np.uint8)
+        if img.ndim != 2:
+            raise ValueError("img must be a 2-D array")
+        h = img.shape[0]
+        w = img.shape[1] if w is None else w
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        prm = prm or describe_params()
+        desc, valid, bins = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        _check(lib().pm_describe_points(self._h, _p(img), w, h, img.shape[1], _p(pts), n, C.byref(prm), _p(desc), _p(valid), _p(bins)))
+        return desc[:n], valid[:n], bins[:n]
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

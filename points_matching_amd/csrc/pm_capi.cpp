@@ -206,6 +206,7 @@ int pm_ctx_destroy(pm_ctx* ctx)
     if (ctx->kf_tile) (void)hipFree(ctx->kf_tile);
     if (ctx->widen) (void)hipFree(ctx->widen);
     if (ctx->feat) (void)hipFree(ctx->feat);
+    if (ctx->desc_tab) (void)hipFree(ctx->desc_tab);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;

@@ -101,6 +101,8 @@ struct pm_ctx {
     int feat_noct = 0;
     int feat_w[16] = {}, feat_h[16] = {};
     size_t feat_off[16] = {};              // byte offset of each octave's six planes
+    // point descriptors (describe_points.hip): the Q20 bin table and the steered offsets of S72 / S73, uploaded on the first call
+    char* desc_tab = nullptr;
 };
 
 namespace pm {

@@ -1,5 +1,5 @@
-// pyramid.hpp — the device image pyramid of docs/SPEC.md S61, shared by the tracker (track_lk.hip, which builds it) and the
-// corner detector (corners.hip, which reads level 0).
+// pyramid.hpp — the device image pyramid of docs/SPEC.md S61, shared by the tracker (track_lk.hip, which builds it), the
+// corner detector (corners.hip, which reads level 0) and the point descriptors (describe_points.hip, which read one level).
 #pragma once
 #include <cstddef>
 #include <cstdint>

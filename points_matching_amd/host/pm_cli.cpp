@@ -10,7 +10,7 @@
 //          [--filter midpoint|ratio|cross|cross-ratio] [--ratio 0.8] [--iters 10000] [--thresh 1.0] [--seed 24301]
 //          [--method 7point-lmeds|ransac8] [--f-scale opencv|unit] [--device 0] [--gpus N] [--quiet] [--json]
 //          [--print-epilines] [--epilines out.ppm [--canvas W H] [--img2 right.pgm]] [--matcher bf|flann]
-//          [--guided TAU] [--features host|device] [--descriptor grad|bits]
+//          [--guided TAU] [--features host|device|corners] [--descriptor grad|bits]
 //          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]
 //                           [--points dog|corners [--corner-dist D] [--corner-quality Q] [--corner-min-eig M]]]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
@@ -22,6 +22,10 @@
 // --matcher flann, --gpus N / --mgpu, the second pass of --guided) takes host rows by its interface and is given the
 // downloaded float rows: same values, one upload more.  host (default): the C++ extractor of pm_features.cpp.  Same
 // keypoints either way; descriptors may differ by one in rare elements (pm.h).
+// --features corners (with --img1/--img2): on both images a pyramid, the minimum-eigenvalue corners of its level 0
+// (pm_corners_dev: --max-kp corners, block radius 10, --corner-dist / --corner-quality / --corner-min-eig as for --points
+// corners) and their oriented 256-bit descriptors (pm_describe_points_gather_dev at level 0, docs/SPEC.md S71-S74); from there
+// the path of --features device --descriptor bits.  --descriptor grad, --matcher track|flann and --points are usage errors.
 // --descriptor bits (with --img1/--img2; default grad): 256-bit steered binary descriptors (docs/SPEC.md S58-S60) in place of
 // the 128-D gradient rows: the descriptor matrices are uint8 with 32 columns, every path below matches them by Hamming
 // distance, and with --features device (pm_detect_describe_bits_dev) the plain matcher reads them through
@@ -200,7 +204,7 @@ int main(int argc, char** argv)
     unsigned long long seed = 0x5EED;
     int device = 0, gpus = 1, canvas_w = 993, canvas_h = 660;       // canvas default: the size of img01/img02
     std::string epi_ppm, img2_path, matcher = "bf", img1_path, save_prefix, knn_hint, features = "host", descriptor = "grad";
-    bool extract_only = false, filter_given = false;
+    bool extract_only = false, filter_given = false, descriptor_given = false;
     int lk_radius = 10, lk_levels = 3;
     float lk_fb = 0.f;
     std::string points = "dog";
@@ -243,8 +247,8 @@ int main(int argc, char** argv)
         else if (a == "--img2") img2_path = val("--img2");
         else if (a == "--img1") img1_path = val("--img1");
         else if (a == "--max-kp") max_kp = atoi(val("--max-kp"));
-        else if (a == "--features") features = val("--features");      // host | device: where --img1/--img2 are extracted
-        else if (a == "--descriptor") descriptor = val("--descriptor");  // grad | bits: what --img1/--img2 are described with
+        else if (a == "--features") features = val("--features");      // host | device | corners: how --img1/--img2 are extracted
+        else if (a == "--descriptor") { descriptor = val("--descriptor"); descriptor_given = true; }  // grad | bits: what --img1/--img2 are described with
         else if (a == "--dump-bits-pattern") {                             // the host extractor's 256 tests of S58, one per line; no GPU
             signed char pat[256][4];
             pm_feat::bits_pattern(pat);
@@ -260,11 +264,19 @@ int main(int argc, char** argv)
     }
     Matrix d1, d2, k1, k2;
     const bool from_images = !img1_path.empty();
-    if (features != "host" && features != "device") { fprintf(stderr, "pm_cli: --features host|device\n"); return 2; }
+    const bool corner_feat = features == "corners";
+    if (features != "host" && features != "device" && !corner_feat) { fprintf(stderr, "pm_cli: --features host|device|corners\n"); return 2; }
     if (features == "device" && !from_images) { fprintf(stderr, "pm_cli: --features device needs --img1 / --img2\n"); return 2; }
+    if (corner_feat && !from_images) { fprintf(stderr, "pm_cli: --features corners needs --img1 / --img2\n"); return 2; }
     if (descriptor != "grad" && descriptor != "bits") { fprintf(stderr, "pm_cli: --descriptor grad|bits\n"); return 2; }
     if (descriptor == "bits" && !from_images) { fprintf(stderr, "pm_cli: --descriptor bits needs --img1 / --img2\n"); return 2; }
-    const bool want_bits = descriptor == "bits";
+    if (corner_feat && descriptor_given && descriptor == "grad") {
+        fprintf(stderr, "pm_cli: --features corners describes by bits and takes no --descriptor grad\n");
+        return 2;
+    }
+    if (corner_feat && matcher != "bf") { fprintf(stderr, "pm_cli: --features corners takes --matcher bf only\n"); return 2; }
+    if (corner_feat && points_given) { fprintf(stderr, "pm_cli: --features corners takes no --points\n"); return 2; }
+    const bool want_bits = descriptor == "bits" || corner_feat;
     const bool track = matcher == "track";
     if (track && (!from_images || features != "device" || want_bits || filter_given || guided || gpus != 1 || force_mgpu)) {
         fprintf(stderr, "pm_cli: --matcher track needs --img1 / --img2 --features device and takes no --descriptor bits, --filter, "
@@ -276,11 +288,11 @@ int main(int argc, char** argv)
         return 2;
     }
     const bool corner_points = points == "corners";
-    if ((points_given || corner_opt_given) && (!track || (points != "dog" && !corner_points) || (corner_opt_given && !corner_points))) {
+    if ((points_given || (corner_opt_given && !corner_feat)) && (!track || (points != "dog" && !corner_points) || (corner_opt_given && !corner_points))) {
         fprintf(stderr, "pm_cli: --points dog|corners needs --matcher track, and the --corner-* options need --points corners\n");
         return 2;
     }
-    if (corner_points && (!(corner_dist >= 0.f) || !(corner_dist <= 1e6f) || !(corner_quality >= 0.f) || !(corner_quality <= 1.f) ||
+    if ((corner_points || corner_feat) && (!(corner_dist >= 0.f) || !(corner_dist <= 1e6f) || !(corner_quality >= 0.f) || !(corner_quality <= 1.f) ||
                           !(corner_min_eig >= 0.f) || !(corner_min_eig <= 3.0e38f))) {
         fprintf(stderr, "pm_cli: --corner-dist 0..1e6, --corner-quality 0..1, --corner-min-eig >= 0\n");
         return 2;
@@ -361,6 +373,50 @@ int main(int argc, char** argv)
                 ft.kp_xy.resize(2 * static_cast<size_t>(n));
                 r = pm_device_download(feat_ctx, ft.kp_xy.data(), dev_kp[i], ft.kp_xy.size() * sizeof(float));
                 if (r != PM_OK) return fail("download of the corners", r);
+            } else if (corner_feat) {
+                // ---- upload, pyramid (level 0), corners, descriptors of the corners at level 0; the rows stay for the matcher
+                int r = feat_ctx ? PM_OK : pm_ctx_create(device, &feat_ctx);
+                if (r != PM_OK) return fail("pm_ctx_create", r);
+                const size_t rows = static_cast<size_t>(max_kp);
+                r = pm_device_alloc(feat_ctx, im.px.size(), &dev_img[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 8, &dev_kp[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 32, &dev_u8[i]);
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, rows * 8 + 16, &dev_f32[i]);     // the corners, then their count
+                if (r == PM_OK) r = pm_device_alloc(feat_ctx, 4, &dev_n[i]);
+                if (r == PM_OK) r = pm_device_upload(feat_ctx, dev_img[i], im.px.data(), im.px.size());
+                if (r != PM_OK) return fail("device buffers", r);
+                float* d_corner = static_cast<float*>(dev_f32[i]);
+                int32_t* d_ncorner = reinterpret_cast<int32_t*>(static_cast<char*>(dev_f32[i]) + rows * 8);
+                pm_pyramid* pyr = nullptr;
+                r = pm_pyramid_create(feat_ctx, im.w, im.h, 0, &pyr);
+                if (r == PM_OK) r = pm_pyramid_build_dev(feat_ctx, pyr, static_cast<const uint8_t*>(dev_img[i]), im.w);
+                pm_corner_params cp;
+                cp.block_radius = 10; cp.min_eig = corner_min_eig; cp.quality = corner_quality; cp.min_dist = corner_dist;
+                cp.capacity = 0; cp.flags = 0; cp.reserved[0] = cp.reserved[1] = 0;
+                pm_describe_params dp;
+                dp.level = 0; dp.flags = 0; dp.reserved[0] = dp.reserved[1] = 0;
+                int32_t nc = -1, n = 0;
+                while (r == PM_OK && nc < 0) {
+                    r = pm_corners_dev(feat_ctx, pyr, &cp, nullptr, nullptr, 0, max_kp, d_corner, nullptr, d_ncorner);
+                    if (r == PM_OK) r = pm_device_download(feat_ctx, &nc, d_ncorner, sizeof nc);
+                    if (r == PM_OK && nc < 0) {               // more candidates than the buffer holds: double it
+                        if (cp.capacity == 0) cp.capacity = max_kp > 8192 ? 8 * max_kp : 65536;
+                        if (cp.capacity > (1 << 23)) { fprintf(stderr, "pm_cli: too many corner candidates\n"); pm_pyramid_destroy(pyr); return 1; }
+                        cp.capacity *= 2;
+                    }
+                }
+                if (r == PM_OK)
+                    r = pm_describe_points_gather_dev(feat_ctx, pyr, d_corner, d_ncorner, max_kp, &dp, static_cast<float*>(dev_kp[i]),
+                                                      static_cast<uint8_t*>(dev_u8[i]), nullptr, static_cast<int32_t*>(dev_n[i]));
+                if (r == PM_OK) r = pm_device_download(feat_ctx, &n, dev_n[i], sizeof n);
+                pm_pyramid_destroy(pyr);                      // (the download synchronised: nothing reads it any more)
+                if (r != PM_OK) return fail("corners and their descriptors", r);
+                ft.n = n;
+                ft.kp_xy.resize(2 * static_cast<size_t>(n));
+                ft.bits.resize(32 * static_cast<size_t>(n));
+                r = pm_device_download(feat_ctx, ft.kp_xy.data(), dev_kp[i], ft.kp_xy.size() * sizeof(float));
+                if (r == PM_OK) r = pm_device_download(feat_ctx, ft.bits.data(), dev_u8[i], ft.bits.size());
+                if (r != PM_OK) return fail("download of the features", r);
             } else if (features == "device") {
                 // ---- upload, extract on the device, bring back keypoints + float rows (match list, --save-features)
                 int r = feat_ctx ? PM_OK : pm_ctx_create(device, &feat_ctx);
@@ -429,7 +485,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device|corners] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
