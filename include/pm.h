@@ -1189,6 +1189,55 @@ int pm_describe_points(pm_ctx* ctx, const uint8_t* img, int w, int h, int stride
                        const pm_describe_params* p, uint8_t* desc, uint8_t* valid, uint8_t* bin);
 int pm_describe_points_tables(int32_t cos_sin_q20[72], int8_t steered[37 * 256 * 4]);
 
+/* ---- apply a 2-D model: warp an 8-bit image by H or A, transform points — docs/SPEC.md S75-S78 -----------------------------
+ * The step after pm_ransac_homography_run_dev / pm_ransac_affine_run_dev and their refinements (cv::warpPerspective,
+ * cv::warpAffine and cv::perspectiveTransform after cv::findHomography / cv::estimateAffine2D): the stabilised frame, the
+ * mosaic tile, the registered scan, and the tracker's PM_LK_USE_INITIAL guess from the last H, without leaving the stream.
+ * M is 9 doubles, row-major; with PM_WARP_AFFINE 6 doubles as d_A lies (2 x 3), lifted with the last row (0, 0, 1).  Output
+ * pixel (x, y) samples the source at M (x, y, 1)^T: the d_H of x2 ~ H x1 pulls image 2 into frame 1 as it lies.  With
+ * PM_WARP_INVERT the adjugate of M takes its place (cv::warpPerspective's default direction).  Positions are fp64, rounded to
+ * 1/32 pixel (ties to even); the sample is the integer bilinear sum of four taps with weights that add to 1024,
+ * out = (sum + 512) >> 10: every output byte is a function of the inputs alone (bit for bit the plain-C statement
+ * tests/warp_ref.c; OpenCV's bytes are close, not equal).  A tap outside the source contributes border_value, or with
+ * PM_WARP_REPLICATE the nearest source pixel; a tap of weight zero is never read.  A pixel is VALID when its position is
+ * usable (W != 0, finite, below 2^30 in magnitude) and every tap of non-zero weight lies inside the source, under both border
+ * modes; pixels whose position is not usable are border_value.
+ *   pm_warp_dev   one launch on the context's stream, nothing allocated, the model read on the device.  d_src: sh rows of
+ *             sstride bytes, sw used; d_dst: dh rows of dstride bytes, dw written, the rest untouched; base pointers and strides
+ *             of any alignment.  d_valid (may be NULL): dw x dh bytes, stride dw, 1 = valid.  d_info (may be NULL): cleared by
+ *             one 8-byte async memset before the launch; n_valid = number of valid pixels; status 1 = M (or, with
+ *             PM_WARP_AFFINE, its lift) has a non-finite entry or a determinant that is zero or not finite, 2 = every entry of
+ *             M is zero (the "no model" value the estimators leave).  With a status other than 0 the whole output is
+ *             border_value, nothing is valid, and the call still returns PM_OK: data outcomes are reported in *d_info only.
+ *   pm_warp   the blocking host form: one staged device block, freed before it returns.
+ *   pm_transform_points_dev   out = ((float)(X / W), (float)(Y / W)) with (X, Y, W) = M (x, y, 1)^T in fp64; flags:
+ *             PM_WARP_INVERT, PM_WARP_AFFINE.  Both coordinates are NaN (which pm_track_lk* turns into status 2) when W == 0,
+ *             a quotient is not finite, or the model is one pm_warp_dev reports.  n = *d_n clamped to [0, cap], NULL = cap,
+ *             -1 counts as 0; rows at or beyond n are neither read nor written.  d_out may equal d_pts.  One launch.
+ *   pm_transform_points   the blocking host form.
+ * PM_E_INVALID: null required pointers, unknown flag bits, border_value outside 0 .. 255, reserved != 0, a size below 1, a
+ * stride below its width, cap or n < 0, d_src and d_dst ranges that overlap.  PM_E_UNSUPPORTED: more than 100 000 000 pixels
+ * on either side, cap == 0 (n == 0 in the host form), and a capturing stream (refused first, before anything is launched).
+ * Timing names: "warp_bilinear", "warp_points". */
+#define PM_WARP_INVERT    1   /* sample through the adjugate of M */
+#define PM_WARP_REPLICATE 2   /* taps outside the source take the nearest source pixel */
+#define PM_WARP_AFFINE    4   /* M is 6 doubles (2 x 3) */
+typedef struct pm_warp_params {
+    int32_t flags;          /* PM_WARP_* */
+    int32_t border_value;   /* 0 .. 255 */
+    int32_t reserved[2];    /* 0 */
+} pm_warp_params;
+typedef struct pm_warp_info {
+    int32_t status;         /* 0 ok, 1 singular or non-finite, 2 zero model */
+    int32_t n_valid;
+} pm_warp_info;
+int pm_warp_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, int sstride, const double* d_M, const pm_warp_params* p,
+                uint8_t* d_dst, int dw, int dh, int dstride, uint8_t* d_valid, pm_warp_info* d_info);
+int pm_warp(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstride, const double* M, const pm_warp_params* p,
+            uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info);
+int pm_transform_points_dev(pm_ctx* ctx, const double* d_M, int flags, const float* d_pts, const int32_t* d_n, int cap, float* d_out);
+int pm_transform_points(pm_ctx* ctx, const double* M, int flags, const float* pts, int n, float* out);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

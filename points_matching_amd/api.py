@@ -78,6 +78,7 @@ EXPORTS = [
     "pm_track_lk_dev", "pm_track_lk_gather_dev", "pm_track_lk",
     "pm_corners_dev", "pm_corners_replenish_dev", "pm_corners",
     "pm_describe_points_dev", "pm_describe_points_gather_dev", "pm_describe_points", "pm_describe_points_tables",
+    "pm_warp_dev", "pm_warp", "pm_transform_points_dev", "pm_transform_points",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -134,6 +135,24 @@ PM_DESCRIBE_UPRIGHT = 1
 def describe_params(level=0, flags=0):
     """level: the pyramid level the points are described on; flags: 0 or PM_DESCRIBE_UPRIGHT."""
     return DescribeParams(level, flags, (C.c_int32 * 2)(0, 0))
+
+
+class WarpParams(C.Structure):
+    """pm_warp_params (include/pm.h, SPEC S75-S77); warp_params() fills it."""
+    _fields_ = [("flags", C.c_int32), ("border_value", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class WarpInfo(C.Structure):
+    """pm_warp_info: status 0 ok, 1 singular or non-finite model, 2 the zero model; n_valid = valid output pixels."""
+    _fields_ = [("status", C.c_int32), ("n_valid", C.c_int32)]
+
+
+PM_WARP_INVERT, PM_WARP_REPLICATE, PM_WARP_AFFINE = 1, 2, 4
+
+
+def warp_params(flags=0, border_value=0):
+    """flags: PM_WARP_INVERT | PM_WARP_REPLICATE | PM_WARP_AFFINE; border_value: 0 .. 255."""
+    return WarpParams(flags, border_value, (C.c_int32 * 2)(0, 0))
 
 
 class Camera(C.Structure):
@@ -757,6 +776,49 @@ class Context:
         desc, valid, bins = np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
         _check(lib().pm_describe_points(self._h, _p(img), w, h, img.shape[1], _p(pts), n, C.byref(prm), _p(desc), _p(valid), _p(bins)))
         return desc[:n], valid[:n], bins[:n]
+
+    # -- apply a 2-D model: image warp by H or A, point transform (SPEC S75-S78) -------------------------------------------
+    def warp_dev(self, dsrc_ptr, sw, sh, sstride, dM_ptr, prm, ddst_ptr, dw, dh, dstride, dvalid_ptr=None, dinfo_ptr=None):
+        """Device pointers; dM: 9 doubles (6 with PM_WARP_AFFINE) read on the device; prm: WarpParams.  dvalid (dw x dh bytes) and
+        dinfo (a WarpInfo, 8 bytes) may be None."""
+        _check(lib().pm_warp_dev(self._h, C.c_void_p(dsrc_ptr), sw, sh, sstride, C.c_void_p(dM_ptr), C.byref(prm) if prm is not None else None,
+                                 C.c_void_p(ddst_ptr), dw, dh, dstride, C.c_void_p(dvalid_ptr or 0), C.c_void_p(dinfo_ptr or 0)))
+
+    def warp(self, src, M, prm=None, dw=None, dh=None, sw=None):
+        """Host form: 8-bit grey image (sh, sw), M (3, 3) or with PM_WARP_AFFINE (2, 3) -> (dst (dh, dw) u8, valid (dh, dw) u8,
+        status, n_valid).  With sw given, src holds rows of src.shape[1] >= sw bytes (a row stride)."""
+        src = np.ascontiguousarray(src, np.uint8)
+        if src.ndim != 2:
+            raise ValueError("src must be a 2-D array")
+        sh = src.shape[0]
+        sw = src.shape[1] if sw is None else sw
+        dw = sw if dw is None else dw
+        dh = sh if dh is None else dh
+        prm = prm or warp_params()
+        M = np.ascontiguousarray(M, np.float64).reshape(-1)
+        if M.size != (6 if prm.flags & PM_WARP_AFFINE else 9):
+            raise ValueError("M must hold 9 doubles, or 6 with PM_WARP_AFFINE")
+        dst, valid = np.zeros((max(dh, 1), max(dw, 1)), np.uint8), np.zeros((max(dh, 1), max(dw, 1)), np.uint8)
+        info = WarpInfo()
+        _check(lib().pm_warp(self._h, _p(src), sw, sh, src.shape[1], _p(M), C.byref(prm), _p(dst), dw, dh, dst.shape[1], _p(valid),
+                             C.byref(info)))
+        return dst, valid, info.status, info.n_valid
+
+    def transform_points_dev(self, dM_ptr, flags, dpts_ptr, dn_ptr, cap, dout_ptr):
+        """Device pointers; dn_ptr (device int32 count) may be None = cap; dout may equal dpts."""
+        _check(lib().pm_transform_points_dev(self._h, C.c_void_p(dM_ptr), flags, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                             C.c_void_p(dout_ptr)))
+
+    def transform_points(self, M, pts, flags=0):
+        """Host form: points (n, 2) through M (3, 3), or (2, 3) with PM_WARP_AFFINE -> (n, 2) f32 (cv::perspectiveTransform)."""
+        M = np.ascontiguousarray(M, np.float64).reshape(-1)
+        if M.size != (6 if flags & PM_WARP_AFFINE else 9):
+            raise ValueError("M must hold 9 doubles, or 6 with PM_WARP_AFFINE")
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        out = np.zeros((max(n, 1), 2), np.float32)
+        _check(lib().pm_transform_points(self._h, _p(M), flags, _p(pts), n, _p(out)))
+        return out[:n]
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

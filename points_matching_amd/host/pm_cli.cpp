@@ -13,6 +13,7 @@
 //          [--guided TAU] [--features host|device|corners] [--descriptor grad|bits]
 //          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]
 //                           [--points dog|corners [--corner-dist D] [--corner-quality Q] [--corner-min-eig M]]]
+//          [--align OUT.pgm [--align-model homography|affine|similarity]]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -26,6 +27,16 @@
 // (pm_corners_dev: --max-kp corners, block radius 10, --corner-dist / --corner-quality / --corner-min-eig as for --points
 // corners) and their oriented 256-bit descriptors (pm_describe_points_gather_dev at level 0, docs/SPEC.md S71-S74); from there
 // the path of --features device --descriptor bits.  --descriptor grad, --matcher track|flann and --points are usage errors.
+// --align OUT.pgm (with --img1/--img2 of one size, any matcher or track route, one GPU): after the correspondences the chosen
+// 2-D model (--align-model homography (default) | affine | similarity: pm_ransac_homography_run_dev + pm_homography_refine_dev,
+// or pm_ransac_affine_run_dev + pm_affine_refine_dev with PM_AFFINE_FULL | PM_AFFINE_PARTIAL; --iters, --thresh, --seed as
+// given) takes the place of the F estimator, and pm_warp_dev (docs/SPEC.md S75-S77) pulls image 2 into the frame of image 1
+// by that model as it lies on the device, with a valid mask: upload, estimate, refine and warp are enqueued on one stream and
+// synchronised once.  OUT.pgm is the warped image (P5, border 0); one line is printed after the match list:
+//   align: model=M inliers=N valid=V mad_before=B mad_after=A
+// B and A being the mean absolute grey differences to image 1 over the V valid pixels, of image 2 as it is and warped.  No F
+// is estimated, so the residual report is not printed; --json, --guided, --epilines, --print-epilines and --gpus N / --mgpu
+// are usage errors with it.
 // --descriptor bits (with --img1/--img2; default grad): 256-bit steered binary descriptors (docs/SPEC.md S58-S60) in place of
 // the 128-D gradient rows: the descriptor matrices are uint8 with 32 columns, every path below matches them by Hamming
 // distance, and with --features device (pm_detect_describe_bits_dev) the plain matcher reads them through
@@ -193,6 +204,88 @@ int fail(const char* what, int rc)
     return 1;
 }
 
+bool write_pgm(const std::string& path, const std::vector<uint8_t>& px, int w, int h)
+{
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { fprintf(stderr, "pm_cli: cannot write %s\n", path.c_str()); return false; }
+    fprintf(f, "P5\n%d %d\n255\n", w, h);
+    const bool ok = fwrite(px.data(), 1, px.size(), f) == px.size();
+    return fclose(f) == 0 && ok;
+}
+
+// --align: the 2-D model of the correspondences and image 2 warped into the frame of image 1 by it, on the context's stream
+// with one synchronisation (the first download); the PGM and the report line.
+int run_align(pm_ctx* ctx, const std::string& model, const std::string& out_path, const std::string& path1, const std::string& path2,
+              const std::vector<float>& xy1, const std::vector<float>& xy2, int n, pm_ransac_params prm)
+{
+    pm_feat::Image im1, im2;
+    std::string err;
+    if (!pm_feat::load_pnm_gray(path1, im1, err) || !pm_feat::load_pnm_gray(path2, im2, err)) { fprintf(stderr, "pm_cli: %s\n", err.c_str()); return 1; }
+    if (im1.w != im2.w || im1.h != im2.h) { fprintf(stderr, "pm_cli: --align needs two images of one size\n"); return 1; }
+    const bool homography = model == "homography";
+    const int affine_model = model == "similarity" ? PM_AFFINE_PARTIAL : PM_AFFINE_FULL;
+    const int min_pts = homography ? 4 : (affine_model == PM_AFFINE_PARTIAL ? 2 : 3);
+    if (n < min_pts) { fprintf(stderr, "pm_cli: --align: too few correspondences (%d)\n", n); return 1; }
+    const int w = im1.w, h = im1.h;
+    const size_t px = static_cast<size_t>(w) * h, xyb = static_cast<size_t>(n) * 8;
+    void *d_src = nullptr, *d_dst = nullptr, *d_valid = nullptr, *d_xy1 = nullptr, *d_xy2 = nullptr, *d_mask = nullptr, *d_small = nullptr;
+    auto release = [&]() { for (void* p : {d_src, d_dst, d_valid, d_xy1, d_xy2, d_mask, d_small}) pm_device_free(ctx, p); };
+    int rc = pm_device_alloc(ctx, px, &d_src);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, px, &d_dst);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, px, &d_valid);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, xyb, &d_xy1);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, xyb, &d_xy2);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, static_cast<size_t>(n), &d_mask);
+    // one block of small results: model in (72 B), refined model (72 B), key (8 B), inlier count (4 B, padded), warp info (8 B)
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, 256, &d_small);
+    if (rc != PM_OK) { release(); return fail("device buffers of --align", rc); }
+    char* small = static_cast<char*>(d_small);
+    double* d_M = reinterpret_cast<double*>(small);
+    double* d_Mr = reinterpret_cast<double*>(small + 72);
+    uint64_t* d_key = reinterpret_cast<uint64_t*>(small + 144);
+    int32_t* d_ninl = reinterpret_cast<int32_t*>(small + 152);
+    pm_warp_info* d_info = reinterpret_cast<pm_warp_info*>(small + 160);
+    rc = pm_device_upload(ctx, d_src, im2.px.data(), px);
+    if (rc == PM_OK) rc = pm_device_upload(ctx, d_xy1, xy1.data(), xyb);
+    if (rc == PM_OK) rc = pm_device_upload(ctx, d_xy2, xy2.data(), xyb);
+    pm_points_view view;
+    view.xy1 = static_cast<const float*>(d_xy1); view.xy2 = static_cast<const float*>(d_xy2); view.counts = nullptr;
+    view.parts = 1; view.cap = n; view.pitch_xy = 0; view.pitch_cnt = 1; view.reserved = 0;
+    prm.error_kind = PM_ERR_REPROJ;
+    pm_warp_params wp;
+    wp.flags = homography ? 0 : PM_WARP_AFFINE; wp.border_value = 0; wp.reserved[0] = wp.reserved[1] = 0;
+    if (rc == PM_OK && homography) {
+        rc = pm_ransac_homography_run_dev(ctx, &view, &prm, d_key, d_M, static_cast<uint8_t*>(d_mask), n, d_ninl);
+        if (rc == PM_OK) rc = pm_homography_refine_dev(ctx, &view, static_cast<const uint8_t*>(d_mask), d_M, 10, d_Mr, nullptr);
+    } else if (rc == PM_OK) {
+        rc = pm_ransac_affine_run_dev(ctx, affine_model, &view, &prm, d_key, d_M, static_cast<uint8_t*>(d_mask), n, d_ninl);
+        if (rc == PM_OK) rc = pm_affine_refine_dev(ctx, affine_model, &view, static_cast<const uint8_t*>(d_mask), d_M, d_Mr, nullptr);
+    }
+    if (rc == PM_OK)
+        rc = pm_warp_dev(ctx, static_cast<const uint8_t*>(d_src), w, h, w, d_Mr, &wp, static_cast<uint8_t*>(d_dst), w, h, w,
+                         static_cast<uint8_t*>(d_valid), d_info);
+    std::vector<uint8_t> dst(px), valid(px);
+    pm_warp_info info = {0, 0};
+    int32_t n_inl = 0;
+    if (rc == PM_OK) rc = pm_device_download(ctx, dst.data(), d_dst, px);           // the one synchronisation
+    if (rc == PM_OK) rc = pm_device_download(ctx, valid.data(), d_valid, px);
+    if (rc == PM_OK) rc = pm_device_download(ctx, &info, d_info, sizeof info);
+    if (rc == PM_OK) rc = pm_device_download(ctx, &n_inl, d_ninl, sizeof n_inl);
+    release();
+    if (rc != PM_OK) return fail("--align", rc);
+    if (info.status != 0) { fprintf(stderr, "pm_cli: --align: no usable %s (warp status %d)\n", model.c_str(), info.status); return 1; }
+    long long before = 0, after = 0;
+    for (size_t i = 0; i < px; ++i)
+        if (valid[i]) {
+            before += std::abs(static_cast<int>(im2.px[i]) - static_cast<int>(im1.px[i]));
+            after += std::abs(static_cast<int>(dst[i]) - static_cast<int>(im1.px[i]));
+        }
+    if (!write_pgm(out_path, dst, w, h)) return 1;
+    const double nv = info.n_valid > 0 ? static_cast<double>(info.n_valid) : 1.0;
+    printf("align: model=%s inliers=%d valid=%d mad_before=%.4f mad_after=%.4f\n", model.c_str(), n_inl, info.n_valid, before / nv, after / nv);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -207,7 +300,8 @@ int main(int argc, char** argv)
     bool extract_only = false, filter_given = false, descriptor_given = false;
     int lk_radius = 10, lk_levels = 3;
     float lk_fb = 0.f;
-    std::string points = "dog";
+    std::string points = "dog", align_pgm, align_model = "homography";
+    bool align_model_given = false;
     bool points_given = false, corner_opt_given = false;
     float corner_dist = 8.f, corner_quality = 0.01f, corner_min_eig = 1e-4f;
     int max_kp = 4000;
@@ -227,6 +321,8 @@ int main(int argc, char** argv)
         else if (a == "--lk-levels") lk_levels = atoi(val("--lk-levels"));
         else if (a == "--lk-fb") lk_fb = strtof(val("--lk-fb"), nullptr);
         else if (a == "--points") { points = val("--points"); points_given = true; }
+        else if (a == "--align") align_pgm = val("--align");
+        else if (a == "--align-model") { align_model = val("--align-model"); align_model_given = true; }
         else if (a == "--corner-dist") { corner_dist = strtof(val("--corner-dist"), nullptr); corner_opt_given = true; }
         else if (a == "--corner-quality") { corner_quality = strtof(val("--corner-quality"), nullptr); corner_opt_given = true; }
         else if (a == "--corner-min-eig") { corner_min_eig = strtof(val("--corner-min-eig"), nullptr); corner_opt_given = true; }
@@ -295,6 +391,17 @@ int main(int argc, char** argv)
     if ((corner_points || corner_feat) && (!(corner_dist >= 0.f) || !(corner_dist <= 1e6f) || !(corner_quality >= 0.f) || !(corner_quality <= 1.f) ||
                           !(corner_min_eig >= 0.f) || !(corner_min_eig <= 3.0e38f))) {
         fprintf(stderr, "pm_cli: --corner-dist 0..1e6, --corner-quality 0..1, --corner-min-eig >= 0\n");
+        return 2;
+    }
+    const bool align = !align_pgm.empty();
+    if (align_model_given && !align) { fprintf(stderr, "pm_cli: --align-model needs --align OUT.pgm\n"); return 2; }
+    if (align && align_model != "homography" && align_model != "affine" && align_model != "similarity") {
+        fprintf(stderr, "pm_cli: --align-model homography|affine|similarity\n");
+        return 2;
+    }
+    if (align && !from_images) { fprintf(stderr, "pm_cli: --align needs --img1 / --img2\n"); return 2; }
+    if (align && (json || guided || print_epi || !epi_ppm.empty() || gpus != 1 || force_mgpu)) {
+        fprintf(stderr, "pm_cli: --align takes no --json, --guided, --epilines, --print-epilines, --gpus N or --mgpu\n");
         return 2;
     }
     int img_w[2] = {0, 0}, img_h[2] = {0, 0};
@@ -485,7 +592,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device|corners] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device|corners] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--align out.pgm [--align-model homography|affine|similarity]] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
@@ -691,6 +798,14 @@ int main(int argc, char** argv)
     t2 = clk::now();
     }
 
+    if (align) {
+        // ---- the 2-D model and the warp in place of the F estimator and its report
+        const int arc = run_align(ctx, align_model, align_pgm, img1_path, img2_path, xy1, xy2, n_good, prm);
+        if (feat_ctx == ctx) ctx = nullptr;
+        free_device_features();
+        pm_ctx_destroy(ctx);
+        return arc;
+    }
     // ---- cv::findFundamentalMat(...)                                           main.cpp:94-98
     if (method == "7point-lmeds") {
         pm_lmeds_params lp;
