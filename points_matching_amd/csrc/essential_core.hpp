@@ -23,11 +23,17 @@ struct Cam {
     double fx, fy, cx, cy;
 };
 
-// S31: pixel -> normalised, f64 arithmetic rounded to f32
+// S31: pixel -> normalised, f64 arithmetic rounded to f32; NaN unless |value| <= 2^20 (a NaN, an infinity or a
+// coordinate no pinhole image holds: S8's squares of the rest stay finite, so inf <= inf never makes such a row an inlier)
+constexpr float NORM_MAX = 1048576.0f;
+__device__ __forceinline__ float normalise1(float p, double c, double f)
+{
+    const float v = static_cast<float>((static_cast<double>(p) - c) / f);
+    return fabsf(v) <= NORM_MAX ? v : __builtin_nanf("");
+}
 __device__ __forceinline__ float2 normalise(const Cam& k, float2 p)
 {
-    return float2{static_cast<float>((static_cast<double>(p.x) - k.cx) / k.fx),
-                  static_cast<float>((static_cast<double>(p.y) - k.cy) / k.fy)};
+    return float2{normalise1(p.x, k.cx, k.fx), normalise1(p.y, k.cy, k.fy)};
 }
 
 // S32: 5 distinct indices in [0, n) as a pure function of (seed, h, n), n >= 5.  S6's walk on its own stream.

@@ -24,7 +24,11 @@ constexpr int PO_LM = 15 + 5 + 1;         // J^T J, J^T r, cost
 constexpr int PO_MODEL = 27;              // R (9), t (3), E (9), b1 (3), b2 (3)
 
 // S31: the normalised coordinate as the scorer reads it
-__device__ __forceinline__ double norm31(double x, double c, double f) { return static_cast<double>(static_cast<float>((x - c) / f)); }
+__device__ __forceinline__ double norm31(double x, double c, double f)
+{
+    const float v = static_cast<float>((x - c) / f);
+    return fabsf(v) <= 1048576.0f ? static_cast<double>(v) : static_cast<double>(__builtin_nanf(""));
+}
 
 // E = [t]x R
 __device__ __forceinline__ void e_of(const double* R, const double* t, double* E)

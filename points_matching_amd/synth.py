@@ -448,3 +448,149 @@ def affine_view_wide(n, seed=0, width=4000, height=3000, angle=None, scale=None,
         inl[bad] = False
         x2[bad] = rng.uniform(x2[inl].min(axis=0), x2[inl].max(axis=0), (n_out, 2))
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), A, inl
+
+
+def _rodrigues(axis, th):
+    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+
+
+def _wide_camera(width, height, focal, aspect, pp_offset):
+    """K with fx = focal, fy = focal / aspect and the principal point pp_offset (fractions of the size) off-centre."""
+    return np.array([[focal, 0, width * (0.5 + pp_offset[0])], [0, focal / aspect, height * (0.5 + pp_offset[1])],
+                     [0, 0, 1.0]])
+
+
+def _log_uniform(rng, lo, hi, m):
+    return np.exp(rng.uniform(np.log(lo), np.log(hi), m))
+
+
+def calibrated_view_wide(n, seed=0, width=4000, height=3000, focal=3000.0, aspect=1.0, pp_offset=(0.0, 0.0), angle=None,
+                         depth=(4.0, 12.0), forward=False, plane_frac=0.0, noise_px=0.5, outlier_frac=0.3):
+    """calibrated_view at hard geometry: images up to 16000 px wide, narrow and wide fields, any rotation up to 60
+    degrees, near-pure rotation, forward motion, depth ranges of 1:1000, a dominant plane.
+
+    K has fx = `focal`, fy = focal / `aspect` and the principal point `pp_offset` (fractions of the image size) off the
+    centre.  R is a rotation by `angle` radians (None: uniform in [0, pi / 3]) about a random axis.  t is a unit
+    baseline: sideways with random y and z parts, or (`forward`) mostly along the optical axis, so that the epipoles lie
+    inside the images.  The depths of the points in camera 1 are log-uniform over `depth`, in baselines: (100, 100) is a
+    baseline over depth of 1e-2, (0.5, 500) a depth ratio of 1:1000.  `plane_frac` of the points lie on one tilted plane
+    through the middle (geometric mean) of the depth range, the rest off it.  A point is kept if it is at least 0.1
+    baselines in front of both cameras and projects inside both images; ValueError if the two fields barely overlap.
+    Both images get N(0, noise_px); `outlier_frac` of the pairs get uniform-random image-2 positions.
+
+    Returns xy1, xy2 (n x 2 float32 pixels), K (3 x 3), R (3 x 3), t (unit 3-vector; x2 ~ K (R X + t)), X (n x 3 points
+    in camera-1 coordinates) and the boolean ground-truth inlier flags, as calibrated_view does.
+    """
+    rng = np.random.default_rng([seed, 0xE55F])
+    K = _wide_camera(width, height, focal, aspect, pp_offset)
+    Ki = np.linalg.inv(K)
+    axis = rng.normal(size=3)
+    th = rng.uniform(0.0, np.pi / 3) if angle is None else float(angle)
+    R = _rodrigues(axis, th)
+    t = (np.array([rng.uniform(-0.1, 0.1), rng.uniform(-0.1, 0.1), -1.0]) if forward else
+         np.array([1.0, rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)]))
+    t /= np.linalg.norm(t)
+    nrm = np.array([0.15, -0.2, 1.0])
+    d_plane = np.sqrt(depth[0] * depth[1])
+    X = np.zeros((0, 3))
+    on = np.zeros(0, bool)
+    for _ in range(200):
+        if X.shape[0] >= n:
+            break
+        m = 4 * n + 64
+        ray = np.c_[rng.uniform([0, 0], [width, height], (m, 2)), np.ones(m)] @ Ki.T
+        z = _log_uniform(rng, depth[0], depth[1], m)
+        flat = rng.random(m) < plane_frac
+        z = np.where(flat, d_plane / (ray @ nrm), z)
+        P = ray * z[:, None]
+        P2 = P @ R.T + t
+        p2 = P2 @ K.T
+        with np.errstate(all="ignore"):
+            p2 = p2[:, :2] / p2[:, 2:3]
+        ok = ((P[:, 2] > 0.1) & (P2[:, 2] > 0.1) & (p2[:, 0] > 0) & (p2[:, 0] < width) & (p2[:, 1] > 0) &
+              (p2[:, 1] < height))
+        X = np.r_[X, P[ok]]
+        on = np.r_[on, flat[ok]]
+    if X.shape[0] < n:
+        raise ValueError("the two fields of view barely overlap: no scene")
+    X = X[:n]
+    x1 = X @ K.T
+    x1 = x1[:, :2] / x1[:, 2:3]
+    x2 = (X @ R.T + t) @ K.T
+    x2 = x2[:, :2] / x2[:, 2:3]
+    x1 = x1 + rng.normal(0, noise_px, x1.shape)
+    x2 = x2 + rng.normal(0, noise_px, x2.shape)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = rng.permutation(n)[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform([0, 0], [width, height], (n_out, 2))
+    return (np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), K, R, t, X, inl)
+
+
+def pnp_scene_wide(n, seed=0, width=4000, height=3000, focal=3000.0, aspect=1.0, pp_offset=(0.0, 0.0), angle=None,
+                   offset=0.0, depth=(4.0, 12.0), thickness=None, collinear_frac=0.0, behind_frac=0.0, noise_px=0.5,
+                   outlier_frac=0.3):
+    """pnp_scene at hard geometry: any rotation, map coordinates far from the origin, depths of 1:1000, a near-planar
+    map, narrow and wide fields, collinear map points, outliers behind the camera.
+
+    K as calibrated_view_wide.  R is a rotation by `angle` radians (None: uniform in [0, pi]) about a random axis; the
+    camera sits up to 2 units from the map's own origin, and the whole map is shifted by a vector of length `offset`
+    (1e3-1e4: the float32 world coordinates then carry 6e-5 to 1e-3 units of rounding).  Camera-frame depths are
+    log-uniform over `depth`; with `thickness` the points lie within thickness * depth of one tilted plane at the
+    middle of the depth range instead.  `collinear_frac` of the points (inliers) are moved onto one line through two of
+    the map's points, A + k d with A and d on a grid of 2^-10 units and integer k, so that they are EXACTLY collinear in
+    float32 (needs offset = 0).  `outlier_frac` of the pixels are uniform-random image positions; `behind_frac` of those
+    outliers instead keep their true pixel and get the world point mirrored through the camera centre, which projects
+    onto that pixel from behind (w < 0).
+
+    Returns xyz (n x 3 float32 world points), uv (n x 2 float32 pixels), K (3 x 3), R (3 x 3), t (3; x_cam = R X + t) and
+    the boolean ground-truth inlier flags, as pnp_scene does.
+    """
+    if collinear_frac and offset:
+        raise ValueError("exactly collinear points need offset = 0")
+    rng = np.random.default_rng([seed, 0x9AA0])
+    K = _wide_camera(width, height, focal, aspect, pp_offset)
+    Ki = np.linalg.inv(K)
+    axis = rng.normal(size=3)
+    th = rng.uniform(0.0, np.pi) if angle is None else float(angle)
+    R = _rodrigues(axis, th)
+    t0 = rng.uniform(-2.0, 2.0, 3)
+    ray = np.c_[rng.uniform([0, 0], [width, height], (n, 2)), np.ones(n)] @ Ki.T
+    if thickness is None:
+        z = _log_uniform(rng, depth[0], depth[1], n)
+    else:
+        nrm = np.array([0.15, -0.2, 1.0])
+        d_plane = np.sqrt(depth[0] * depth[1])
+        z = d_plane * (1.0 + thickness * rng.uniform(-0.5, 0.5, n)) / (ray @ nrm)
+    Xc = ray * z[:, None]
+    Xw = (Xc - t0) @ R                                          # world = R^T (x_cam - t0)
+    inl = np.ones(n, bool)
+    n_out = int(round(outlier_frac * n))
+    order = rng.permutation(n)
+    bad = order[:n_out]
+    inl[bad] = False
+    n_col = int(round(collinear_frac * n))
+    if n_col:
+        rows = order[n_out:n_out + n_col]
+        g = 2.0 ** -10
+        A = np.rint(Xw[rows[0]] / g) * g
+        d = np.rint((Xw[rows[1]] - A) / 512.0 / g) * g
+        Xw[rows] = A + rng.integers(0, 513, n_col)[:, None] * d
+    shift = rng.normal(size=3)
+    shift *= offset / np.linalg.norm(shift)
+    Xw = Xw + shift
+    t = t0 - R @ shift
+    X32 = Xw.astype(np.float32)
+    Xc = X32.astype(np.float64) @ R.T + t                      # pixels of the float32 map points
+    uv = Xc @ K.T
+    uv = uv[:, :2] / uv[:, 2:3] + rng.normal(0, noise_px, (n, 2))
+    if n_out:
+        n_beh = int(round(behind_frac * n_out))
+        uv[bad[n_beh:]] = rng.uniform([0, 0], [width, height], (n_out - n_beh, 2))
+        mirrored = (-Xc[bad[:n_beh]] - t) @ R                   # R X + t = -x_cam
+        X32[bad[:n_beh]] = mirrored.astype(np.float32)
+    return np.ascontiguousarray(X32), np.ascontiguousarray(uv.astype(np.float32)), K, R, t, inl

@@ -30,11 +30,17 @@ int er_k_valid(const double K[4], float thr_px, float* thr_n)
     return 1;
 }
 
+static float er_norm1(float p, double c, double f)
+{
+    const float v = (float)(((double)p - c) / f);
+    return fabsf(v) <= 1048576.0f ? v : NAN;                 /* NaN, an infinity, beyond 2^20: NaN */
+}
+
 void er_normalise(const double K[4], const float* xy, int n, float* out)
 {
     for (int i = 0; i < n; ++i) {
-        out[2 * i] = (float)(((double)xy[2 * i] - K[2]) / K[0]);
-        out[2 * i + 1] = (float)(((double)xy[2 * i + 1] - K[3]) / K[1]);
+        out[2 * i] = er_norm1(xy[2 * i], K[2], K[0]);
+        out[2 * i + 1] = er_norm1(xy[2 * i + 1], K[3], K[1]);
     }
 }
 

@@ -557,7 +557,11 @@ static void e_of(const double R[9], const double t[3], double E[9])
 }
 
 /* S31: the normalised coordinate as the scorer reads it */
-static double norm31(double x, double c, double f) { return (double)(float)((x - c) / f); }
+static double norm31(double x, double c, double f)
+{
+    const float v = (float)((x - c) / f);
+    return fabsf(v) <= 1048576.0f ? (double)v : (double)NAN;      /* S31: NaN, an infinity, beyond 2^20: NaN */
+}
 
 /* S46: squared Sampson distance of one correspondence under E, in normalised units */
 static double p_cost_term(const p_ctx* s, double x1, double y1, double x2, double y2)
