@@ -682,7 +682,8 @@ int pm_estimate_affine(pm_ctx* ctx, int model, const float* xy1, const float* xy
                        pm_h_refine_info* info);
 
 /* ---- calibrated relative pose (cv::findEssentialMat with RANSAC + cv::recoverPose: visual odometry, SfM front ends,
- * stereo rigs) — docs/SPEC.md S31-S35.  One pinhole camera shared by both views; no distortion.  K is invalid unless
+ * stereo rigs) — docs/SPEC.md S31-S35.  One pinhole camera shared by both views; no distortion
+ * (pixels of a real lens go through pm_undistort_points* first, S81).  K is invalid unless
  * fx, fy > 0, all four values are finite and the normalised threshold thresh_px / ((fx + fy) / 2) is finite and > 0 in
  * fp32.  Correspondences are normalised as xn = (x - cx) / fx, yn = (y - cy) / fy (fp64, rounded to fp32).
  * RANSAC-E: pm_ransac_params with error_kind = PM_ERR_SAMPSON; sample h in [hyp_begin, hyp_end) draws 5
@@ -758,7 +759,8 @@ int pm_estimate_pose_refined(pm_ctx* ctx, const float* xy1, const float* xy2, in
 
 /* ---- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P: locating a new frame against 3-D points that are
  * already known, e.g. those pm_recover_pose triangulates) — docs/SPEC.md S36-S39.  Correspondence i is a world point
- * xyz[3i .. 3i+2] and its pixel uv[2i .. 2i+1] (f32).  One pinhole pm_camera K, no distortion; K is invalid unless fx, fy > 0
+ * xyz[3i .. 3i+2] and its pixel uv[2i .. 2i+1] (f32).  One pinhole pm_camera K, no distortion (pixels of a real lens
+ * go through pm_undistort_points* first, S81); K is invalid unless fx, fy > 0
  * and all four values are finite.  Pose: x_cam = R X + t, pixel ~ K x_cam; R 9 doubles row-major, t 3 doubles.
  * pm_ransac_params with error_kind = PM_ERR_REPROJ and thresh_px finite and > 0 (OpenCV's default reprojectionError is
  * 8); sample h in [hyp_begin, hyp_end) draws 3 correspondences (S37) and the P3P solve (Grunert's quartic, S38) gives up
@@ -1237,6 +1239,65 @@ int pm_warp(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstride, const 
             uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info);
 int pm_transform_points_dev(pm_ctx* ctx, const double* d_M, int flags, const float* d_pts, const int32_t* d_n, int cap, float* d_out);
 int pm_transform_points(pm_ctx* ctx, const double* M, int flags, const float* pts, int n, float* out);
+
+/* ---- lens distortion: undistort points and images, remap through a map — docs/SPEC.md S79-S83 ------------------------------
+ * The step in front of the calibrated estimators (cv::undistortPoints before cv::findEssentialMat / cv::solvePnPRansac) and in
+ * front of the image front end (cv::undistort, cv::initUndistortRectifyMap + cv::remap), without leaving the stream.  The
+ * model is OpenCV's with 5 coefficients (k1, k2, p1, p2, k3): for normalised (x, y), r2 = x^2 + y^2,
+ * rad = 1 + ((k3 r2 + k2) r2 + k1) r2, xd = x rad + (2 p1 x y + p2 (r2 + 2 x^2)), yd = y rad + (p1 (r2 + 2 y^2) + 2 p2 x y),
+ * pixel = (fx xd + cx, fy yd + cy).  All arithmetic is fp64 without fused operations and without transcendental functions:
+ * every output is a function of the inputs alone (bit for bit the plain-C statement tests/undistort_ref.c).
+ * K (the camera the lens belongs to), lens, R and K_new (the camera of the ideal pixels) are HOST pointers read at call time:
+ * lens == NULL means all coefficients zero, R == NULL identity (the rotation step is then skipped, not multiplied through),
+ * K_new == NULL means K.  R is 9 doubles, row-major: the rectifying rotation of cv::undistortPoints /
+ * cv::initUndistortRectifyMap.  The image forms use its TRANSPOSE as its inverse; R is checked for finiteness only, not for
+ * being a rotation.
+ *   pm_distort_points_dev     ideal pixel under K_new -> distorted pixel under K (S80): normalise by K_new, apply R^T and divide
+ *             by Z (when R is given), distort, project by K, round to fp32.  Both outputs are NaN when Z <= 0, rad <= 0 or a
+ *             value is not finite.
+ *   pm_undistort_points_dev   the inverse (S81): exactly `iters` fixed-point rounds as cv::undistortPoints runs them, then a
+ *             convergence gate: the point is re-distorted and kept only when its pixel error is at most tol_px (and rad > 0);
+ *             then R (Z > 0 required) and K_new.  A rejected point is a NaN pair: the estimators never count one as an inlier and
+ *             pm_track_lk* turns it into status 2.
+ *             Both: n = *d_n clamped to [0, cap], NULL = cap, -1 counts as 0; rows at or beyond n are neither read nor written;
+ *             d_out may equal d_pts.  One launch.  pm_undistort_points / pm_distort_points: the blocking host forms.
+ *   pm_undistort_dev   output pixel (u, v) under K_new samples the source at the position pm_distort_points gives it, rounded
+ *             to 1/32 pixel (S82); sampling, the valid mask, n_valid and the border modes are pm_warp_dev's (S77), and so are
+ *             the buffer rules.  A pixel without a usable position (NaN by S80, or 2^30 / 32 pixels away) is border_value and
+ *             not valid.  One launch; d_info->status is always 0 (a bad model is PM_E_INVALID on the host).  pm_undistort: the
+ *             blocking host form, one staged block.
+ *   pm_undistort_map_dev   the positions alone: dw * dh pairs (qx, qy) of int32, 1/32 pixel units, row-major, stride dw;
+ *             (INT32_MIN, INT32_MIN) marks a pixel without a usable position.  d_map must be 8-byte aligned.
+ *   pm_remap_dev   S77 at the positions of a map: exactly the bytes of pm_undistort_dev when the map is pm_undistort_map_dev's.
+ *             Every int32 pair is legal; the pair (INT32_MIN, INT32_MIN) gives border_value and is not valid.  pm_remap: the
+ *             blocking host form.
+ * PM_E_INVALID: null required pointers, a flag other than PM_WARP_REPLICATE, border_value outside 0 .. 255, reserved != 0, a
+ * size below 1, a stride below its width, cap or n < 0, d_src and d_dst (or d_map and d_dst) ranges that overlap, a d_map that
+ * is not 8-byte aligned, K or K_new with a non-finite value or fx, fy not > 0, a non-finite lens coefficient or entry of R,
+ * iters outside [1, 50], tol_px not finite or not > 0.  PM_E_UNSUPPORTED: more than 100 000 000 pixels on either side,
+ * cap == 0 (n == 0 in the host form), and a capturing stream (refused first, before anything is launched).
+ * Timing names: "undistort_bilinear", "undistort_map", "remap_q5", "undistort_points", "distort_points". */
+typedef struct pm_lens { double k1, k2, p1, p2, k3; } pm_lens;   /* OpenCV's distCoeffs order (5 coefficients) */
+int pm_undistort_points_dev(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new,
+                            int iters, double tol_px, const float* d_pts, const int32_t* d_n, int cap, float* d_out);
+int pm_undistort_points(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new,
+                        int iters, double tol_px, const float* pts, int n, float* out);
+int pm_distort_points_dev(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new,
+                          const float* d_pts, const int32_t* d_n, int cap, float* d_out);
+int pm_distort_points(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new,
+                      const float* pts, int n, float* out);
+int pm_undistort_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, int sstride, const pm_camera* K, const pm_lens* lens,
+                     const double* R, const pm_camera* K_new, const pm_warp_params* p,
+                     uint8_t* d_dst, int dw, int dh, int dstride, uint8_t* d_valid, pm_warp_info* d_info);
+int pm_undistort(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstride, const pm_camera* K, const pm_lens* lens,
+                 const double* R, const pm_camera* K_new, const pm_warp_params* p,
+                 uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info);
+int pm_undistort_map_dev(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new,
+                         int dw, int dh, int32_t* d_map);
+int pm_remap_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, int sstride, const int32_t* d_map, const pm_warp_params* p,
+                 uint8_t* d_dst, int dw, int dh, int dstride, uint8_t* d_valid, pm_warp_info* d_info);
+int pm_remap(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstride, const int32_t* map, const pm_warp_params* p,
+             uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info);
 
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference

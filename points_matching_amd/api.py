@@ -79,6 +79,8 @@ EXPORTS = [
     "pm_corners_dev", "pm_corners_replenish_dev", "pm_corners",
     "pm_describe_points_dev", "pm_describe_points_gather_dev", "pm_describe_points", "pm_describe_points_tables",
     "pm_warp_dev", "pm_warp", "pm_transform_points_dev", "pm_transform_points",
+    "pm_undistort_points_dev", "pm_undistort_points", "pm_distort_points_dev", "pm_distort_points",
+    "pm_undistort_dev", "pm_undistort", "pm_undistort_map_dev", "pm_remap_dev", "pm_remap",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -156,7 +158,7 @@ def warp_params(flags=0, border_value=0):
 
 
 class Camera(C.Structure):
-    """pm_camera: one pinhole camera shared by both views (fx, fy, cx, cy; no distortion)."""
+    """pm_camera: one pinhole camera shared by both views (fx, fy, cx, cy; no distortion: see Lens and undistort_points)."""
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
 
@@ -168,6 +170,35 @@ def _camera(K):
     if k.shape == (3, 3):
         return Camera(k[0, 0], k[1, 1], k[0, 2], k[1, 2])
     return Camera(*[float(v) for v in k.reshape(4)])
+
+
+class Lens(C.Structure):
+    """pm_lens: OpenCV's first five distortion coefficients in distCoeffs order (SPEC S79); lens() fills it."""
+    _fields_ = [("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double)]
+
+
+def lens(k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+    """k1, k2, k3 radial, p1, p2 tangential."""
+    return Lens(float(k1), float(k2), float(p1), float(p2), float(k3))
+
+
+def _lens(d):
+    """A Lens from a Lens, up to five coefficients (k1, k2, p1, p2, k3), or None (no distortion: NULL)."""
+    if d is None or isinstance(d, Lens):
+        return d
+    return lens(*[float(v) for v in np.asarray(d, np.float64).reshape(-1)])
+
+
+def _lens_model(K, dist, R, K_new):
+    """The four model arguments of the S79-S83 calls as ctypes values (None -> NULL); the tuple keeps them alive."""
+    k, d = _camera(K), _lens(dist)
+    n = None if K_new is None else _camera(K_new)
+    r = None
+    if R is not None:
+        r = np.ascontiguousarray(R, np.float64).reshape(-1)
+        if r.size != 9:
+            raise ValueError("R must hold 9 doubles")
+    return C.byref(k), (C.byref(d) if d is not None else None), _p(r), (C.byref(n) if n is not None else None), (k, d, r, n)
 
 
 class PnpView(C.Structure):
@@ -819,6 +850,94 @@ class Context:
         out = np.zeros((max(n, 1), 2), np.float32)
         _check(lib().pm_transform_points(self._h, _p(M), flags, _p(pts), n, _p(out)))
         return out[:n]
+
+    # -- lens distortion: points both ways, undistort an image, map + remap (SPEC S79-S83) -------------------------------
+    # K, K_new: a Camera, (fx, fy, cx, cy) or a 3 x 3 matrix (K_new None = K); dist: a Lens, up to five coefficients or None;
+    # R: 3 x 3 or None.  All four are host values read at call time.
+    def undistort_points_dev(self, K, dist, R, K_new, iters, tol_px, dpts_ptr, dn_ptr, cap, dout_ptr):
+        """Device pointers; dn_ptr (device int32 count) may be None = cap; dout may equal dpts.  Rejected rows are NaN pairs."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        _check(lib().pm_undistort_points_dev(self._h, k, d, r, n, iters, C.c_double(tol_px), C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                             C.c_void_p(dout_ptr)))
+
+    def undistort_points(self, K, dist, pts, R=None, K_new=None, iters=20, tol_px=1e-3):
+        """Host form: distorted pixels (n, 2) under K -> ideal pixels under K_new, (n, 2) f32 (cv::undistortPoints with P)."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        cnt = pts.shape[0]
+        out = np.zeros((max(cnt, 1), 2), np.float32)
+        _check(lib().pm_undistort_points(self._h, k, d, r, n, iters, C.c_double(tol_px), _p(pts), cnt, _p(out)))
+        return out[:cnt]
+
+    def distort_points_dev(self, K, dist, R, K_new, dpts_ptr, dn_ptr, cap, dout_ptr):
+        """Device pointers, as undistort_points_dev: ideal pixels under K_new -> distorted pixels under K."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        _check(lib().pm_distort_points_dev(self._h, k, d, r, n, C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap, C.c_void_p(dout_ptr)))
+
+    def distort_points(self, K, dist, pts, R=None, K_new=None):
+        """Host form: ideal pixels (n, 2) under K_new -> distorted pixels under K, (n, 2) f32."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        cnt = pts.shape[0]
+        out = np.zeros((max(cnt, 1), 2), np.float32)
+        _check(lib().pm_distort_points(self._h, k, d, r, n, _p(pts), cnt, _p(out)))
+        return out[:cnt]
+
+    def undistort_dev(self, dsrc_ptr, sw, sh, sstride, K, dist, R, K_new, prm, ddst_ptr, dw, dh, dstride, dvalid_ptr=None, dinfo_ptr=None):
+        """Device pointers; prm: WarpParams (PM_WARP_REPLICATE is the only flag).  dvalid (dw x dh bytes) and dinfo (a WarpInfo)
+        may be None."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        _check(lib().pm_undistort_dev(self._h, C.c_void_p(dsrc_ptr), sw, sh, sstride, k, d, r, n, C.byref(prm) if prm is not None else None,
+                                      C.c_void_p(ddst_ptr), dw, dh, dstride, C.c_void_p(dvalid_ptr or 0), C.c_void_p(dinfo_ptr or 0)))
+
+    def undistort(self, src, K, dist, R=None, K_new=None, prm=None, dw=None, dh=None, sw=None, dst=None):
+        """Host form: 8-bit grey image (sh, sw) -> (dst (dh, dw) u8, valid (dh, dw) u8, n_valid) (cv::undistort; with R and
+        K_new cv::initUndistortRectifyMap + cv::remap).  With sw given, src holds rows of src.shape[1] >= sw bytes; with dst (a
+        contiguous (dh, dstride >= dw) u8 array) given it is written in place and returned."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        src = np.ascontiguousarray(src, np.uint8)
+        if src.ndim != 2:
+            raise ValueError("src must be a 2-D array")
+        sh = src.shape[0]
+        sw = src.shape[1] if sw is None else sw
+        dw = sw if dw is None else dw
+        dh = sh if dh is None else dh
+        prm = prm or warp_params()
+        if dst is None:
+            dst = np.zeros((max(dh, 1), max(dw, 1)), np.uint8)
+        if dst.dtype != np.uint8 or dst.ndim != 2 or not dst.flags.c_contiguous or dst.shape[0] != max(dh, 1):
+            raise ValueError("dst must be a contiguous (dh, dstride) uint8 array")
+        valid = np.zeros((max(dh, 1), max(dw, 1)), np.uint8)
+        info = WarpInfo()
+        _check(lib().pm_undistort(self._h, _p(src), sw, sh, src.shape[1], k, d, r, n, C.byref(prm), _p(dst), dw, dh, dst.shape[1], _p(valid),
+                                  C.byref(info)))
+        return dst, valid, info.n_valid
+
+    def undistort_map_dev(self, K, dist, R, K_new, dw, dh, dmap_ptr):
+        """dmap: dw * dh int32 pairs (qx, qy) in 1/32 pixel, (INT32_MIN, INT32_MIN) = no usable position; 8-byte aligned."""
+        k, d, r, n, keep = _lens_model(K, dist, R, K_new)
+        _check(lib().pm_undistort_map_dev(self._h, k, d, r, n, dw, dh, C.c_void_p(dmap_ptr)))
+
+    def remap_dev(self, dsrc_ptr, sw, sh, sstride, dmap_ptr, prm, ddst_ptr, dw, dh, dstride, dvalid_ptr=None, dinfo_ptr=None):
+        """Device pointers; dmap as undistort_map_dev writes it (any int32 pairs are legal)."""
+        _check(lib().pm_remap_dev(self._h, C.c_void_p(dsrc_ptr), sw, sh, sstride, C.c_void_p(dmap_ptr), C.byref(prm) if prm is not None else None,
+                                  C.c_void_p(ddst_ptr), dw, dh, dstride, C.c_void_p(dvalid_ptr or 0), C.c_void_p(dinfo_ptr or 0)))
+
+    def remap(self, src, qmap, prm=None, sw=None):
+        """Host form: src (sh, sw) u8, qmap (dh, dw, 2) int32 -> (dst (dh, dw) u8, valid (dh, dw) u8, n_valid)."""
+        src = np.ascontiguousarray(src, np.uint8)
+        qmap = np.ascontiguousarray(qmap, np.int32)
+        if src.ndim != 2 or qmap.ndim != 3 or qmap.shape[2] != 2:
+            raise ValueError("src must be 2-D and qmap (dh, dw, 2)")
+        sh = src.shape[0]
+        sw = src.shape[1] if sw is None else sw
+        dh, dw = qmap.shape[:2]
+        prm = prm or warp_params()
+        dst, valid = np.zeros((max(dh, 1), max(dw, 1)), np.uint8), np.zeros((max(dh, 1), max(dw, 1)), np.uint8)
+        info = WarpInfo()
+        _check(lib().pm_remap(self._h, _p(src), sw, sh, src.shape[1], _p(qmap), C.byref(prm), _p(dst), dw, dh, dst.shape[1], _p(valid),
+                              C.byref(info)))
+        return dst, valid, info.n_valid
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

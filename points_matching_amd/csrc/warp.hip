@@ -7,7 +7,8 @@
 // pixel; a last row of exactly (0, 0, 1) takes a wave-uniform branch without the division.  Source taps are plain global
 // byte loads; a tap of weight zero is never loaded.  The four results leave as one dword where the address is 4-byte aligned
 // and all four are inside the row, as bytes otherwise (the caller's base pointer and stride may be odd).  n_valid: wave
-// ballots, four wave totals through LDS, one integer atomic per workgroup.
+// ballots, four wave totals through LDS, one integer atomic per workgroup.  The sample, the four-byte store, the ballot count and
+// the count clamp live in warp_core.hpp, which undistort.hip shares.
 //
 // warp_points: one thread per point, the count protocol of pm_track_lk_dev; d_out may be d_pts (a thread reads its own row
 // before it writes it).
@@ -15,10 +16,17 @@
 #include <cstdint>
 
 #include "pm_common.hpp"
+#include "warp_core.hpp"
 
 namespace {
 
-constexpr int TILE_W = 64, TILE_H = 16, PX = 4;          // output tile of a workgroup; pixels of a thread
+using warp_core::TILE_W;
+using warp_core::TILE_H;
+using warp_core::PX;
+using warp_core::sample;
+using warp_core::store4;
+using warp_core::clamped_count;
+
 constexpr int KNOWN_FLAGS = PM_WARP_INVERT | PM_WARP_REPLICATE | PM_WARP_AFFINE;
 
 struct Model {
@@ -73,37 +81,6 @@ struct WarpArgs {
     pm_warp_info* info;
 };
 
-// S77 for one pixel at the Q5 position (qx, qy): the grey value; ok = every tap of non-zero weight lies inside the source.
-template <bool REPLICATE>
-__device__ __forceinline__ int sample(const WarpArgs& a, int qx, int qy, bool& ok)
-{
-    const int x0 = qx >> 5, y0 = qy >> 5, ax = qx & 31, ay = qy & 31;
-    const int wx[2] = {32 - ax, ax}, wy[2] = {32 - ay, ay};
-    int sum = 0;
-    ok = true;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int wgt = wx[i] * wy[j];
-            if (wgt == 0) continue;                                   // never read, never outside
-            int xx = x0 + i, yy = y0 + j;
-            const bool in = static_cast<unsigned>(xx) < static_cast<unsigned>(a.sw) && static_cast<unsigned>(yy) < static_cast<unsigned>(a.sh);
-            ok = ok && in;
-            int v = a.border;
-            if (REPLICATE) {
-                xx = min(max(xx, 0), a.sw - 1);
-                yy = min(max(yy, 0), a.sh - 1);
-                v = a.src[static_cast<size_t>(yy) * a.sstride + xx];
-            } else if (in) {
-                v = a.src[static_cast<size_t>(yy) * a.sstride + xx];
-            }
-            sum += wgt * v;
-        }
-    }
-    return (sum + 512) >> 10;
-}
-
 // S76 from the homogeneous position: false = outside.
 template <bool UNIT_W>
 __device__ __forceinline__ bool position(double X, double Y, double W, int& qx, int& qy)
@@ -122,19 +99,6 @@ __device__ __forceinline__ bool position(double X, double Y, double W, int& qx, 
     qx = static_cast<int>(rint(fx));
     qy = static_cast<int>(rint(fy));
     return true;
-}
-
-// four bytes to p[0 .. cnt): one dword where it is aligned and whole, bytes otherwise
-__device__ __forceinline__ void store4(uint8_t* p, const int v[PX], int cnt)
-{
-    if (cnt == PX && (reinterpret_cast<uintptr_t>(p) & 3) == 0) {
-        *reinterpret_cast<unsigned*>(p) = static_cast<unsigned>(v[0]) | (static_cast<unsigned>(v[1]) << 8) |
-                                          (static_cast<unsigned>(v[2]) << 16) | (static_cast<unsigned>(v[3]) << 24);
-    } else {
-#pragma unroll
-        for (int j = 0; j < PX; ++j)
-            if (j < cnt) p[j] = static_cast<uint8_t>(v[j]);
-    }
 }
 
 template <bool REPLICATE, bool UNIT_W>
@@ -191,23 +155,13 @@ __global__ __launch_bounds__(256) void warp_bilinear(WarpArgs a)
         if (a.valid) store4(a.valid + static_cast<size_t>(y) * a.dw + x, ok, cnt);
     }
     if (a.info) {                                                   // (kernel argument: the same for every thread)
-        int total = 0;
-#pragma unroll
-        for (int j = 0; j < PX; ++j) total += __popcll(__ballot(ok[j] != 0));
-        if ((tid & 63) == 0) s_cnt[tid >> 6] = total;
-        __syncthreads();
+        warp_core::block_valid_totals(ok, s_cnt, tid);
         if (tid == 0) {
-            const int sum = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+            const int sum = warp_core::block_valid_sum(s_cnt);
             if (sum) atomicAdd(&a.info->n_valid, sum);
             if (blockIdx.x == 0 && blockIdx.y == 0) a.info->status = mdl.status;
         }
     }
-}
-
-__device__ __forceinline__ int clamped_count(const int32_t* d_n, int cap)
-{
-    const int n = d_n ? *d_n : cap;            // (the -1 that the point sources write on overflow counts as 0)
-    return n < 0 ? 0 : (n > cap ? cap : n);
 }
 
 // S78

@@ -14,6 +14,7 @@
 //          [--matcher track [--lk-radius R] [--lk-levels L] [--lk-fb T]
 //                           [--points dog|corners [--corner-dist D] [--corner-quality Q] [--corner-min-eig M]]]
 //          [--align OUT.pgm [--align-model homography|affine|similarity]]
+//   pm_cli --undistort OUT.pgm --img1 IN.pgm --camera fx,fy,cx,cy --lens k1,k2,p1,p2,k3 [--new-camera fx,fy,cx,cy] [--json]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -37,6 +38,11 @@
 // B and A being the mean absolute grey differences to image 1 over the V valid pixels, of image 2 as it is and warped.  No F
 // is estimated, so the residual report is not printed; --json, --guided, --epilines, --print-epilines and --gpus N / --mgpu
 // are usage errors with it.
+// --undistort OUT.pgm (with --img1 alone, --camera and --lens; docs/SPEC.md S79-S83): the image as an ideal pinhole camera
+// (--new-camera, default --camera) would have taken it, by pm_undistort_dev with border 0; OUT.pgm is written, one line
+//   undistort: valid=V
+// is printed (with --json the record {"undistort": {"width": W, "height": H, "n_valid": V}} instead) and the tool exits, as
+// with --extract-only.  A --camera / --new-camera that is not four numbers or a --lens that is not five is a usage error.
 // --descriptor bits (with --img1/--img2; default grad): 256-bit steered binary descriptors (docs/SPEC.md S58-S60) in place of
 // the 128-D gradient rows: the descriptor matrices are uint8 with 32 columns, every path below matches them by Hamming
 // distance, and with --features device (pm_detect_describe_bits_dev) the plain matcher reads them through
@@ -286,6 +292,55 @@ int run_align(pm_ctx* ctx, const std::string& model, const std::string& out_path
     return 0;
 }
 
+// "a,b,c": exactly n finite numbers separated by commas
+bool parse_numbers(const char* text, int n, double* out)
+{
+    const char* p = text;
+    for (int i = 0; i < n; ++i) {
+        char* end = nullptr;
+        out[i] = strtod(p, &end);
+        if (end == p || !(out[i] - out[i] == 0.0)) return false;
+        if (*end != (i + 1 < n ? ',' : '\0')) return false;
+        p = end + 1;
+    }
+    return true;
+}
+
+// --undistort: upload, pm_undistort_dev, download; the PGM and the report
+int run_undistort(int device, const std::string& out_path, const std::string& in_path, const pm_camera& K, const pm_lens& lens, const pm_camera* K_new,
+                  bool json)
+{
+    pm_feat::Image im;
+    std::string err;
+    if (!pm_feat::load_pnm_gray(in_path, im, err)) { fprintf(stderr, "pm_cli: %s\n", err.c_str()); return 1; }
+    pm_ctx* ctx = nullptr;
+    int rc = pm_ctx_create(device, &ctx);
+    if (rc != PM_OK) return fail("pm_ctx_create", rc);
+    const int w = im.w, h = im.h;
+    const size_t px = static_cast<size_t>(w) * h;
+    void *d_src = nullptr, *d_dst = nullptr, *d_info = nullptr;
+    rc = pm_device_alloc(ctx, px, &d_src);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, px, &d_dst);
+    if (rc == PM_OK) rc = pm_device_alloc(ctx, sizeof(pm_warp_info), &d_info);
+    if (rc == PM_OK) rc = pm_device_upload(ctx, d_src, im.px.data(), px);
+    pm_warp_params wp;
+    wp.flags = 0; wp.border_value = 0; wp.reserved[0] = wp.reserved[1] = 0;
+    if (rc == PM_OK)
+        rc = pm_undistort_dev(ctx, static_cast<const uint8_t*>(d_src), w, h, w, &K, &lens, nullptr, K_new, &wp, static_cast<uint8_t*>(d_dst), w, h, w,
+                              nullptr, static_cast<pm_warp_info*>(d_info));
+    std::vector<uint8_t> dst(px);
+    pm_warp_info info = {0, 0};
+    if (rc == PM_OK) rc = pm_device_download(ctx, dst.data(), d_dst, px);
+    if (rc == PM_OK) rc = pm_device_download(ctx, &info, d_info, sizeof info);
+    for (void* p : {d_src, d_dst, d_info}) pm_device_free(ctx, p);
+    if (rc != PM_OK) { fail("--undistort", rc); pm_ctx_destroy(ctx); return 1; }
+    pm_ctx_destroy(ctx);
+    if (!write_pgm(out_path, dst, w, h)) return 1;
+    if (json) printf("{\"undistort\": {\"width\": %d, \"height\": %d, \"n_valid\": %d}}\n", w, h, info.n_valid);
+    else printf("undistort: valid=%d\n", info.n_valid);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -302,6 +357,7 @@ int main(int argc, char** argv)
     float lk_fb = 0.f;
     std::string points = "dog", align_pgm, align_model = "homography";
     bool align_model_given = false;
+    std::string undistort_pgm, camera_arg, lens_arg, new_camera_arg;
     bool points_given = false, corner_opt_given = false;
     float corner_dist = 8.f, corner_quality = 0.01f, corner_min_eig = 1e-4f;
     int max_kp = 4000;
@@ -323,6 +379,10 @@ int main(int argc, char** argv)
         else if (a == "--points") { points = val("--points"); points_given = true; }
         else if (a == "--align") align_pgm = val("--align");
         else if (a == "--align-model") { align_model = val("--align-model"); align_model_given = true; }
+        else if (a == "--undistort") undistort_pgm = val("--undistort");
+        else if (a == "--camera") camera_arg = val("--camera");
+        else if (a == "--lens") lens_arg = val("--lens");
+        else if (a == "--new-camera") new_camera_arg = val("--new-camera");
         else if (a == "--corner-dist") { corner_dist = strtof(val("--corner-dist"), nullptr); corner_opt_given = true; }
         else if (a == "--corner-quality") { corner_quality = strtof(val("--corner-quality"), nullptr); corner_opt_given = true; }
         else if (a == "--corner-min-eig") { corner_min_eig = strtof(val("--corner-min-eig"), nullptr); corner_opt_given = true; }
@@ -357,6 +417,27 @@ int main(int argc, char** argv)
         else if (a == "--quiet") quiet = true;
         else if (a == "--json") json = true;
         else { fprintf(stderr, "pm_cli: unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (undistort_pgm.empty() && !(camera_arg.empty() && lens_arg.empty() && new_camera_arg.empty())) {
+        fprintf(stderr, "pm_cli: --camera, --lens and --new-camera need --undistort OUT.pgm\n");
+        return 2;
+    }
+    if (!undistort_pgm.empty()) {
+        // ---- one image through pm_undistort_dev, then exit (no features, no matcher)
+        if (img1_path.empty() || camera_arg.empty() || lens_arg.empty()) {
+            fprintf(stderr, "pm_cli: --undistort needs --img1 IN.pgm --camera fx,fy,cx,cy --lens k1,k2,p1,p2,k3\n");
+            return 2;
+        }
+        double c[4], l[5], nc[4];
+        if (!parse_numbers(camera_arg.c_str(), 4, c)) { fprintf(stderr, "pm_cli: --camera fx,fy,cx,cy (four numbers)\n"); return 2; }
+        if (!parse_numbers(lens_arg.c_str(), 5, l)) { fprintf(stderr, "pm_cli: --lens k1,k2,p1,p2,k3 (five numbers)\n"); return 2; }
+        if (!new_camera_arg.empty() && !parse_numbers(new_camera_arg.c_str(), 4, nc)) {
+            fprintf(stderr, "pm_cli: --new-camera fx,fy,cx,cy (four numbers)\n");
+            return 2;
+        }
+        const pm_camera K = {c[0], c[1], c[2], c[3]}, Kn = {nc[0], nc[1], nc[2], nc[3]};
+        const pm_lens lens = {l[0], l[1], l[2], l[3], l[4]};
+        return run_undistort(device, undistort_pgm, img1_path, K, lens, new_camera_arg.empty() ? nullptr : &Kn, json);
     }
     Matrix d1, d2, k1, k2;
     const bool from_images = !img1_path.empty();
@@ -592,7 +673,7 @@ int main(int argc, char** argv)
     if (desc1.empty() || desc2.empty() || kp1.empty() || kp2.empty()) {
         fprintf(stderr, "usage: pm_cli (--img1 L.pgm --img2 R.pgm | --desc1 A --desc2 B --kp1 KA --kp2 KB) [--filter midpoint|ratio|cross|cross-ratio] "
                         "[--ratio r] [--method 7point-lmeds|ransac8] [--iters n] [--thresh px] [--seed s] [--f-scale opencv|unit] "
-                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device|corners] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--align out.pgm [--align-model homography|affine|similarity]] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
+                        "[--matcher bf|flann|track [--lk-radius r] [--lk-levels l] [--lk-fb px] [--points dog|corners [--corner-dist px] [--corner-quality q] [--corner-min-eig m]]] [--guided tau_px] [--features host|device|corners] [--descriptor grad|bits] [--knn-hint auto|int|u8|unit] [--align out.pgm [--align-model homography|affine|similarity]] [--undistort out.pgm --camera fx,fy,cx,cy --lens k1,k2,p1,p2,k3 [--new-camera fx,fy,cx,cy]] [--gpus N] [--print-epilines] [--epilines out.ppm] [--json] [--quiet]\n"
                         "  (default matcher bf = exact brute force, main.cpp:43; the reference's active one is --matcher flann, main.cpp:44)\n");
         return 2;
     }
