@@ -1299,6 +1299,62 @@ int pm_remap_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, int sstride,
 int pm_remap(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstride, const int32_t* map, const pm_warp_params* p,
              uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info);
 
+/* ---- dense stereo: rectifying rotations, block matching, depth at points — docs/SPEC.md S84-S88 ------------------------------
+ * From a calibrated pair to metric 3-D points for pm_ransac_pnp*, on one stream: pm_stereo_rectify gives the R arguments of
+ * pm_undistort* (cv::stereoRectify's R1, R2), pm_undistort_dev rectifies both images, pm_stereo_bm_dev gives a disparity map
+ * (cv::StereoBM: sums of absolute differences, winner, uniqueness, sub-pixel, all in integers), pm_stereo_lr_check_dev
+ * removes what the right image does not confirm, pm_stereo_points_dev reads the depth at given points
+ * (cv::reprojectImageTo3D at those pixels).  Every output is a function of the inputs alone (bit for bit the plain-C
+ * statement tests/stereo_ref.c).
+ *
+ *   pm_stereo_rectify   host only, no launch, fp64 (S84).  R, t: the pose of S35, x2 ~ R x1 + t.  R1, R2: camera frame ->
+ *             rectified frame of view 1 and view 2; with one K_new for both views corresponding points share a row and
+ *             x_left - x_right = fx_new * baseline / Z.  *left_is_view2 != 0: view 2 is the left image.  PM_E_INVALID: null
+ *             pointers, non-finite input.  PM_E_NO_MODEL (outputs zero): no baseline, or an optical axis along it.
+ *             PM_E_UNSUPPORTED (outputs zero): a vertical rig, |c_y| > |c_x| for the centre c of camera 2.
+ *   pm_stereo_bm_dev   8-bit rectified pair of one size -> int16 disparities in 1/16 pixel, PM_STEREO_INVALID where there is
+ *             none (S85).  Disparities min_disp .. min_disp + num_disp - 1, window (2 radius + 1)^2; 1 <= radius <= 10,
+ *             1 <= num_disp <= 256, -1024 <= min_disp, min_disp + num_disp - 1 <= 1024, 0 <= uniqueness <= 99 (per cent; 0
+ *             rejects nothing).  Only pixels for which every disparity is testable are computed.  PM_STEREO_FROM_RIGHT: the
+ *             disparity of the right image's pixels, same sign.  dstride in elements.  One launch; d_info (may be NULL):
+ *             status always 0, n_valid = pixels that are not PM_STEREO_INVALID.  pm_stereo_bm: the blocking host form;
+ *             lr_max_diff16 >= 0 runs the left pass, the FROM_RIGHT pass and pm_stereo_lr_check_dev in one call (and is
+ *             PM_E_INVALID together with PM_STEREO_FROM_RIGHT), below 0 there is no check.
+ *   pm_stereo_lr_check_dev   in place on the left map (S86): a valid value v at (x, y) survives when the right map at
+ *             (x - floor((v + 8) / 16), y) exists, is valid and differs from v by at most max_diff16.  One launch; n_valid is
+ *             the count afterwards.
+ *   pm_stereo_points_dev   rows (x, y) in the rectified left image -> rows (X, Y, Z) f32 (S87): the map value v at the
+ *             rounded pixel, Z = fx * baseline * 16 / v, with R (host, 9 doubles, or NULL) R^T (X, Y, Z): with R1 the frame of
+ *             that camera before rectification.  Three quiet NaNs where a coordinate is not finite, the pixel is outside the
+ *             map, v is PM_STEREO_INVALID or v <= 0: S36 makes such rows outliers of pm_ransac_pnp*.  The count protocol of
+ *             pm_transform_points_dev.  One launch.  pm_stereo_points: the blocking host form.
+ * PM_E_INVALID: null required pointers, a parameter out of range, unknown flag bits, reserved != 0, a size below 1, a stride
+ * below the width, max_diff16, cap or n < 0, an output range (the map, the xyz rows, the info record) that overlaps an input range or another
+ * output, in the host forms as in the _dev forms, a bad K_rect, baseline not finite
+ * or not > 0, a non-finite R.  PM_E_UNSUPPORTED: more than 100 000 000 pixels, cap == 0 (n == 0), and a capturing stream, refused
+ * before anything else.  An image too small to hold a computed pixel is not an error: every pixel is PM_STEREO_INVALID.
+ * Timing names: "stereo_bm", "stereo_lr_check", "stereo_points". */
+#define PM_STEREO_INVALID (-32768)
+#define PM_STEREO_FROM_RIGHT 1
+typedef struct pm_stereo_params {
+    int32_t min_disp, num_disp, radius, uniqueness, flags, reserved[3];
+} pm_stereo_params;
+typedef struct pm_stereo_info {
+    int32_t status;  /* always 0 */
+    int32_t n_valid;
+} pm_stereo_info;
+int pm_stereo_rectify(const double R[9], const double t[3], double R1[9], double R2[9], double* baseline, int* left_is_view2);
+int pm_stereo_bm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int w, int h, int lstride, int rstride,
+                     const pm_stereo_params* p, int16_t* d_disp, int dstride, pm_stereo_info* d_info);
+int pm_stereo_bm(pm_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int lstride, int rstride,
+                 const pm_stereo_params* p, int lr_max_diff16, int16_t* disp, int dstride, pm_stereo_info* info);
+int pm_stereo_lr_check_dev(pm_ctx* ctx, int16_t* d_left, const int16_t* d_right, int w, int h, int lstride, int rstride,
+                           int max_diff16, pm_stereo_info* d_info);
+int pm_stereo_points_dev(pm_ctx* ctx, const int16_t* d_disp, int w, int h, int dstride, const pm_camera* K_rect, double baseline,
+                         const double* R, const float* d_pts, const int32_t* d_n, int cap, float* d_xyz);
+int pm_stereo_points(pm_ctx* ctx, const int16_t* disp, int w, int h, int dstride, const pm_camera* K_rect, double baseline,
+                     const double* R, const float* pts, int n, float* xyz);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

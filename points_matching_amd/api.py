@@ -81,6 +81,7 @@ EXPORTS = [
     "pm_warp_dev", "pm_warp", "pm_transform_points_dev", "pm_transform_points",
     "pm_undistort_points_dev", "pm_undistort_points", "pm_distort_points_dev", "pm_distort_points",
     "pm_undistort_dev", "pm_undistort", "pm_undistort_map_dev", "pm_remap_dev", "pm_remap",
+    "pm_stereo_rectify", "pm_stereo_bm_dev", "pm_stereo_bm", "pm_stereo_lr_check_dev", "pm_stereo_points_dev", "pm_stereo_points",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -199,6 +200,41 @@ def _lens_model(K, dist, R, K_new):
         if r.size != 9:
             raise ValueError("R must hold 9 doubles")
     return C.byref(k), (C.byref(d) if d is not None else None), _p(r), (C.byref(n) if n is not None else None), (k, d, r, n)
+
+
+class StereoParams(C.Structure):
+    """pm_stereo_params (include/pm.h, SPEC S85); stereo_params() fills it."""
+    _fields_ = [("min_disp", C.c_int32), ("num_disp", C.c_int32), ("radius", C.c_int32), ("uniqueness", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class StereoInfo(C.Structure):
+    """pm_stereo_info: status always 0; n_valid = pixels of the map that are not PM_STEREO_INVALID."""
+    _fields_ = [("status", C.c_int32), ("n_valid", C.c_int32)]
+
+
+PM_STEREO_INVALID = -32768
+PM_STEREO_FROM_RIGHT = 1
+
+
+def stereo_params(num_disp=64, radius=4, min_disp=0, uniqueness=0, flags=0):
+    """Disparities min_disp .. min_disp + num_disp - 1, window (2 radius + 1)^2, uniqueness in per cent (0 rejects nothing),
+    flags: 0 or PM_STEREO_FROM_RIGHT."""
+    return StereoParams(min_disp, num_disp, radius, uniqueness, flags, (C.c_int32 * 3)(0, 0, 0))
+
+
+def stereo_rectify(R, t):
+    """Host only (SPEC S84): the pose x2 ~ R x1 + t -> (rc, R1 (3, 3), R2 (3, 3), baseline, left_is_view2); rc is PM_OK,
+    PM_E_NO_MODEL or PM_E_UNSUPPORTED (outputs zero), anything else raises PmError."""
+    R = np.ascontiguousarray(R, np.float64).reshape(-1)
+    t = np.ascontiguousarray(t, np.float64).reshape(-1)
+    if R.size != 9 or t.size != 3:
+        raise ValueError("R must hold 9 doubles and t 3")
+    R1, R2, b, flag = np.zeros(9), np.zeros(9), C.c_double(0.0), C.c_int(0)
+    rc = lib().pm_stereo_rectify(_p(R), _p(t), _p(R1), _p(R2), C.byref(b), C.byref(flag))
+    if rc not in (PM_OK, PM_E_NO_MODEL, PM_E_UNSUPPORTED):
+        _check(rc)
+    return rc, R1.reshape(3, 3), R2.reshape(3, 3), b.value, flag.value
 
 
 class PnpView(C.Structure):
@@ -938,6 +974,63 @@ class Context:
         _check(lib().pm_remap(self._h, _p(src), sw, sh, src.shape[1], _p(qmap), C.byref(prm), _p(dst), dw, dh, dst.shape[1], _p(valid),
                               C.byref(info)))
         return dst, valid, info.n_valid
+
+    # -- dense stereo on a rectified pair: block matching, left-right check, depth at points (SPEC S85-S87) ----------------
+    def stereo_bm_dev(self, dleft_ptr, dright_ptr, w, h, lstride, rstride, prm, ddisp_ptr, dstride, dinfo_ptr=None):
+        """Device pointers; prm: StereoParams; ddisp: int16 rows of dstride elements; dinfo (a StereoInfo, 8 bytes) may be None."""
+        _check(lib().pm_stereo_bm_dev(self._h, C.c_void_p(dleft_ptr), C.c_void_p(dright_ptr), w, h, lstride, rstride,
+                                      C.byref(prm) if prm is not None else None, C.c_void_p(ddisp_ptr), dstride, C.c_void_p(dinfo_ptr or 0)))
+
+    def stereo_bm(self, left, right, prm=None, lr_max_diff16=-1, w=None, disp=None):
+        """Host form: a rectified 8-bit pair (h, w) -> (disp (h, w) int16 in 1/16 pixel, n_valid) (cv::StereoBM without its
+        pre-filter).  lr_max_diff16 >= 0 adds the FROM_RIGHT pass and the left-right check.  With w given, the images hold rows of
+        shape[1] >= w bytes; with disp (a contiguous (h, dstride >= w) int16 array) given it is written in place and returned."""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        if left.ndim != 2 or right.ndim != 2 or left.shape[0] != right.shape[0]:
+            raise ValueError("left and right must be 2-D arrays of one height")
+        h = left.shape[0]
+        w = left.shape[1] if w is None else w
+        prm = prm or stereo_params()
+        if disp is None:
+            disp = np.zeros((max(h, 1), max(w, 1)), np.int16)
+        if disp.dtype != np.int16 or disp.ndim != 2 or not disp.flags.c_contiguous or disp.shape[0] != max(h, 1):
+            raise ValueError("disp must be a contiguous (h, dstride) int16 array")
+        info = StereoInfo()
+        _check(lib().pm_stereo_bm(self._h, _p(left), _p(right), w, h, left.shape[1], right.shape[1], C.byref(prm), lr_max_diff16, _p(disp),
+                                  disp.shape[1], C.byref(info)))
+        return disp, info.n_valid
+
+    def stereo_lr_check_dev(self, dleft_ptr, dright_ptr, w, h, lstride, rstride, max_diff16, dinfo_ptr=None):
+        """Device pointers to the two int16 maps (strides in elements); the left map is checked in place."""
+        _check(lib().pm_stereo_lr_check_dev(self._h, C.c_void_p(dleft_ptr), C.c_void_p(dright_ptr), w, h, lstride, rstride, max_diff16,
+                                            C.c_void_p(dinfo_ptr or 0)))
+
+    def stereo_points_dev(self, ddisp_ptr, w, h, dstride, K_rect, baseline, R, dpts_ptr, dn_ptr, cap, dxyz_ptr):
+        """Device pointers; K_rect as the other cameras, R (3 x 3 or None) a host value; dn_ptr (device int32 count) may be None =
+        cap.  Rows without a depth are three NaNs."""
+        k = _camera(K_rect)
+        r = None if R is None else np.ascontiguousarray(R, np.float64).reshape(-1)
+        if r is not None and r.size != 9:
+            raise ValueError("R must hold 9 doubles")
+        _check(lib().pm_stereo_points_dev(self._h, C.c_void_p(ddisp_ptr), w, h, dstride, C.byref(k), C.c_double(baseline), _p(r),
+                                          C.c_void_p(dpts_ptr), C.c_void_p(dn_ptr or 0), cap, C.c_void_p(dxyz_ptr)))
+
+    def stereo_points(self, disp, K_rect, baseline, pts, R=None, w=None):
+        """Host form: disp (h, w) int16, pts (n, 2) in the rectified left image -> (n, 3) f32 (cv::reprojectImageTo3D at pts)."""
+        disp = np.ascontiguousarray(disp, np.int16)
+        if disp.ndim != 2:
+            raise ValueError("disp must be a 2-D array")
+        h = disp.shape[0]
+        w = disp.shape[1] if w is None else w
+        k = _camera(K_rect)
+        r = None if R is None else np.ascontiguousarray(R, np.float64).reshape(-1)
+        if r is not None and r.size != 9:
+            raise ValueError("R must hold 9 doubles")
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = pts.shape[0]
+        out = np.zeros((max(n, 1), 3), np.float32)
+        _check(lib().pm_stereo_points(self._h, _p(disp), w, h, disp.shape[1], C.byref(k), C.c_double(baseline), _p(r), _p(pts), n, _p(out)))
+        return out[:n]
 
     def bf_knn_l2_u8(self, q, t, k):
         """u8 descriptor rows, host arrays (pm_bf_knn_l2_u8)."""

@@ -21,7 +21,7 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
-           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip"]
+           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -55,7 +55,10 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # image warp and point transform (S75-S78): four pixels per thread with fp64 positions; warp_bilinear must not spill
          "warp.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # lens distortion (S79-S83): fp64 polynomial positions, four pixels per thread; no kernel may use scratch or spill
-         "undistort.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "undistort.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # dense stereo (S84-S88): a lane owns a disparity, two image tiles and a ring of column sums in LDS; no kernel may use
+         # scratch or spill
+         "stereo.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

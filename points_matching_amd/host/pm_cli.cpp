@@ -15,6 +15,7 @@
 //                           [--points dog|corners [--corner-dist D] [--corner-quality Q] [--corner-min-eig M]]]
 //          [--align OUT.pgm [--align-model homography|affine|similarity]]
 //   pm_cli --undistort OUT.pgm --img1 IN.pgm --camera fx,fy,cx,cy --lens k1,k2,p1,p2,k3 [--new-camera fx,fy,cx,cy] [--json]
+//   pm_cli --stereo OUT.pgm --img1 L.pgm --img2 R.pgm --num-disp N [--min-disp M] [--radius R] [--uniqueness U] [--lr-check T16] [--json]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -38,6 +39,14 @@
 // B and A being the mean absolute grey differences to image 1 over the V valid pixels, of image 2 as it is and warped.  No F
 // is estimated, so the residual report is not printed; --json, --guided, --epilines, --print-epilines and --gpus N / --mgpu
 // are usage errors with it.
+// --stereo OUT.pgm (with --img1, --img2, an already rectified pair of one size, and --num-disp; docs/SPEC.md S85-S88): the
+// disparity map of the left image by pm_stereo_bm (radius default 4, uniqueness 0; --lr-check T16 >= 0 adds the right map and the
+// left-right check).  OUT.pgm is a 16-bit binary PGM (maxval 65535, most significant byte first) holding v - 16 * min_disp + 1
+// and 0 where there is no disparity; one line
+//   stereo: valid=V
+// is printed (with --json the record {"stereo": {"width": W, "height": H, "n_valid": V}}) and the tool exits.
+// Any switch of another mode with it (--undistort, --align, --guided, --epilines, --matcher, --features, --filter, ...) is a
+// usage error.
 // --undistort OUT.pgm (with --img1 alone, --camera and --lens; docs/SPEC.md S79-S83): the image as an ideal pinhole camera
 // (--new-camera, default --camera) would have taken it, by pm_undistort_dev with border 0; OUT.pgm is written, one line
 //   undistort: valid=V
@@ -341,6 +350,41 @@ int run_undistort(int device, const std::string& out_path, const std::string& in
     return 0;
 }
 
+// --stereo: an already rectified pair through pm_stereo_bm (with --lr-check T16 >= 0 also the FROM_RIGHT pass and the left-right
+// check); a 16-bit PGM, most significant byte first: v - 16 * min_disp + 1, 0 where there is no disparity
+int run_stereo(int device, const std::string& out_path, const std::string& left_path, const std::string& right_path, const pm_stereo_params& prm,
+               int lr_check, bool json)
+{
+    pm_feat::Image im1, im2;
+    std::string err;
+    if (!pm_feat::load_pnm_gray(left_path, im1, err) || !pm_feat::load_pnm_gray(right_path, im2, err)) { fprintf(stderr, "pm_cli: %s\n", err.c_str()); return 1; }
+    if (im1.w != im2.w || im1.h != im2.h) { fprintf(stderr, "pm_cli: --stereo needs two images of one size\n"); return 1; }
+    pm_ctx* ctx = nullptr;
+    int rc = pm_ctx_create(device, &ctx);
+    if (rc != PM_OK) return fail("pm_ctx_create", rc);
+    const int w = im1.w, h = im1.h;
+    const size_t px = static_cast<size_t>(w) * h;
+    std::vector<int16_t> disp(px);
+    pm_stereo_info info = {0, 0};
+    rc = pm_stereo_bm(ctx, im1.px.data(), im2.px.data(), w, h, w, w, &prm, lr_check, disp.data(), w, &info);
+    if (rc != PM_OK) { fail("--stereo", rc); pm_ctx_destroy(ctx); return 1; }
+    pm_ctx_destroy(ctx);
+    std::vector<uint8_t> out(px * 2);
+    for (size_t i = 0; i < px; ++i) {
+        const int v = disp[i] == PM_STEREO_INVALID ? 0 : disp[i] - 16 * prm.min_disp + 1;
+        out[2 * i] = static_cast<uint8_t>(v >> 8);
+        out[2 * i + 1] = static_cast<uint8_t>(v & 255);
+    }
+    FILE* f = fopen(out_path.c_str(), "wb");
+    if (!f) { fprintf(stderr, "pm_cli: cannot write %s\n", out_path.c_str()); return 1; }
+    fprintf(f, "P5\n%d %d\n65535\n", w, h);
+    const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (fclose(f) != 0 || !ok) { fprintf(stderr, "pm_cli: cannot write %s\n", out_path.c_str()); return 1; }
+    if (json) printf("{\"stereo\": {\"width\": %d, \"height\": %d, \"n_valid\": %d}}\n", w, h, info.n_valid);
+    else printf("stereo: valid=%d\n", info.n_valid);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -358,6 +402,10 @@ int main(int argc, char** argv)
     std::string points = "dog", align_pgm, align_model = "homography";
     bool align_model_given = false;
     std::string undistort_pgm, camera_arg, lens_arg, new_camera_arg;
+    std::string stereo_pgm;
+    pm_stereo_params stereo_prm = {0, 0, 4, 0, 0, {0, 0, 0}};
+    int stereo_lr = -1;
+    bool stereo_opt_given = false;
     bool points_given = false, corner_opt_given = false;
     float corner_dist = 8.f, corner_quality = 0.01f, corner_min_eig = 1e-4f;
     int max_kp = 4000;
@@ -380,6 +428,12 @@ int main(int argc, char** argv)
         else if (a == "--align") align_pgm = val("--align");
         else if (a == "--align-model") { align_model = val("--align-model"); align_model_given = true; }
         else if (a == "--undistort") undistort_pgm = val("--undistort");
+        else if (a == "--stereo") stereo_pgm = val("--stereo");
+        else if (a == "--num-disp") { stereo_prm.num_disp = atoi(val("--num-disp")); stereo_opt_given = true; }
+        else if (a == "--min-disp") { stereo_prm.min_disp = atoi(val("--min-disp")); stereo_opt_given = true; }
+        else if (a == "--radius") { stereo_prm.radius = atoi(val("--radius")); stereo_opt_given = true; }
+        else if (a == "--uniqueness") { stereo_prm.uniqueness = atoi(val("--uniqueness")); stereo_opt_given = true; }
+        else if (a == "--lr-check") { stereo_lr = atoi(val("--lr-check")); stereo_opt_given = true; }
         else if (a == "--camera") camera_arg = val("--camera");
         else if (a == "--lens") lens_arg = val("--lens");
         else if (a == "--new-camera") new_camera_arg = val("--new-camera");
@@ -421,6 +475,26 @@ int main(int argc, char** argv)
     if (undistort_pgm.empty() && !(camera_arg.empty() && lens_arg.empty() && new_camera_arg.empty())) {
         fprintf(stderr, "pm_cli: --camera, --lens and --new-camera need --undistort OUT.pgm\n");
         return 2;
+    }
+    if (stereo_pgm.empty() && stereo_opt_given) {
+        fprintf(stderr, "pm_cli: --num-disp, --min-disp, --radius, --uniqueness and --lr-check need --stereo OUT.pgm\n");
+        return 2;
+    }
+    if (!stereo_pgm.empty()) {
+        // ---- a rectified pair through pm_stereo_bm, then exit (no features, no matcher)
+        if (img1_path.empty() || img2_path.empty() || stereo_prm.num_disp < 1 || !undistort_pgm.empty()) {
+            fprintf(stderr, "pm_cli: --stereo needs --img1 L.pgm --img2 R.pgm --num-disp N (and no --undistort)\n");
+            return 2;
+        }
+        const bool other_mode = !align_pgm.empty() || align_model_given || guided || !epi_ppm.empty() || print_epi || matcher != "bf" ||
+                                features != "host" || filter_given || descriptor_given || points_given || corner_opt_given || extract_only ||
+                                !save_prefix.empty() || !knn_hint.empty() || force_mgpu || gpus != 1 || iters_given || !desc1.empty() ||
+                                !desc2.empty() || !kp1.empty() || !kp2.empty();
+        if (other_mode) {
+            fprintf(stderr, "pm_cli: --stereo takes --img1, --img2, its own options, --device and --json only\n");
+            return 2;
+        }
+        return run_stereo(device, stereo_pgm, img1_path, img2_path, stereo_prm, stereo_lr, json);
     }
     if (!undistort_pgm.empty()) {
         // ---- one image through pm_undistort_dev, then exit (no features, no matcher)
