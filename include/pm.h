@@ -1355,6 +1355,34 @@ int pm_stereo_points_dev(pm_ctx* ctx, const int16_t* d_disp, int w, int h, int d
 int pm_stereo_points(pm_ctx* ctx, const int16_t* disp, int w, int h, int dstride, const pm_camera* K_rect, double baseline,
                      const double* R, const float* pts, int n, float* xyz);
 
+/* ---- semi-global stereo matching: census cost, 4 or 8 paths — docs/SPEC.md S89-S92 ------------------------------------------
+ * A second matcher for the chain above (cv::StereoSGBM, libSGM): where the block matcher lets every pixel decide alone, the
+ * costs of a pixel's disparities are summed along 4 or 8 paths with a penalty p1 for a step of one disparity and p2 for a
+ * larger one, so textureless and repetitive regions take the disparity of their surroundings.  All integers: the map is a
+ * function of the inputs alone (bit for bit the plain-C statement tests/sgm_ref.c).  The map has pm_stereo_bm's format:
+ * pm_stereo_lr_check_dev and pm_stereo_points_dev take it unchanged.
+ *
+ *   pm_stereo_sgm_dev   8-bit rectified pair of one size -> int16 disparities in 1/16 pixel.  The cost of (x, y, d) is the
+ *             number of differing bits of two 9 x 7 census words (S89, S90), 0..62; the path sums of S91 use
+ *             0 <= p1 <= p2 <= 1023 and paths = 4 (horizontal, vertical) or 8 (and diagonal); winner, uniqueness and
+ *             sub-pixel step are S85's on the sum over the paths (S92).  1 <= num_disp <= 256, -1024 <= min_disp,
+ *             min_disp + num_disp - 1 <= 1024, 0 <= uniqueness <= 99, flags 0 or PM_STEREO_FROM_RIGHT, reserved 0.  Computed
+ *             pixels: rows 3 .. h - 4 and the columns where every disparity is testable with the window's margin of 4; every
+ *             other pixel is PM_STEREO_INVALID.  The workspace (two planes of census words and the u16 sums, computed
+ *             pixels x num_disp) comes from the context's arena; nothing returns to the host.  paths + 1 launches.  d_info
+ *             (may be NULL): status 0, n_valid.
+ *   pm_stereo_sgm   the blocking host form; lr_max_diff16 >= 0 runs the left map, the FROM_RIGHT map and
+ *             pm_stereo_lr_check_dev (and is PM_E_INVALID together with PM_STEREO_FROM_RIGHT).
+ * PM_E_INVALID and PM_E_UNSUPPORTED as for pm_stereo_bm*; also PM_E_UNSUPPORTED: computed pixels x num_disp above 2^30.
+ * Timing names: "sgm_census", "sgm_path", "sgm_path_winner". */
+typedef struct pm_sgm_params {
+    int32_t min_disp, num_disp, p1, p2, paths, uniqueness, flags, reserved;
+} pm_sgm_params;
+int pm_stereo_sgm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int w, int h, int lstride, int rstride,
+                      const pm_sgm_params* p, int16_t* d_disp, int dstride, pm_stereo_info* d_info);
+int pm_stereo_sgm(pm_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int lstride, int rstride,
+                  const pm_sgm_params* p, int lr_max_diff16, int16_t* disp, int dstride, pm_stereo_info* info);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

@@ -82,6 +82,7 @@ EXPORTS = [
     "pm_undistort_points_dev", "pm_undistort_points", "pm_distort_points_dev", "pm_distort_points",
     "pm_undistort_dev", "pm_undistort", "pm_undistort_map_dev", "pm_remap_dev", "pm_remap",
     "pm_stereo_rectify", "pm_stereo_bm_dev", "pm_stereo_bm", "pm_stereo_lr_check_dev", "pm_stereo_points_dev", "pm_stereo_points",
+    "pm_stereo_sgm_dev", "pm_stereo_sgm",
     "pm_device_alloc", "pm_device_free", "pm_device_upload", "pm_device_download",
 ]
 
@@ -221,6 +222,18 @@ def stereo_params(num_disp=64, radius=4, min_disp=0, uniqueness=0, flags=0):
     """Disparities min_disp .. min_disp + num_disp - 1, window (2 radius + 1)^2, uniqueness in per cent (0 rejects nothing),
     flags: 0 or PM_STEREO_FROM_RIGHT."""
     return StereoParams(min_disp, num_disp, radius, uniqueness, flags, (C.c_int32 * 3)(0, 0, 0))
+
+
+class SgmParams(C.Structure):
+    """pm_sgm_params (include/pm.h, SPEC S89-S92); sgm_params() fills it."""
+    _fields_ = [("min_disp", C.c_int32), ("num_disp", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("paths", C.c_int32),
+                ("uniqueness", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+def sgm_params(num_disp=64, p1=4, p2=24, paths=8, min_disp=0, uniqueness=0, flags=0):
+    """Disparities min_disp .. min_disp + num_disp - 1, penalties 0 <= p1 <= p2 <= 1023 on the 0..62 census cost, paths 4 or 8,
+    uniqueness in per cent (0 rejects nothing), flags: 0 or PM_STEREO_FROM_RIGHT."""
+    return SgmParams(min_disp, num_disp, p1, p2, paths, uniqueness, flags, 0)
 
 
 def stereo_rectify(R, t):
@@ -998,6 +1011,29 @@ class Context:
         info = StereoInfo()
         _check(lib().pm_stereo_bm(self._h, _p(left), _p(right), w, h, left.shape[1], right.shape[1], C.byref(prm), lr_max_diff16, _p(disp),
                                   disp.shape[1], C.byref(info)))
+        return disp, info.n_valid
+
+    def stereo_sgm_dev(self, dleft_ptr, dright_ptr, w, h, lstride, rstride, prm, ddisp_ptr, dstride, dinfo_ptr=None):
+        """Semi-global matching (SPEC S89-S92) on device pointers; prm: SgmParams; the map and dinfo as for stereo_bm_dev."""
+        _check(lib().pm_stereo_sgm_dev(self._h, C.c_void_p(dleft_ptr), C.c_void_p(dright_ptr), w, h, lstride, rstride,
+                                       C.byref(prm) if prm is not None else None, C.c_void_p(ddisp_ptr), dstride, C.c_void_p(dinfo_ptr or 0)))
+
+    def stereo_sgm(self, left, right, prm=None, lr_max_diff16=-1, w=None, disp=None):
+        """Host form of stereo_sgm_dev: a rectified 8-bit pair (h, w) -> (disp (h, w) int16 in 1/16 pixel, n_valid)
+        (cv::StereoSGBM's place in the chain).  lr_max_diff16, w and disp as for stereo_bm."""
+        left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        if left.ndim != 2 or right.ndim != 2 or left.shape[0] != right.shape[0]:
+            raise ValueError("left and right must be 2-D arrays of one height")
+        h = left.shape[0]
+        w = left.shape[1] if w is None else w
+        prm = prm or sgm_params()
+        if disp is None:
+            disp = np.zeros((max(h, 1), max(w, 1)), np.int16)
+        if disp.dtype != np.int16 or disp.ndim != 2 or not disp.flags.c_contiguous or disp.shape[0] != max(h, 1):
+            raise ValueError("disp must be a contiguous (h, dstride) int16 array")
+        info = StereoInfo()
+        _check(lib().pm_stereo_sgm(self._h, _p(left), _p(right), w, h, left.shape[1], right.shape[1], C.byref(prm), lr_max_diff16, _p(disp),
+                                   disp.shape[1], C.byref(info)))
         return disp, info.n_valid
 
     def stereo_lr_check_dev(self, dleft_ptr, dright_ptr, w, h, lstride, rstride, max_diff16, dinfo_ptr=None):

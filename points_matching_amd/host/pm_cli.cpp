@@ -16,6 +16,7 @@
 //          [--align OUT.pgm [--align-model homography|affine|similarity]]
 //   pm_cli --undistort OUT.pgm --img1 IN.pgm --camera fx,fy,cx,cy --lens k1,k2,p1,p2,k3 [--new-camera fx,fy,cx,cy] [--json]
 //   pm_cli --stereo OUT.pgm --img1 L.pgm --img2 R.pgm --num-disp N [--min-disp M] [--radius R] [--uniqueness U] [--lr-check T16] [--json]
+//   pm_cli --stereo OUT.pgm --img1 L.pgm --img2 R.pgm --num-disp N --sgm P1,P2 [--paths 4|8] [--min-disp M] [--uniqueness U] [--lr-check T16] [--json]
 //          [--knn-hint auto|int|u8|unit]   what the caller knows about float descriptors (pm.h PM_KNN_HINT_*; default auto, and
 //                                     u8 for --img1/--img2, whose extractor writes u8-valued rows): route only, same output
 // --features device (with --img1/--img2): both images are uploaded and keypoints + descriptors are extracted on the GPU
@@ -45,6 +46,9 @@
 // and 0 where there is no disparity; one line
 //   stereo: valid=V
 // is printed (with --json the record {"stereo": {"width": W, "height": H, "n_valid": V}}) and the tool exits.
+// --sgm P1,P2 with it: the map by pm_stereo_sgm instead (semi-global matching, docs/SPEC.md S89-S92; --paths 4 or 8, default 8),
+// same file and same line.  --radius with --sgm, --paths without --sgm, --sgm without --stereo and a malformed P1,P2 are usage
+// errors.
 // Any switch of another mode with it (--undistort, --align, --guided, --epilines, --matcher, --features, --filter, ...) is a
 // usage error.
 // --undistort OUT.pgm (with --img1 alone, --camera and --lens; docs/SPEC.md S79-S83): the image as an ideal pinhole camera
@@ -353,7 +357,7 @@ int run_undistort(int device, const std::string& out_path, const std::string& in
 // --stereo: an already rectified pair through pm_stereo_bm (with --lr-check T16 >= 0 also the FROM_RIGHT pass and the left-right
 // check); a 16-bit PGM, most significant byte first: v - 16 * min_disp + 1, 0 where there is no disparity
 int run_stereo(int device, const std::string& out_path, const std::string& left_path, const std::string& right_path, const pm_stereo_params& prm,
-               int lr_check, bool json)
+               const pm_sgm_params* sgm, int lr_check, bool json)
 {
     pm_feat::Image im1, im2;
     std::string err;
@@ -366,7 +370,8 @@ int run_stereo(int device, const std::string& out_path, const std::string& left_
     const size_t px = static_cast<size_t>(w) * h;
     std::vector<int16_t> disp(px);
     pm_stereo_info info = {0, 0};
-    rc = pm_stereo_bm(ctx, im1.px.data(), im2.px.data(), w, h, w, w, &prm, lr_check, disp.data(), w, &info);
+    if (sgm) rc = pm_stereo_sgm(ctx, im1.px.data(), im2.px.data(), w, h, w, w, sgm, lr_check, disp.data(), w, &info);
+    else rc = pm_stereo_bm(ctx, im1.px.data(), im2.px.data(), w, h, w, w, &prm, lr_check, disp.data(), w, &info);
     if (rc != PM_OK) { fail("--stereo", rc); pm_ctx_destroy(ctx); return 1; }
     pm_ctx_destroy(ctx);
     std::vector<uint8_t> out(px * 2);
@@ -405,7 +410,8 @@ int main(int argc, char** argv)
     std::string stereo_pgm;
     pm_stereo_params stereo_prm = {0, 0, 4, 0, 0, {0, 0, 0}};
     int stereo_lr = -1;
-    bool stereo_opt_given = false;
+    bool stereo_opt_given = false, radius_given = false, paths_given = false, sgm_given = false;
+    pm_sgm_params sgm_prm = {0, 0, 0, 0, 8, 0, 0, 0};
     bool points_given = false, corner_opt_given = false;
     float corner_dist = 8.f, corner_quality = 0.01f, corner_min_eig = 1e-4f;
     int max_kp = 4000;
@@ -431,7 +437,17 @@ int main(int argc, char** argv)
         else if (a == "--stereo") stereo_pgm = val("--stereo");
         else if (a == "--num-disp") { stereo_prm.num_disp = atoi(val("--num-disp")); stereo_opt_given = true; }
         else if (a == "--min-disp") { stereo_prm.min_disp = atoi(val("--min-disp")); stereo_opt_given = true; }
-        else if (a == "--radius") { stereo_prm.radius = atoi(val("--radius")); stereo_opt_given = true; }
+        else if (a == "--radius") { stereo_prm.radius = atoi(val("--radius")); stereo_opt_given = radius_given = true; }
+        else if (a == "--sgm") {
+            int used = 0;
+            const char* v = val("--sgm");
+            if (sscanf(v, "%d,%d%n", &sgm_prm.p1, &sgm_prm.p2, &used) != 2 || v[used] != '\0') {
+                fprintf(stderr, "pm_cli: --sgm needs P1,P2 (two integers)\n");
+                return 2;
+            }
+            sgm_given = true;
+        }
+        else if (a == "--paths") { sgm_prm.paths = atoi(val("--paths")); paths_given = true; }
         else if (a == "--uniqueness") { stereo_prm.uniqueness = atoi(val("--uniqueness")); stereo_opt_given = true; }
         else if (a == "--lr-check") { stereo_lr = atoi(val("--lr-check")); stereo_opt_given = true; }
         else if (a == "--camera") camera_arg = val("--camera");
@@ -480,6 +496,10 @@ int main(int argc, char** argv)
         fprintf(stderr, "pm_cli: --num-disp, --min-disp, --radius, --uniqueness and --lr-check need --stereo OUT.pgm\n");
         return 2;
     }
+    if ((sgm_given && stereo_pgm.empty()) || (paths_given && !sgm_given) || (sgm_given && radius_given)) {
+        fprintf(stderr, "pm_cli: --sgm P1,P2 needs --stereo OUT.pgm and takes no --radius; --paths needs --sgm\n");
+        return 2;
+    }
     if (!stereo_pgm.empty()) {
         // ---- a rectified pair through pm_stereo_bm, then exit (no features, no matcher)
         if (img1_path.empty() || img2_path.empty() || stereo_prm.num_disp < 1 || !undistort_pgm.empty()) {
@@ -494,7 +514,8 @@ int main(int argc, char** argv)
             fprintf(stderr, "pm_cli: --stereo takes --img1, --img2, its own options, --device and --json only\n");
             return 2;
         }
-        return run_stereo(device, stereo_pgm, img1_path, img2_path, stereo_prm, stereo_lr, json);
+        sgm_prm.min_disp = stereo_prm.min_disp; sgm_prm.num_disp = stereo_prm.num_disp; sgm_prm.uniqueness = stereo_prm.uniqueness;
+        return run_stereo(device, stereo_pgm, img1_path, img2_path, stereo_prm, sgm_given ? &sgm_prm : nullptr, stereo_lr, json);
     }
     if (!undistort_pgm.empty()) {
         // ---- one image through pm_undistort_dev, then exit (no features, no matcher)
