@@ -82,12 +82,6 @@ struct DescArgs {
     uint8_t* bin;
 };
 
-__device__ __forceinline__ int clamped_count(const int32_t* d_n, int cap)
-{
-    const int n = d_n ? *d_n : cap;            // (the -1 that the corner and feature front ends write on overflow counts as 0)
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
 // The lanes of ONE wave exchange data through their slice of LDS (as in track_lk.hip): LDS operations of a wave complete in
 // issue order, so all that is needed is that the compiler keeps the order too.
 __device__ __forceinline__ void wave_lds_sync()
@@ -111,7 +105,7 @@ __global__ __launch_bounds__(64 * WPB) void desc_points(const DescArgs a)
     __shared__ __attribute__((aligned(16))) unsigned char s_mem[WPB][WAVE_BYTES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pt = blockIdx.x * WPB + wave;
-    if (pt >= clamped_count(a.d_n, a.cap)) return;
+    if (pt >= pm::clamped_count(a.d_n, a.cap)) return;
     unsigned char* s_px = s_mem[wave];
     unsigned short* s_row = reinterpret_cast<unsigned short*>(s_px + PX_BYTES);
     unsigned short* s_box = s_row + ROW_SHORTS;
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(1024) void desc_compact(const float* pts, const int
     __shared__ int s_wave[16];
     __shared__ int s_dst[1024];
     __shared__ int s_base;
-    const int n = clamped_count(d_n, cap);
+    const int n = pm::clamped_count(d_n, cap);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) s_base = 0;
     __syncthreads();

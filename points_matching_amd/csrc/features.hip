@@ -822,7 +822,7 @@ int check_args(pm_ctx* ctx, const void* img, int w, int h, int stride, int max_k
     PM_REQUIRE(w >= 1 && h >= 1 && stride >= w && max_kp >= 1, PM_E_INVALID, "need w, h >= 1, stride >= w, max_kp >= 1");
     PM_REQUIRE(img != nullptr && kp != nullptr, PM_E_INVALID, "null image or keypoint pointer");
     PM_REQUIRE(contrast == contrast && edge_r == edge_r, PM_E_INVALID, "contrast / edge_r is NaN");
-    PM_REQUIRE(static_cast<long long>(w) * h <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(w, h));
     return PM_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "image_args.hpp"
 #include "pm.h"
 #include "stage_layout.hpp"
 
@@ -34,6 +35,13 @@ void set_error(const char* fmt, ...);
             ::pm::set_error("%s: %s", __func__, msg);                                   \
             return (status);                                                            \
         }                                                                               \
+    } while (0)
+
+// a pm_image::Check (image_args.hpp) that did not pass: its status and its message under the caller's name
+#define PM_REQUIRE_PASS(check)                                                          \
+    do {                                                                                \
+        const ::pm_image::Check c_ = (check);                                           \
+        PM_REQUIRE(c_.status == PM_OK, c_.status, c_.why);                              \
     } while (0)
 
 // The matcher and the compaction kernels tag their side-band words with a per-call epoch that the HOST increments (it
@@ -143,6 +151,52 @@ struct __attribute__((visibility("hidden"))) StagedBlock : StageLayout {
         bo.download(out, o_out, ob);
         return bo.sync();
     }
+    // An image -> image call's whole sequence around dev(d_extra, d_src, d_dst, d_valid, d_info).  extra is the call's own input
+    // (a model, a map; 0 bytes: none).  dst is uploaded, so that the bytes between its rows come back as they were; valid and
+    // info are staged, and handed to dev, only when the caller asked for them.
+    template <class Dev> static int image(pm_ctx* ctx, const char* who, const void* extra, size_t extra_b, const uint8_t* src, int sw, int sh,
+                                          int sstride, uint8_t* dst, int dw, int dh, int dstride, uint8_t* valid, pm_warp_info* info, Dev dev)
+    {
+        const size_t src_b = pm_image::span(sw, sh, sstride, 1), dst_b = pm_image::span(dw, dh, dstride, 1), val_b = static_cast<size_t>(dw) * dh;
+        StagedBlock b(ctx, who);
+        const size_t o_extra = b.add(extra_b), o_info = b.add(sizeof(pm_warp_info)), o_src = b.add(src_b), o_dst = b.add(dst_b);
+        const size_t o_val = b.add(valid ? val_b : 0);
+        b.alloc();
+        b.upload(o_extra, extra, extra_b);
+        b.upload(o_src, src, src_b);
+        b.upload(o_dst, dst, dst_b);
+        if (b.rc == PM_OK)
+            b.rc = dev(b.at<const char>(o_extra), b.at<const uint8_t>(o_src), b.at<uint8_t>(o_dst), valid ? b.at<uint8_t>(o_val) : nullptr,
+                       info ? b.at<pm_warp_info>(o_info) : nullptr);
+        b.download(dst, o_dst, dst_b);
+        if (valid) b.download(valid, o_val, val_b);
+        if (info) b.download(info, o_info, sizeof(pm_warp_info));
+        return b.sync();
+    }
+    // A stereo matcher's whole sequence: the left map by base(d_left, d_right, d_disp, d_info) and, with lr_max_diff16 >= 0, the
+    // right map (w elements per row) by from_right(d_left, d_right, d_rmap) and S86 on the two.  disp is uploaded, so that the
+    // elements between its rows come back as they were.  n_valid is always counted on the device: the count is of the last pass.
+    template <class Base, class FromRight>
+    static int stereo(pm_ctx* ctx, const char* who, const uint8_t* left, const uint8_t* right, int w, int h, int lstride, int rstride,
+                      int lr_max_diff16, int16_t* disp, int dstride, pm_stereo_info* info, Base base, FromRight from_right)
+    {
+        const bool lr = lr_max_diff16 >= 0;
+        const size_t l_b = pm_image::span(w, h, lstride, 1), r_b = pm_image::span(w, h, rstride, 1), d_b = pm_image::span(w, h, dstride, 2);
+        const size_t rmap_b = lr ? static_cast<size_t>(w) * h * 2 : 0;
+        StagedBlock b(ctx, who);
+        const size_t o_info = b.add(sizeof(pm_stereo_info)), o_l = b.add(l_b), o_r = b.add(r_b), o_d = b.add(d_b), o_rmap = b.add(rmap_b);
+        b.alloc();
+        b.upload(o_l, left, l_b);
+        b.upload(o_r, right, r_b);
+        b.upload(o_d, disp, d_b);
+        pm_stereo_info* d_info = b.at<pm_stereo_info>(o_info);
+        if (b.rc == PM_OK) b.rc = base(b.at<const uint8_t>(o_l), b.at<const uint8_t>(o_r), b.at<int16_t>(o_d), d_info);
+        if (lr && b.rc == PM_OK) b.rc = from_right(b.at<const uint8_t>(o_l), b.at<const uint8_t>(o_r), b.at<int16_t>(o_rmap));
+        if (lr && b.rc == PM_OK) b.rc = pm_stereo_lr_check_dev(ctx, b.at<int16_t>(o_d), b.at<int16_t>(o_rmap), w, h, dstride, w, lr_max_diff16, d_info);
+        b.download(disp, o_d, d_b);
+        if (info) b.download(info, o_info, sizeof(pm_stereo_info));
+        return b.sync();
+    }
 };
 
 // RAII event bracket: records start/stop on ctx->stream when timing is on.
@@ -157,6 +211,13 @@ struct ScopedKernelTime {
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 #if defined(__HIPCC__)
+// n = *d_n clamped to [0, cap]; NULL = cap (the -1 that the point sources write on overflow counts as 0)
+__device__ __forceinline__ int clamped_count(const int32_t* d_n, int cap)
+{
+    const int n = d_n ? *d_n : cap;
+    return n < 0 ? 0 : (n > cap ? cap : n);
+}
+
 // Wave-wide reductions on the DPP path (all 64 lanes must be active): four v_min/v_max with a
 // row_ror operand reduce each row of 16 lanes, four v_readlane + scalar ops combine the rows; the
 // result is wave-uniform.  A __shfl_xor butterfly costs six ds_bpermute round trips (two each for

@@ -9,22 +9,26 @@
 // consecutive bytes (16 banks, four lanes per dword, no conflict), and v_sad_u8 adds |a - b| to the running sum in one
 // instruction.  The window slides: C(x) = C(x - 1) + V(x + r) - V(x - r - 1), with the last 2r + 1 column sums in a
 // per-lane ring in LDS (u16: V <= 21 * 255).  D > 64 gives a lane up to four disparities (template NC), so the cost curve of
-// a pixel lies across the lanes: the winner is one DPP wave minimum of the key (cost << 9) | (d - dmin), which is the
-// lowest-d tie rule; c2 a second minimum; p and n two lane reads.  A lane keeps the result of "its" column and the segment
-// goes out as one 128-byte store.  One integer atomic per workgroup for n_valid.
+// a pixel lies across the lanes: the winner is stereo_core::winner (stereo_core.hpp, shared with stereo_sgm.hip): one DPP wave
+// minimum of the key (cost << 9) | (d - dmin), which is the lowest-d tie rule; c2 a second minimum; p and n two lane reads.  A
+// lane keeps the result of "its" column and the segment goes out as one 128-byte store.  One integer atomic per workgroup for
+// n_valid.  The range and size rules of the arguments are image_args.hpp's, the host form is StagedBlock::stereo (pm_common.hpp).
 //
 // stereo_lr_check (S86): a 64 x 32 tile per workgroup, eight rows per thread.  stereo_points (S87): one thread per point.
 #include <cmath>
 #include <cstdint>
 
 #include "pm_common.hpp"
+#include "stereo_core.hpp"
 #include "stereo_rectify_core.hpp"
 
 namespace {
 
+using pm_image::overlap;
+using pm_image::span;
+using stereo_core::INVALID;
+
 constexpr int TILE_W = 64, TILE_H = 4;                    // output tile of a workgroup: one 64-pixel row segment per wave
-constexpr int INVALID = PM_STEREO_INVALID;
-constexpr unsigned NO_KEY = 0xFFFFFFFFu;
 
 struct BmArgs {
     const uint8_t* base;                                  // the image whose pixels get a disparity (right with FROM_RIGHT)
@@ -58,18 +62,6 @@ __device__ __forceinline__ void stage(uint8_t* dst, const uint8_t* img, int w, i
         }
         *reinterpret_cast<unsigned*>(dst + ry * pitch + rx) = word;
     }
-}
-
-template <int NC>
-__device__ __forceinline__ unsigned cost_at(const unsigned (&C)[NC], int k)          // k is wave-uniform
-{
-    unsigned v = __builtin_amdgcn_readlane(C[0], k & 63);          // a lane read per group and scalar selects: no indexed array
-#pragma unroll
-    for (int c = 1; c < NC; ++c) {
-        const unsigned t = __builtin_amdgcn_readlane(C[c], k & 63);
-        v = (k >> 6) == c ? t : v;
-    }
-    return v;
 }
 
 template <int NC>
@@ -133,32 +125,8 @@ __global__ __launch_bounds__(256) void stereo_bm(BmArgs a)
             const int x = col - r;
             if (x < xs) continue;                                                    // the window is not whole yet
 
-            unsigned key = NO_KEY;
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (live[c]) key = min(key, (C[c] << 9) | static_cast<unsigned>(lane + 64 * c));
-            key = pm::wave_min_u32(key);
-            const int c1 = static_cast<int>(key >> 9), k1 = static_cast<int>(key & 511u);
-            bool keep = true;
-            if (a.uniq > 0) {
-                unsigned second = NO_KEY;
-#pragma unroll
-                for (int c = 0; c < NC; ++c)
-                    if (live[c] && abs(lane + 64 * c - k1) > 1) second = min(second, C[c]);
-                second = pm::wave_min_u32(second);
-                if (second != NO_KEY && static_cast<int>(second) * (100 - a.uniq) < c1 * 100) keep = false;
-            }
-            int sub = 0;
-            if (k1 > 0 && k1 < D - 1) {
-                const int p = static_cast<int>(cost_at<NC>(C, k1 - 1)), n = static_cast<int>(cost_at<NC>(C, k1 + 1));
-                const int den = p + n - 2 * c1;
-                if (den != 0) {
-                    const int num = 16 * (p - n) + den, d2 = 2 * den;                // den > 0: c1 is the minimum
-                    sub = num / d2;
-                    if (num < 0 && sub * d2 != num) --sub;                           // floor
-                }
-            }
-            if (lane == x - x0) mine = keep ? 16 * (a.dmin + k1) + sub : INVALID;
+            const int won = stereo_core::winner<pm::wave_min_u32>(C, live, lane, D, a.dmin, a.uniq).value;          // wave-uniform
+            if (lane == x - x0) mine = won;
         }
     }
     const int x = x0 + lane;
@@ -226,8 +194,7 @@ __global__ __launch_bounds__(256) void stereo_points(PointArgs a, const int16_t*
                                                      const int32_t* d_n, int cap, float* xyz)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = d_n ? *d_n : cap;
-    if (i >= (n < 0 ? 0 : (n > cap ? cap : n))) return;
+    if (i >= pm::clamped_count(d_n, cap)) return;
     const double x = static_cast<double>(pts[2 * static_cast<size_t>(i)]), y = static_cast<double>(pts[2 * static_cast<size_t>(i) + 1]);
     const float nan = __uint_as_float(0x7FC00000u);
     float o0 = nan, o1 = nan, o2 = nan;
@@ -256,14 +223,6 @@ __global__ __launch_bounds__(256) void stereo_points(PointArgs a, const int16_t*
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-size_t span(int w, int h, int stride, size_t elem) { return (static_cast<size_t>(h - 1) * stride + w) * elem; }
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return !(a0 + a_bytes <= b0 || b0 + b_bytes <= a0);
-}
-
 int check_bm(const void* left, const void* right, int w, int h, int lstride, int rstride, const pm_stereo_params* p, const void* disp, int dstride)
 {
     PM_REQUIRE(left != nullptr && right != nullptr && p != nullptr && disp != nullptr, PM_E_INVALID, "null pointer");
@@ -275,18 +234,7 @@ int check_bm(const void* left, const void* right, int w, int h, int lstride, int
     PM_REQUIRE(p->uniqueness >= 0 && p->uniqueness <= 99, PM_E_INVALID, "uniqueness outside [0, 99]");
     PM_REQUIRE(w >= 1 && h >= 1, PM_E_INVALID, "need sizes >= 1");
     PM_REQUIRE(lstride >= w && rstride >= w && dstride >= w, PM_E_INVALID, "a stride below the width");
-    PM_REQUIRE(static_cast<long long>(w) * h <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
-    return PM_OK;
-}
-
-// S85's buffer rule: the map overlaps neither image, the info record none of the three
-int check_bm_ranges(const void* left, const void* right, int w, int h, int lstride, int rstride, const void* disp, int dstride, const void* info)
-{
-    const size_t l_b = span(w, h, lstride, 1), r_b = span(w, h, rstride, 1), d_b = span(w, h, dstride, 2);
-    PM_REQUIRE(!overlap(left, l_b, disp, d_b) && !overlap(right, r_b, disp, d_b), PM_E_INVALID, "an input image and the disparity map overlap");
-    PM_REQUIRE(!info || (!overlap(info, sizeof(pm_stereo_info), left, l_b) && !overlap(info, sizeof(pm_stereo_info), right, r_b) &&
-                         !overlap(info, sizeof(pm_stereo_info), disp, d_b)),
-               PM_E_INVALID, "the info record overlaps an image or the map");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(w, h));
     return PM_OK;
 }
 
@@ -296,7 +244,7 @@ int check_lr(const void* left, const void* right, int w, int h, int lstride, int
     PM_REQUIRE(max_diff16 >= 0, PM_E_INVALID, "max_diff16 < 0");
     PM_REQUIRE(w >= 1 && h >= 1, PM_E_INVALID, "need sizes >= 1");
     PM_REQUIRE(lstride >= w && rstride >= w, PM_E_INVALID, "a stride below the width");
-    PM_REQUIRE(static_cast<long long>(w) * h <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(w, h));
     return PM_OK;
 }
 
@@ -317,7 +265,7 @@ int make_points(const void* disp, int w, int h, int dstride, const pm_camera* K,
         PM_REQUIRE(!R || std::isfinite(R[i]), PM_E_INVALID, "an entry of R is not finite");
         a->R[i] = R ? R[i] : (i % 4 == 0 ? 1.0 : 0.0);
     }
-    PM_REQUIRE(static_cast<long long>(w) * h <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(w, h));
     PM_REQUIRE(n >= 1, PM_E_UNSUPPORTED, "cap == 0 or n == 0: no points");
     const size_t x_b = static_cast<size_t>(n) * 12;
     PM_REQUIRE(!overlap(xyz, x_b, disp, span(w, h, dstride, 2)) && !overlap(xyz, x_b, pts, static_cast<size_t>(n) * 8), PM_E_INVALID,
@@ -347,12 +295,12 @@ extern "C" int pm_stereo_bm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_
     PM_REFUSE_CAPTURE(ctx);
     const int rc = check_bm(d_left, d_right, w, h, lstride, rstride, p, d_disp, dstride);
     if (rc != PM_OK) return rc;
-    int rc2 = check_bm_ranges(d_left, d_right, w, h, lstride, rstride, d_disp, dstride, d_info);
-    if (rc2 != PM_OK) return rc2;
+    PM_REQUIRE_PASS(pm_image::disparity_map_ranges(d_left, d_right, w, h, lstride, rstride, d_disp, dstride, d_info));
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     if (d_info) PM_HIP_CHECK(hipMemsetAsync(d_info, 0, sizeof(pm_stereo_info), ctx->stream));
     const bool from_right = (p->flags & PM_STEREO_FROM_RIGHT) != 0;
-    const int r = p->radius, D = p->num_disp, dmin = p->min_disp, dmax = dmin + D - 1;
+    const int r = p->radius, D = p->num_disp, dmin = p->min_disp;
+    const pm_image::Columns cols = pm_image::computed_columns(from_right, r, dmin, dmin + D - 1, w);
     BmArgs a;
     a.base = from_right ? d_right : d_left;
     a.other = from_right ? d_left : d_right;
@@ -361,8 +309,7 @@ extern "C" int pm_stereo_bm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_
     a.w = w; a.h = h;
     a.dmin = dmin; a.D = D; a.r = r; a.uniq = p->uniqueness;
     a.sgn = from_right ? 1 : -1;
-    a.cx0 = from_right ? r - (dmin < 0 ? dmin : 0) : r + (dmax > 0 ? dmax : 0);
-    a.cx1 = from_right ? w - 1 - r - (dmax > 0 ? dmax : 0) : w - 1 - r + (dmin < 0 ? dmin : 0);
+    a.cx0 = cols.x0; a.cx1 = cols.x1;
     a.nbx = (w + TILE_W - 1) / TILE_W;
     a.bw = (TILE_W + 2 * r + 3) & ~3;
     a.ow = (TILE_W + 2 * r + D - 1 + 3) & ~3;
@@ -415,28 +362,13 @@ extern "C" int pm_stereo_bm(pm_ctx* ctx, const uint8_t* left, const uint8_t* rig
     if (rc != PM_OK) return rc;
     const bool lr = lr_max_diff16 >= 0;
     PM_REQUIRE(!lr || (p->flags & PM_STEREO_FROM_RIGHT) == 0, PM_E_INVALID, "the left-right check needs the left map: no PM_STEREO_FROM_RIGHT");
-    const int rc2 = check_bm_ranges(left, right, w, h, lstride, rstride, disp, dstride, info);
-    if (rc2 != PM_OK) return rc2;
-    const size_t l_b = span(w, h, lstride, 1), r_b = span(w, h, rstride, 1), d_b = span(w, h, dstride, 2);
-    const size_t rmap_b = lr ? static_cast<size_t>(w) * h * 2 : 0;
-    pm::StagedBlock b(ctx, __func__);
-    const size_t o_info = b.add(sizeof(pm_stereo_info)), o_l = b.add(l_b), o_r = b.add(r_b), o_d = b.add(d_b), o_rmap = b.add(rmap_b);
-    b.alloc();
-    b.upload(o_l, left, l_b);
-    b.upload(o_r, right, r_b);
-    b.upload(o_d, disp, d_b);                                     // the elements between the rows of disp come back as they were
-    pm_stereo_info* d_info = b.at<pm_stereo_info>(o_info);          // always counted on the device: the count is of the last pass
-    if (b.rc == PM_OK) b.rc = pm_stereo_bm_dev(ctx, b.at<uint8_t>(o_l), b.at<uint8_t>(o_r), w, h, lstride, rstride, p, b.at<int16_t>(o_d), dstride, d_info);
-    if (lr) {
-        pm_stereo_params q = *p;
-        q.flags |= PM_STEREO_FROM_RIGHT;
-        if (b.rc == PM_OK)
-            b.rc = pm_stereo_bm_dev(ctx, b.at<uint8_t>(o_l), b.at<uint8_t>(o_r), w, h, lstride, rstride, &q, b.at<int16_t>(o_rmap), w, nullptr);
-        if (b.rc == PM_OK) b.rc = pm_stereo_lr_check_dev(ctx, b.at<int16_t>(o_d), b.at<int16_t>(o_rmap), w, h, dstride, w, lr_max_diff16, d_info);
-    }
-    b.download(disp, o_d, d_b);
-    if (info) b.download(info, o_info, sizeof(pm_stereo_info));
-    return b.sync();
+    PM_REQUIRE_PASS(pm_image::disparity_map_ranges(left, right, w, h, lstride, rstride, disp, dstride, info));
+    pm_stereo_params q = *p;
+    q.flags |= PM_STEREO_FROM_RIGHT;
+    return pm::StagedBlock::stereo(
+        ctx, __func__, left, right, w, h, lstride, rstride, lr_max_diff16, disp, dstride, info,
+        [&](const uint8_t* l, const uint8_t* r, int16_t* d, pm_stereo_info* i) { return pm_stereo_bm_dev(ctx, l, r, w, h, lstride, rstride, p, d, dstride, i); },
+        [&](const uint8_t* l, const uint8_t* r, int16_t* d) { return pm_stereo_bm_dev(ctx, l, r, w, h, lstride, rstride, &q, d, w, nullptr); });
 }
 
 extern "C" int pm_stereo_points_dev(pm_ctx* ctx, const int16_t* d_disp, int w, int h, int dstride, const pm_camera* K_rect, double baseline,

@@ -15,16 +15,18 @@
 // A horizontal pass has a wave per row.  A vertical or diagonal pass has a wave per start column that steps one row at a time
 // and moves its column by dx; when it leaves the rectangle's side it enters at the other side and restarts with L = C, so wc
 // waves cover every diagonal path.  The first pass writes S, the others add, the last one does not store: it picks the winner
-// of S85 with the sums still in registers (one wave minimum of (S << 9) | k, as stereo_bm) and writes the map.
+// of S85 with the sums still in registers (stereo_core::winner, the one stereo_bm calls) and writes the map.  The range and size
+// rules of the arguments are image_args.hpp's, the host form is StagedBlock::stereo (pm_common.hpp).
 #include <cstdint>
 
 #include "pm_common.hpp"
+#include "stereo_core.hpp"
 #include "stereo_sgm_plan.hpp"
 
 namespace {
 
-constexpr int INVALID = PM_STEREO_INVALID;
-constexpr unsigned NO_KEY = 0xFFFFFFFFu;
+using stereo_core::INVALID;
+
 constexpr unsigned BIG = 1u << 16;                        // above every L_r + p2 (<= 2108): a lane that holds no disparity
 constexpr int TW = pm_sgm::CENSUS_TILE_W, TH = pm_sgm::CENSUS_TILE_H, MX = pm_sgm::MARGIN_X, MY = pm_sgm::MARGIN_Y;
 constexpr int LW = TW + 2 * MX, LH = TH + 2 * MY;         // the staged tile: 72 x 10 bytes
@@ -81,18 +83,6 @@ struct PathArgs {
     int dstride;
     pm_stereo_info* info;
 };
-
-template <int NC>
-__device__ __forceinline__ unsigned sum_at(const unsigned (&S)[NC], int k)           // k is wave-uniform
-{
-    unsigned v = __builtin_amdgcn_readlane(S[0], k & 63);
-#pragma unroll
-    for (int c = 1; c < NC; ++c) {
-        const unsigned t = __builtin_amdgcn_readlane(S[c], k & 63);
-        v = (k >> 6) == c ? t : v;
-    }
-    return v;
-}
 
 // pm::wave_min_u32 with the value that no lane reads (every row_ror lane has a source) set to the minimum's identity, so that
 // the compiler folds each move into its v_min_u32: one instruction per stage instead of three.  All 64 lanes active.
@@ -231,33 +221,9 @@ __global__ __launch_bounds__(64) void sgm_path(PathArgs a)
             for (int c = 0; c < NC; ++c)
                 if (live[c]) cs[lane + 64 * c] = static_cast<uint16_t>(Sv[c]);
         } else {
-            unsigned key = NO_KEY;
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-                if (live[c]) key = min(key, (Sv[c] << 9) | static_cast<unsigned>(lane + 64 * c));
-            key = wave_min(key);
-            const int c1 = static_cast<int>(key >> 9), k1 = static_cast<int>(key & 511u);
-            bool keep = true;
-            if (a.uniq > 0) {
-                unsigned second = NO_KEY;
-#pragma unroll
-                for (int c = 0; c < NC; ++c)
-                    if (live[c] && abs(lane + 64 * c - k1) > 1) second = min(second, Sv[c]);
-                second = wave_min(second);
-                if (second != NO_KEY && static_cast<int>(second) * (100 - a.uniq) < c1 * 100) keep = false;
-            }
-            int sub = 0;
-            if (k1 > 0 && k1 < D - 1) {
-                const int p = static_cast<int>(sum_at<NC>(Sv, k1 - 1)), n = static_cast<int>(sum_at<NC>(Sv, k1 + 1));
-                const int den = p + n - 2 * c1;
-                if (den != 0) {
-                    const int num = 16 * (p - n) + den, d2 = 2 * den;                    // den > 0: c1 is the minimum
-                    sub = num / d2;
-                    if (num < 0 && sub * d2 != num) --sub;                               // floor
-                }
-            }
-            if (keep) ++n_valid;
-            if (lane == 0) *cd = static_cast<int16_t>(keep ? 16 * (a.dmin + k1) + sub : INVALID);
+            const stereo_core::Won won = stereo_core::winner<wave_min>(Sv, live, lane, D, a.dmin, a.uniq);
+            if (won.kept) ++n_valid;
+            if (lane == 0) *cd = static_cast<int16_t>(won.value);
         }
         col = ncol;
         cs += ds;
@@ -299,18 +265,6 @@ int check_sgm(const void* left, const void* right, int w, int h, int lstride, in
     return PM_OK;
 }
 
-int check_sgm_ranges(const void* left, const void* right, int w, int h, int lstride, int rstride, const void* disp, int dstride, const void* info)
-{
-    using pm_sgm::overlap;
-    using pm_sgm::span;
-    const size_t l_b = span(w, h, lstride, 1), r_b = span(w, h, rstride, 1), d_b = span(w, h, dstride, 2);
-    PM_REQUIRE(!overlap(left, l_b, disp, d_b) && !overlap(right, r_b, disp, d_b), PM_E_INVALID, "an input image and the disparity map overlap");
-    PM_REQUIRE(!info || (!overlap(info, sizeof(pm_stereo_info), left, l_b) && !overlap(info, sizeof(pm_stereo_info), right, r_b) &&
-                         !overlap(info, sizeof(pm_stereo_info), disp, d_b)),
-               PM_E_INVALID, "the info record overlaps an image or the map");
-    return PM_OK;
-}
-
 }  // namespace
 
 extern "C" int pm_stereo_sgm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int w, int h, int lstride, int rstride,
@@ -321,8 +275,7 @@ extern "C" int pm_stereo_sgm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8
     pm_sgm::Plan q;
     const int rc = check_sgm(d_left, d_right, w, h, lstride, rstride, p, d_disp, dstride, &q);
     if (rc != PM_OK) return rc;
-    const int rc2 = check_sgm_ranges(d_left, d_right, w, h, lstride, rstride, d_disp, dstride, d_info);
-    if (rc2 != PM_OK) return rc2;
+    PM_REQUIRE_PASS(pm_image::disparity_map_ranges(d_left, d_right, w, h, lstride, rstride, d_disp, dstride, d_info));
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     pm::arena_reset(ctx);
     const int rc3 = pm::arena_reserve(ctx, q.need);
@@ -375,26 +328,11 @@ extern "C" int pm_stereo_sgm(pm_ctx* ctx, const uint8_t* left, const uint8_t* ri
     if (rc != PM_OK) return rc;
     const bool lr = lr_max_diff16 >= 0;
     PM_REQUIRE(!lr || (p->flags & PM_STEREO_FROM_RIGHT) == 0, PM_E_INVALID, "the left-right check needs the left map: no PM_STEREO_FROM_RIGHT");
-    const int rc2 = check_sgm_ranges(left, right, w, h, lstride, rstride, disp, dstride, info);
-    if (rc2 != PM_OK) return rc2;
-    const size_t l_b = pm_sgm::span(w, h, lstride, 1), r_b = pm_sgm::span(w, h, rstride, 1), d_b = pm_sgm::span(w, h, dstride, 2);
-    const size_t rmap_b = lr ? static_cast<size_t>(w) * h * 2 : 0;
-    pm::StagedBlock b(ctx, __func__);
-    const size_t o_info = b.add(sizeof(pm_stereo_info)), o_l = b.add(l_b), o_r = b.add(r_b), o_d = b.add(d_b), o_rmap = b.add(rmap_b);
-    b.alloc();
-    b.upload(o_l, left, l_b);
-    b.upload(o_r, right, r_b);
-    b.upload(o_d, disp, d_b);                                     // the elements between the rows of disp come back as they were
-    pm_stereo_info* d_info = b.at<pm_stereo_info>(o_info);
-    if (b.rc == PM_OK) b.rc = pm_stereo_sgm_dev(ctx, b.at<uint8_t>(o_l), b.at<uint8_t>(o_r), w, h, lstride, rstride, p, b.at<int16_t>(o_d), dstride, d_info);
-    if (lr) {
-        pm_sgm_params r = *p;
-        r.flags |= PM_STEREO_FROM_RIGHT;
-        if (b.rc == PM_OK)
-            b.rc = pm_stereo_sgm_dev(ctx, b.at<uint8_t>(o_l), b.at<uint8_t>(o_r), w, h, lstride, rstride, &r, b.at<int16_t>(o_rmap), w, nullptr);
-        if (b.rc == PM_OK) b.rc = pm_stereo_lr_check_dev(ctx, b.at<int16_t>(o_d), b.at<int16_t>(o_rmap), w, h, dstride, w, lr_max_diff16, d_info);
-    }
-    b.download(disp, o_d, d_b);
-    if (info) b.download(info, o_info, sizeof(pm_stereo_info));
-    return b.sync();
+    PM_REQUIRE_PASS(pm_image::disparity_map_ranges(left, right, w, h, lstride, rstride, disp, dstride, info));
+    pm_sgm_params pr = *p;
+    pr.flags |= PM_STEREO_FROM_RIGHT;
+    return pm::StagedBlock::stereo(
+        ctx, __func__, left, right, w, h, lstride, rstride, lr_max_diff16, disp, dstride, info,
+        [&](const uint8_t* l, const uint8_t* r, int16_t* d, pm_stereo_info* i) { return pm_stereo_sgm_dev(ctx, l, r, w, h, lstride, rstride, p, d, dstride, i); },
+        [&](const uint8_t* l, const uint8_t* r, int16_t* d) { return pm_stereo_sgm_dev(ctx, l, r, w, h, lstride, rstride, &pr, d, w, nullptr); });
 }

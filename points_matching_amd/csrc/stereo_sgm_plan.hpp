@@ -5,13 +5,13 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "image_args.hpp"
 #include "pm.h"
 
 namespace pm_sgm {
 
 constexpr int CENSUS_TILE_W = 64, CENSUS_TILE_H = 4;      // output tile of a sgm_census workgroup (256 threads)
 constexpr int MARGIN_X = 4, MARGIN_Y = 3;                 // the 9 x 7 census window
-constexpr long long MAX_PIXELS = 100000000LL;
 constexpr long long MAX_VOLUME = 1LL << 30;               // computed pixels x D: the u16 volume S stays within 2 GiB
 
 struct Pass {
@@ -38,14 +38,6 @@ struct Plan {
 
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
-inline size_t span(int w, int h, int stride, size_t elem) { return (static_cast<size_t>(h - 1) * stride + w) * elem; }
-
-inline bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return !(a0 + a_bytes <= b0 || b0 + b_bytes <= a0);
-}
-
 inline Plan refuse(int status, const char* why)
 {
     Plan q;
@@ -66,14 +58,16 @@ inline Plan plan(int w, int h, int lstride, int rstride, int dstride, const pm_s
     if (p->uniqueness < 0 || p->uniqueness > 99) return refuse(PM_E_INVALID, "uniqueness outside [0, 99]");
     if (w < 1 || h < 1) return refuse(PM_E_INVALID, "need sizes >= 1");
     if (lstride < w || rstride < w || dstride < w) return refuse(PM_E_INVALID, "a stride below the width");
-    if (static_cast<long long>(w) * h > MAX_PIXELS) return refuse(PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    const pm_image::Check cap = pm_image::pixel_cap(w, h);
+    if (cap.status != PM_OK) return refuse(cap.status, cap.why);
 
     Plan q;
-    const int D = p->num_disp, dmin = p->min_disp, dmax = dmin + D - 1;
+    const int D = p->num_disp;
     q.from_right = (p->flags & PM_STEREO_FROM_RIGHT) != 0;
     q.sgn = q.from_right ? 1 : -1;
-    q.cx0 = q.from_right ? MARGIN_X - (dmin < 0 ? dmin : 0) : MARGIN_X + (dmax > 0 ? dmax : 0);
-    q.cx1 = q.from_right ? w - 1 - MARGIN_X - (dmax > 0 ? dmax : 0) : w - 1 - MARGIN_X + (dmin < 0 ? dmin : 0);
+    const pm_image::Columns cols = pm_image::computed_columns(q.from_right != 0, MARGIN_X, p->min_disp, p->min_disp + D - 1, w);
+    q.cx0 = cols.x0;
+    q.cx1 = cols.x1;
     q.cy0 = MARGIN_Y;
     q.cy1 = h - 1 - MARGIN_Y;
     q.rows = q.cy1 >= q.cy0 ? q.cy1 - q.cy0 + 1 : 0;

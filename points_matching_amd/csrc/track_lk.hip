@@ -214,18 +214,12 @@ __device__ __forceinline__ int track_point(const LkArgs& a, int dir, float ptx, 
     return status;
 }
 
-__device__ __forceinline__ int clamped_count(const int32_t* d_n, int cap)
-{
-    const int n = d_n ? *d_n : cap;            // (the -1 that the feature front end writes on overflow counts as 0)
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
 __global__ __launch_bounds__(64 * WPB) void lk_track(const LkArgs a)
 {
     __shared__ __attribute__((aligned(16))) short s_mem[WPB][WAVE_SHORTS];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pt = blockIdx.x * WPB + wave;
-    if (pt >= clamped_count(a.d_n, a.cap)) return;                // (no workgroup barrier anywhere below)
+    if (pt >= pm::clamped_count(a.d_n, a.cap)) return;                // (no workgroup barrier anywhere below)
     short* sT = s_mem[wave];
     short* sgx = sT + T_MAX;
     short* sgy = sgx + G_MAX;
@@ -259,7 +253,7 @@ __global__ __launch_bounds__(1024) void lk_compact(const float* pts, const int32
 {
     __shared__ int s_wave[16];
     __shared__ int s_base;
-    const int n = clamped_count(d_n, cap);
+    const int n = pm::clamped_count(d_n, cap);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid == 0) s_base = 0;
     __syncthreads();
@@ -396,7 +390,7 @@ extern "C" int pm_pyramid_create(pm_ctx* ctx, int w, int h, int max_level, pm_py
     PM_REQUIRE(max_level >= 0 && max_level <= 7, PM_E_INVALID, "max_level outside [0, 7]");
     PM_REQUIRE(w >= 1 && h >= 1, PM_E_INVALID, "need w, h >= 1");
     PM_REQUIRE(w >= 16 && h >= 16, PM_E_UNSUPPORTED, "images below 16 pixels a side are not tracked");
-    PM_REQUIRE(static_cast<long long>(w) * h <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(w, h));
     pm_pyramid* p = new pm_pyramid;
     p->device = ctx->device;
     p->w = w;

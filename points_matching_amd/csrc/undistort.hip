@@ -27,7 +27,9 @@ using warp_core::TILE_H;
 using warp_core::PX;
 using warp_core::sample;
 using warp_core::store4;
-using warp_core::clamped_count;
+using pm::clamped_count;
+using pm_image::overlap;
+using pm_image::span;
 
 struct LensArgs {
     double fx, fy, cx, cy;              // K: the camera the lens belongs to
@@ -312,17 +314,9 @@ int check_image_args(const void* src, int sw, int sh, int sstride, const pm_warp
     if (rc != PM_OK) return rc;
     PM_REQUIRE(sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1, PM_E_INVALID, "need sizes >= 1");
     PM_REQUIRE(sstride >= sw && dstride >= dw, PM_E_INVALID, "a stride below its width");
-    PM_REQUIRE(static_cast<long long>(sw) * sh <= 100000000LL && static_cast<long long>(dw) * dh <= 100000000LL, PM_E_UNSUPPORTED,
-               "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(sw, sh));
+    PM_REQUIRE_PASS(pm_image::pixel_cap(dw, dh));
     return PM_OK;
-}
-
-size_t image_span(int w, int h, int stride) { return static_cast<size_t>(h - 1) * stride + w; }
-
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return !(a0 + a_bytes <= b0 || b0 + b_bytes <= a0);
 }
 
 ImageArgs image_args(const uint8_t* src, int sw, int sh, int sstride, const pm_warp_params* p, uint8_t* dst, int dw, int dh, int dstride,
@@ -366,8 +360,7 @@ extern "C" int pm_undistort_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int s
     LensArgs L;
     rc = make_lens(K, lens, R, K_new, &L);
     if (rc != PM_OK) return rc;
-    PM_REQUIRE(!ranges_overlap(d_src, image_span(sw, sh, sstride), d_dst, image_span(dw, dh, dstride)), PM_E_INVALID,
-               "source and destination overlap");
+    PM_REQUIRE(!overlap(d_src, span(sw, sh, sstride, 1), d_dst, span(dw, dh, dstride, 1)), PM_E_INVALID, "source and destination overlap");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     if (d_info) PM_HIP_CHECK(hipMemsetAsync(d_info, 0, sizeof(pm_warp_info), ctx->stream));
     const ImageArgs a = image_args(d_src, sw, sh, sstride, p, d_dst, dw, dh, dstride, d_valid, d_info);
@@ -390,20 +383,10 @@ extern "C" int pm_undistort(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int
     LensArgs L;
     rc = make_lens(K, lens, R, K_new, &L);
     if (rc != PM_OK) return rc;
-    const size_t src_b = image_span(sw, sh, sstride), dst_b = image_span(dw, dh, dstride), val_b = static_cast<size_t>(dw) * dh;
-    pm::StagedBlock b(ctx, __func__);
-    const size_t o_info = b.add(sizeof(pm_warp_info)), o_src = b.add(src_b), o_dst = b.add(dst_b);
-    const size_t o_val = b.add(valid ? val_b : 0);
-    b.alloc();
-    b.upload(o_src, src, src_b);
-    b.upload(o_dst, dst, dst_b);                                  // the bytes between the rows of dst come back as they were
-    if (b.rc == PM_OK)
-        b.rc = pm_undistort_dev(ctx, b.at<uint8_t>(o_src), sw, sh, sstride, K, lens, R, K_new, p, b.at<uint8_t>(o_dst), dw, dh, dstride,
-                                valid ? b.at<uint8_t>(o_val) : nullptr, info ? b.at<pm_warp_info>(o_info) : nullptr);
-    b.download(dst, o_dst, dst_b);
-    if (valid) b.download(valid, o_val, val_b);
-    if (info) b.download(info, o_info, sizeof(pm_warp_info));
-    return b.sync();
+    auto dev = [&](const void*, const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_valid, pm_warp_info* d_info) {
+        return pm_undistort_dev(ctx, d_src, sw, sh, sstride, K, lens, R, K_new, p, d_dst, dw, dh, dstride, d_valid, d_info);
+    };
+    return pm::StagedBlock::image(ctx, __func__, nullptr, 0, src, sw, sh, sstride, dst, dw, dh, dstride, valid, info, dev);
 }
 
 extern "C" int pm_undistort_map_dev(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new, int dw, int dh,
@@ -414,7 +397,7 @@ extern "C" int pm_undistort_map_dev(pm_ctx* ctx, const pm_camera* K, const pm_le
     PM_REQUIRE(d_map != nullptr, PM_E_INVALID, "null pointer");
     PM_REQUIRE((reinterpret_cast<uintptr_t>(d_map) & 7) == 0, PM_E_INVALID, "d_map is not 8-byte aligned");
     PM_REQUIRE(dw >= 1 && dh >= 1, PM_E_INVALID, "need sizes >= 1");
-    PM_REQUIRE(static_cast<long long>(dw) * dh <= 100000000LL, PM_E_UNSUPPORTED, "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(dw, dh));
     LensArgs L;
     const int rc = make_lens(K, lens, R, K_new, &L);
     if (rc != PM_OK) return rc;
@@ -436,9 +419,9 @@ extern "C" int pm_remap_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, i
     const int rc = check_image_args(d_src, sw, sh, sstride, p, d_dst, dw, dh, dstride);
     if (rc != PM_OK) return rc;
     PM_REQUIRE((reinterpret_cast<uintptr_t>(d_map) & 7) == 0, PM_E_INVALID, "d_map is not 8-byte aligned");
-    const size_t dst_b = image_span(dw, dh, dstride);
-    PM_REQUIRE(!ranges_overlap(d_src, image_span(sw, sh, sstride), d_dst, dst_b), PM_E_INVALID, "source and destination overlap");
-    PM_REQUIRE(!ranges_overlap(d_map, static_cast<size_t>(dw) * dh * 8, d_dst, dst_b), PM_E_INVALID, "map and destination overlap");
+    const size_t dst_b = span(dw, dh, dstride, 1);
+    PM_REQUIRE(!overlap(d_src, span(sw, sh, sstride, 1), d_dst, dst_b), PM_E_INVALID, "source and destination overlap");
+    PM_REQUIRE(!overlap(d_map, static_cast<size_t>(dw) * dh * 8, d_dst, dst_b), PM_E_INVALID, "map and destination overlap");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     if (d_info) PM_HIP_CHECK(hipMemsetAsync(d_info, 0, sizeof(pm_warp_info), ctx->stream));
     const ImageArgs a = image_args(d_src, sw, sh, sstride, p, d_dst, dw, dh, dstride, d_valid, d_info);
@@ -458,21 +441,10 @@ extern "C" int pm_remap(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sst
     PM_REQUIRE(map != nullptr, PM_E_INVALID, "null pointer");
     const int rc = check_image_args(src, sw, sh, sstride, p, dst, dw, dh, dstride);
     if (rc != PM_OK) return rc;
-    const size_t src_b = image_span(sw, sh, sstride), dst_b = image_span(dw, dh, dstride), val_b = static_cast<size_t>(dw) * dh;
-    pm::StagedBlock b(ctx, __func__);
-    const size_t o_map = b.add(val_b * 8), o_info = b.add(sizeof(pm_warp_info)), o_src = b.add(src_b), o_dst = b.add(dst_b);
-    const size_t o_val = b.add(valid ? val_b : 0);
-    b.alloc();
-    b.upload(o_map, map, val_b * 8);
-    b.upload(o_src, src, src_b);
-    b.upload(o_dst, dst, dst_b);                                  // the bytes between the rows of dst come back as they were
-    if (b.rc == PM_OK)
-        b.rc = pm_remap_dev(ctx, b.at<uint8_t>(o_src), sw, sh, sstride, b.at<int32_t>(o_map), p, b.at<uint8_t>(o_dst), dw, dh, dstride,
-                            valid ? b.at<uint8_t>(o_val) : nullptr, info ? b.at<pm_warp_info>(o_info) : nullptr);
-    b.download(dst, o_dst, dst_b);
-    if (valid) b.download(valid, o_val, val_b);
-    if (info) b.download(info, o_info, sizeof(pm_warp_info));
-    return b.sync();
+    auto dev = [&](const void* d_map, const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_valid, pm_warp_info* d_info) {
+        return pm_remap_dev(ctx, d_src, sw, sh, sstride, static_cast<const int32_t*>(d_map), p, d_dst, dw, dh, dstride, d_valid, d_info);
+    };
+    return pm::StagedBlock::image(ctx, __func__, map, static_cast<size_t>(dw) * dh * 8, src, sw, sh, sstride, dst, dw, dh, dstride, valid, info, dev);
 }
 
 extern "C" int pm_undistort_points_dev(pm_ctx* ctx, const pm_camera* K, const pm_lens* lens, const double* R, const pm_camera* K_new, int iters,

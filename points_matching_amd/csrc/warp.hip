@@ -7,8 +7,9 @@
 // pixel; a last row of exactly (0, 0, 1) takes a wave-uniform branch without the division.  Source taps are plain global
 // byte loads; a tap of weight zero is never loaded.  The four results leave as one dword where the address is 4-byte aligned
 // and all four are inside the row, as bytes otherwise (the caller's base pointer and stride may be odd).  n_valid: wave
-// ballots, four wave totals through LDS, one integer atomic per workgroup.  The sample, the four-byte store, the ballot count and
-// the count clamp live in warp_core.hpp, which undistort.hip shares.
+// ballots, four wave totals through LDS, one integer atomic per workgroup.  The sample, the four-byte store and the ballot count
+// live in warp_core.hpp, which undistort.hip shares; the count clamp and the host form (StagedBlock::image) in pm_common.hpp,
+// the range and size rules in image_args.hpp.
 //
 // warp_points: one thread per point, the count protocol of pm_track_lk_dev; d_out may be d_pts (a thread reads its own row
 // before it writes it).
@@ -25,7 +26,7 @@ using warp_core::TILE_H;
 using warp_core::PX;
 using warp_core::sample;
 using warp_core::store4;
-using warp_core::clamped_count;
+using pm::clamped_count;
 
 constexpr int KNOWN_FLAGS = PM_WARP_INVERT | PM_WARP_REPLICATE | PM_WARP_AFFINE;
 
@@ -194,8 +195,8 @@ int check_warp_args(const void* src, int sw, int sh, int sstride, const void* M,
     PM_REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0, PM_E_INVALID, "reserved != 0");
     PM_REQUIRE(sw >= 1 && sh >= 1 && dw >= 1 && dh >= 1, PM_E_INVALID, "need sizes >= 1");
     PM_REQUIRE(sstride >= sw && dstride >= dw, PM_E_INVALID, "a stride below its width");
-    PM_REQUIRE(static_cast<long long>(sw) * sh <= 100000000LL && static_cast<long long>(dw) * dh <= 100000000LL, PM_E_UNSUPPORTED,
-               "more than 100 000 000 pixels");
+    PM_REQUIRE_PASS(pm_image::pixel_cap(sw, sh));
+    PM_REQUIRE_PASS(pm_image::pixel_cap(dw, dh));
     return PM_OK;
 }
 
@@ -206,8 +207,6 @@ int check_points_args(const void* M, int flags, const void* pts, const void* out
     return PM_OK;
 }
 
-size_t image_span(int w, int h, int stride) { return static_cast<size_t>(h - 1) * stride + w; }
-
 }  // namespace
 
 extern "C" int pm_warp_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, int sstride, const double* d_M, const pm_warp_params* p,
@@ -217,8 +216,7 @@ extern "C" int pm_warp_dev(pm_ctx* ctx, const uint8_t* d_src, int sw, int sh, in
     PM_REFUSE_CAPTURE(ctx);
     const int rc = check_warp_args(d_src, sw, sh, sstride, d_M, p, d_dst, dw, dh, dstride);
     if (rc != PM_OK) return rc;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-    PM_REQUIRE(s0 + image_span(sw, sh, sstride) <= d0 || d0 + image_span(dw, dh, dstride) <= s0, PM_E_INVALID,
+    PM_REQUIRE(!pm_image::overlap(d_src, pm_image::span(sw, sh, sstride, 1), d_dst, pm_image::span(dw, dh, dstride, 1)), PM_E_INVALID,
                "source and destination overlap");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     if (d_info) PM_HIP_CHECK(hipMemsetAsync(d_info, 0, sizeof(pm_warp_info), ctx->stream));
@@ -243,22 +241,11 @@ extern "C" int pm_warp(pm_ctx* ctx, const uint8_t* src, int sw, int sh, int sstr
     PM_REFUSE_CAPTURE(ctx);
     const int rc = check_warp_args(src, sw, sh, sstride, M, p, dst, dw, dh, dstride);
     if (rc != PM_OK) return rc;
-    const size_t src_b = image_span(sw, sh, sstride), dst_b = image_span(dw, dh, dstride), val_b = static_cast<size_t>(dw) * dh;
     const size_t m_b = sizeof(double) * ((p->flags & PM_WARP_AFFINE) ? 6 : 9);
-    pm::StagedBlock b(ctx, __func__);
-    const size_t o_m = b.add(m_b), o_info = b.add(sizeof(pm_warp_info)), o_src = b.add(src_b), o_dst = b.add(dst_b);
-    const size_t o_val = b.add(valid ? val_b : 0);
-    b.alloc();
-    b.upload(o_src, src, src_b);
-    b.upload(o_m, M, m_b);
-    b.upload(o_dst, dst, dst_b);                                  // the bytes between the rows of dst come back as they were
-    if (b.rc == PM_OK)
-        b.rc = pm_warp_dev(ctx, b.at<uint8_t>(o_src), sw, sh, sstride, b.at<double>(o_m), p, b.at<uint8_t>(o_dst), dw, dh, dstride,
-                           valid ? b.at<uint8_t>(o_val) : nullptr, info ? b.at<pm_warp_info>(o_info) : nullptr);
-    b.download(dst, o_dst, dst_b);
-    if (valid) b.download(valid, o_val, val_b);
-    if (info) b.download(info, o_info, sizeof(pm_warp_info));
-    return b.sync();
+    auto dev = [&](const void* d_M, const uint8_t* d_src, uint8_t* d_dst, uint8_t* d_valid, pm_warp_info* d_info) {
+        return pm_warp_dev(ctx, d_src, sw, sh, sstride, static_cast<const double*>(d_M), p, d_dst, dw, dh, dstride, d_valid, d_info);
+    };
+    return pm::StagedBlock::image(ctx, __func__, M, m_b, src, sw, sh, sstride, dst, dw, dh, dstride, valid, info, dev);
 }
 
 extern "C" int pm_transform_points_dev(pm_ctx* ctx, const double* d_M, int flags, const float* d_pts, const int32_t* d_n, int cap,

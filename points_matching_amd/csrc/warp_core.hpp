@@ -66,11 +66,4 @@ __device__ __forceinline__ void block_valid_totals(const int ok[PX], int* s_cnt,
 }
 __device__ __forceinline__ int block_valid_sum(const int* s_cnt) { return (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]); }
 
-// n = *d_n clamped to [0, cap]; NULL = cap (the -1 that the point sources write on overflow counts as 0)
-__device__ __forceinline__ int clamped_count(const int32_t* d_n, int cap)
-{
-    const int n = d_n ? *d_n : cap;
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
 }  // namespace warp_core

@@ -134,6 +134,24 @@ def test_disparity_counts_around_the_register_groups(ctx, D, flags):
     assert n > 0
 
 
+@pytest.mark.parametrize("uniq", [0, 15])
+@pytest.mark.parametrize("flags", [0, S.FROM_RIGHT])
+@pytest.mark.parametrize("shift", [62, 63, 64, 65])
+def test_winner_on_either_side_of_a_register_group_edge(ctx, shift, flags, uniq):
+    """The winner at disparity index 62 .. 65 of 128: the parabola's neighbours k1 - 1 and k1 + 1 are lanes 63 and 0 of two
+    different register groups (the sweep above puts k1 at 63 for D = 65 and never at 64).  test_sgm_gpu.py has the same for the
+    winner's other caller."""
+    D, r = 128, 2
+    w = D + 77
+    base = np.random.default_rng(640 + shift).integers(0, 256, (9, w + 300)).astype(np.uint8)
+    left, right = base[:, :w], base[:, shift:w + shift]
+    disp, n = check(ctx, left, right, 0, D, r, uniq, flags)
+    x0, x1 = S.computed_columns(w, 0, D, r, flags)
+    got = disp[r:9 - r, x0:x1 + 1].astype(np.int64)
+    assert got.size == 370 == n and (((got + 8) >> 4) == shift).all()
+    assert ((got & 15) != 0).any()                                    # sub-pixel parts: the neighbour reads took part
+
+
 @pytest.mark.parametrize("flags", [0, S.FROM_RIGHT])
 def test_256_disparities(ctx, flags):
     rng = np.random.default_rng(256)
