@@ -758,7 +758,7 @@ int pm_estimate_pose_refined(pm_ctx* ctx, const float* xy1, const float* xy2, in
                              uint8_t* mask, int* n_inliers, int* n_good, uint64_t* best_key, pm_h_refine_info* info);
 
 /* ---- absolute camera pose (cv::solvePnPRansac with SOLVEPNP_P3P: locating a new frame against 3-D points that are
- * already known, e.g. those pm_recover_pose triangulates) — docs/SPEC.md S36-S39.  Correspondence i is a world point
+ * already known: the map pm_triangulate* builds from posed views, below) — docs/SPEC.md S36-S39.  Correspondence i is a world point
  * xyz[3i .. 3i+2] and its pixel uv[2i .. 2i+1] (f32).  One pinhole pm_camera K, no distortion (pixels of a real lens
  * go through pm_undistort_points* first, S81); K is invalid unless fx, fy > 0
  * and all four values are finite.  Pose: x_cam = R X + t, pixel ~ K x_cam; R 9 doubles row-major, t 3 doubles.
@@ -823,6 +823,60 @@ int pm_solve_pnp_ransac(pm_ctx* ctx, const float* xyz, const float* uv, int n, c
  * {d_xyz, d_uv, d_count, cap} feeds pm_ransac_pnp_run_dev.  An index out of range gives a NaN row (never an inlier). */
 int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_kp_xy, int n_kp,
                       const float* d_obj_xyz, int n_obj, float* d_uv, float* d_xyz);
+
+/* ---- triangulation: map points from 2 .. 8 posed views (cv::triangulatePoints, then the step a map builder runs behind
+ * it: refine the point on its reprojection error and keep it only if it lies in front of every camera, has enough
+ * parallax and reprojects well) — docs/SPEC.md S93-S96.  The structure-only half of bundle adjustment; pm_pnp_refine* is
+ * the motion-only half, and a caller can alternate them on one stream.  Point i is seen at pixel uv[v][2i .. 2i+1] (f32)
+ * of view v, whose pose is x_cam = R X + t as for PnP; one pinhole pm_camera K for every view, no distortion (pixels of a
+ * real lens go through pm_undistort_points* first).  Per point, all fp64: the linear solution of the 2V x 4 DLT system
+ * (S35's, generalised; a view that does not observe the point contributes zero rows), Levenberg-Marquardt over (X, Y, Z)
+ * on the summed squared pixel error with S24's damping (only cost decreases are accepted, so the refined cost is never
+ * above the linear one and an unrefined point is returned bit for bit), then three gates at the final point, the first
+ * failure being the status: depth in (0, max_depth) in every observing view, the smallest cosine between the rays of two
+ * observing views < max_cos_parallax, every observing view's pixel error <= max_reproj_px.  One launch, one lane per
+ * point; the pointer arrays live in the struct because observations and poses lie wherever earlier calls left them (the
+ * xy1 / xy2 of a pm_points_view, the output of pm_track_lk_gather_dev, the d_Rt of pm_pnp_refine_dev or
+ * pm_pose_refine_dev).  A NULL pose is [I|0] exactly: the first camera of pm_recover_pose_dev. */
+#define PM_TRI_MAX_VIEWS 8
+#define PM_TRI_USE_INITIAL 1   /* skip the linear stage: start from the rows already in d_xyz (re-refine a map) */
+
+typedef struct pm_tri_views {
+    const float*   uv[PM_TRI_MAX_VIEWS];  /* view v: cap x 2 pixels (f32), row i = point i; a row S31 turns into NaN
+                                             (NaN, inf, |value| > 2^20) means "not seen in this view" */
+    const double*  Rt[PM_TRI_MAX_VIEWS];  /* view v: 12 doubles (R row-major, then t), x_cam = R X + t as S36;
+                                             NULL = [I|0] exactly */
+    const int32_t* count;                 /* device-side point count, clamped to [0, cap]; NULL: cap */
+    int32_t n_views, cap;
+} pm_tri_views;
+
+typedef struct pm_tri_params {
+    double  max_reproj_px;     /* finite, > 0: largest pixel error allowed in any observing view */
+    double  max_cos_parallax;  /* in (-1, 1]: the widest-angle pair of rays must have cos < this; 1 switches the test off */
+    double  max_depth;         /* > 0, may be +inf: depth in every observing view must lie in (0, max_depth) */
+    int32_t max_iters;         /* [0, 100]; 0 = linear solution only */
+    int32_t flags;
+} pm_tri_params;
+
+enum { PM_TRI_OK = 0, PM_TRI_FEW_VIEWS = 1, PM_TRI_DEGENERATE = 2, PM_TRI_DEPTH = 3, PM_TRI_PARALLAX = 4, PM_TRI_REPROJ = 5 };
+
+/* Device form.  Outputs, row i for point i, rows at or beyond the count not written: d_xyz cap x 3 f32 world points, NaN
+ * unless the status is PM_TRI_OK (pm_gather_pnp_dev and the PnP scorer treat a NaN row as "never an inlier"; nothing is
+ * compacted, so a caller's track table, descriptors and map rows keep one index); d_status cap bytes (PM_TRI_*: fewer
+ * than two observing views, a point at infinity or a non-finite start, then the gates); d_points4 (may be NULL) the
+ * linear stage's homogeneous Q as 4 floats per point, the layout and meaning of cv::triangulatePoints and of
+ * pm_recover_pose's points4 — written whatever the status, not written under PM_TRI_USE_INITIAL; d_err2 (may be NULL) the
+ * largest squared pixel error over the observing views at the final point, NaN unless PM_TRI_OK; *d_n_good (may be NULL)
+ * the number of PM_TRI_OK rows.  Under PM_TRI_USE_INITIAL the start is the f32 row already in d_xyz.  Data outcomes are
+ * reported per point only.  PM_E_INVALID: a null context, struct, K, params, d_xyz, d_status or uv[v] of a view below
+ * n_views, n_views outside [2, 8], cap < 0, a bad K (S31's rule), a parameter outside the ranges above, an unknown flag.
+ * No per-call state: the call may be captured. */
+int pm_triangulate_dev(pm_ctx* ctx, const pm_tri_views* views, const pm_camera* K, const pm_tri_params* p,
+                       float* d_xyz, uint8_t* d_status, float* d_points4, float* d_err2, int32_t* d_n_good);
+/* Host in, host out: uv and Rt are arrays of n_views host pointers (Rt[v] may be NULL), n points; one staged block, one
+ * synchronisation.  Under PM_TRI_USE_INITIAL xyz is read as well as written. */
+int pm_triangulate(pm_ctx* ctx, const float* const* uv, const double* const* Rt, int n_views, int n, const pm_camera* K,
+                   const pm_tri_params* p, float* xyz, uint8_t* status, float* points4, float* err2, int* n_good);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

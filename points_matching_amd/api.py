@@ -64,7 +64,7 @@ EXPORTS = [
     "pm_fundamental_refine", "pm_fundamental_refine_dev", "pm_ransac_fundamental_refined",
     "pm_pose_refine", "pm_pose_refine_dev", "pm_estimate_pose_refined",
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
-    "pm_solve_pnp_ransac", "pm_gather_pnp_dev",
+    "pm_solve_pnp_ransac", "pm_gather_pnp_dev", "pm_triangulate_dev", "pm_triangulate",
     "pm_filter_cross", "pm_filter_cross_gather_dev",
     "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
     "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
@@ -253,6 +253,42 @@ def stereo_rectify(R, t):
 class PnpView(C.Structure):
     """pm_pnp_view: world points (cap x 3) and pixels (cap x 2) on the device with an optional device-side count."""
     _fields_ = [("xyz", C.c_void_p), ("uv", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_int32), ("reserved", C.c_int32)]
+
+
+PM_TRI_MAX_VIEWS = 8
+PM_TRI_USE_INITIAL = 1
+PM_TRI_OK, PM_TRI_FEW_VIEWS, PM_TRI_DEGENERATE, PM_TRI_DEPTH, PM_TRI_PARALLAX, PM_TRI_REPROJ = 0, 1, 2, 3, 4, 5
+
+
+class TriViews(C.Structure):
+    """pm_tri_views: per view a device array of cap x 2 pixels and a device pose of 12 doubles (NULL: [I|0]), with an
+    optional device-side count; tri_views() fills it."""
+    _fields_ = [("uv", C.c_void_p * PM_TRI_MAX_VIEWS), ("Rt", C.c_void_p * PM_TRI_MAX_VIEWS), ("count", C.c_void_p),
+                ("n_views", C.c_int32), ("cap", C.c_int32)]
+
+
+class TriParams(C.Structure):
+    """pm_tri_params (include/pm.h, SPEC S93-S96); tri_params() fills it."""
+    _fields_ = [("max_reproj_px", C.c_double), ("max_cos_parallax", C.c_double), ("max_depth", C.c_double),
+                ("max_iters", C.c_int32), ("flags", C.c_int32)]
+
+
+def tri_params(max_reproj_px=3.0, max_cos_parallax=0.9998, max_depth=float("inf"), max_iters=10, flags=0):
+    """max_cos_parallax 1 switches the parallax test off; max_iters 0 keeps the linear solution; flags: 0 or
+    PM_TRI_USE_INITIAL."""
+    return TriParams(max_reproj_px, max_cos_parallax, max_depth, max_iters, flags)
+
+
+def tri_views(uv_ptrs, Rt_ptrs, cap, count_ptr=None):
+    """A TriViews from device pointers: uv_ptrs[v] the pixels of view v, Rt_ptrs[v] its pose (None or 0: [I|0])."""
+    if len(uv_ptrs) != len(Rt_ptrs) or len(uv_ptrs) > PM_TRI_MAX_VIEWS:
+        raise ValueError("one pose per view, at most %d views" % PM_TRI_MAX_VIEWS)
+    v = TriViews()
+    for i, (u, r) in enumerate(zip(uv_ptrs, Rt_ptrs)):
+        v.uv[i] = u or None
+        v.Rt[i] = r or None
+    v.count, v.n_views, v.cap = count_ptr or None, len(uv_ptrs), cap
+    return v
 
 
 class HRefineInfo(C.Structure):
@@ -1509,6 +1545,35 @@ class Context:
         """Compacted matches -> PnP rows on the device (uv = keypoint of queryIdx, xyz = map point of trainIdx)."""
         _check(lib().pm_gather_pnp_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dkp_ptr),
                                        n_kp, C.c_void_p(dobj_ptr), n_obj, C.c_void_p(duv_ptr), C.c_void_p(dxyz_ptr)))
+
+    # -- triangulation (cv::triangulatePoints + refinement + the map builder's gates, SPEC S93-S96) ----------------------
+    def triangulate_dev(self, views, K, params, dxyz_ptr, dstatus_ptr, dpoints4_ptr=None, derr2_ptr=None, dngood_ptr=None):
+        """Device form over a TriViews: d_xyz cap x 3 f32 (NaN unless PM_TRI_OK; read under PM_TRI_USE_INITIAL), d_status
+        cap bytes, optional d_points4 (cap x 4 f32), d_err2 (cap f32) and *d_n_good (int32).  Asynchronous on the stream."""
+        _check(lib().pm_triangulate_dev(self._h, C.byref(views), C.byref(_camera(K)), C.byref(params), C.c_void_p(dxyz_ptr),
+                                        C.c_void_p(dstatus_ptr), C.c_void_p(dpoints4_ptr), C.c_void_p(derr2_ptr),
+                                        C.c_void_p(dngood_ptr)))
+
+    def triangulate(self, uv, Rt, K, params=None, xyz0=None):
+        """uv: one (n, 2) pixel array per view (a NaN row: not seen there); Rt: one pose per view (12 doubles, R row-major
+        then t, or None for [I|0]).  xyz0: the start under PM_TRI_USE_INITIAL.  Returns (xyz (n, 3), status (n), points4
+        (n, 4), err2 (n), n_good); points4 is zero under PM_TRI_USE_INITIAL."""
+        params = params if params is not None else tri_params()
+        uv = [np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in uv]
+        n = uv[0].shape[0] if uv else 0
+        if any(u.shape[0] != n for u in uv) or len(Rt) != len(uv):
+            raise ValueError("every view needs n pixel rows and a pose")
+        poses = [None if r is None else np.ascontiguousarray(r, np.float64).reshape(12) for r in Rt]
+        up = (C.c_void_p * max(len(uv), 1))(*[_p(u) for u in uv])
+        rp = (C.c_void_p * max(len(uv), 1))(*[_p(r) for r in poses])
+        xyz = np.zeros((max(n, 1), 3), np.float32)
+        if xyz0 is not None:
+            xyz[:n] = np.asarray(xyz0, np.float32).reshape(-1, 3)
+        status, p4, e2 = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 4), np.float32), np.zeros(max(n, 1), np.float32)
+        ng = C.c_int()
+        _check(lib().pm_triangulate(self._h, up, rp, len(uv), n, C.byref(_camera(K)), C.byref(params), _p(xyz), _p(status),
+                                    _p(p4), _p(e2), C.byref(ng)))
+        return xyz[:n], status[:n], p4[:n], e2[:n], ng.value
 
 
 class Pyramid:

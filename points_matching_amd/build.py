@@ -21,7 +21,7 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
-           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip"]
+           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip", "triangulate.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -61,7 +61,10 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          "stereo.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # semi-global matching (S89-S92): a wave walks a path with a lane per disparity, the next step's words and sums loaded
          # ahead; no kernel may use scratch or spill
-         "stereo_sgm.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "stereo_sgm.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # triangulation (S93-S96): a lane owns a point, its 2V x 4 fp64 system and V pixels in registers, one instantiation per
+         # view count; none may use scratch or spill
+         "triangulate.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

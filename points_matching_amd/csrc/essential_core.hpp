@@ -516,11 +516,43 @@ __device__ __forceinline__ bool decompose(const double (&E)[9], Poses& ps)
     return true;
 }
 
+// S35 step 2 on ROWS DLT rows (S94: two per view): one-sided Jacobi on the 4 columns of A with V = I, SWEEPS_T sweeps,
+// Q = the column of V at the first strict minimum column norm.  A row of zeros changes no bit of any sum.
+template <int ROWS>
+__device__ __forceinline__ void dlt_null_vector(double (&A)[ROWS][4], double (&Q)[4])
+{
+    double V[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) V[r][c] = r == c ? 1.0 : 0.0;
+    for (int s = 0; s < SWEEPS_T; ++s) {
+        jacobi_cols<ROWS, 4, 0, 1>(A, V);
+        jacobi_cols<ROWS, 4, 0, 2>(A, V);
+        jacobi_cols<ROWS, 4, 0, 3>(A, V);
+        jacobi_cols<ROWS, 4, 1, 2>(A, V);
+        jacobi_cols<ROWS, 4, 1, 3>(A, V);
+        jacobi_cols<ROWS, 4, 2, 3>(A, V);
+    }
+    double cm = colnorm2<ROWS, 4>(A, 0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) Q[i] = V[i][0];
+#pragma unroll
+    for (int p = 1; p < 4; ++p) {
+        const double c = colnorm2<ROWS, 4>(A, p);
+        if (c < cm) {
+            cm = c;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Q[i] = V[i][p];
+        }
+    }
+}
+
 // S35: linear DLT of one correspondence against [I|0] and [R|t] (t = sg * ps.t): homogeneous Q
 __device__ __forceinline__ void triangulate(const double (&R)[9], const double (&t)[3], double x1, double y1, double x2,
                                             double y2, double (&Q)[4])
 {
-    double A[4][4], V[4][4];
+    double A[4][4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const double p0 = c < 3 ? R[c] : t[0], p1 = c < 3 ? R[3 + c] : t[1], p2 = c < 3 ? R[6 + c] : t[2];
@@ -528,29 +560,8 @@ __device__ __forceinline__ void triangulate(const double (&R)[9], const double (
         A[1][c] = c == 1 ? -1.0 : (c == 2 ? y1 : 0.0);
         A[2][c] = x2 * p2 - p0;
         A[3][c] = y2 * p2 - p1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) V[r][c] = r == c ? 1.0 : 0.0;
     }
-    for (int s = 0; s < SWEEPS_T; ++s) {
-        jacobi_cols<4, 4, 0, 1>(A, V);
-        jacobi_cols<4, 4, 0, 2>(A, V);
-        jacobi_cols<4, 4, 0, 3>(A, V);
-        jacobi_cols<4, 4, 1, 2>(A, V);
-        jacobi_cols<4, 4, 1, 3>(A, V);
-        jacobi_cols<4, 4, 2, 3>(A, V);
-    }
-    double cm = colnorm2<4, 4>(A, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) Q[i] = V[i][0];
-#pragma unroll
-    for (int p = 1; p < 4; ++p) {
-        const double c = colnorm2<4, 4>(A, p);
-        if (c < cm) {
-            cm = c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) Q[i] = V[i][p];
-        }
-    }
+    dlt_null_vector<4>(A, Q);
 }
 
 // S35: OpenCV's cheirality tests of Q for [R|t]
