@@ -1112,39 +1112,46 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void knn_
 }
 
 // ---------------------------------------------------------------------------------------------
-// u8 route refinement (round 3): one wave per query, ONE LANE PER CANDIDATE ROW.  For u8-valued data every partial sum
+// u8 route refinement (round 3; rows read eight lanes to a row since round 5).  For u8-valued data every partial sum
 // of the canonical f32 distance (SPEC S1) is an integer below 2^24, i.e. the canonical value IS the integer squared
-// distance, whatever the summation order — so the rows are re-evaluated on the centred byte copies the coarse pass
-// already made: d2 = ||q'||^2 + ||t'||^2 - 2 q'.t' with 32 v_dot4_i32_i8 per row (128 B per row instead of 512 B and
-// ~400 f32 operations), distance = sqrtf(float(d2)) (correctly rounded), key = (distance bits, index) as everywhere.
-// Candidate groups hold GROUP = 4, 8 or 16 rows (the coarse kernel's selection cost falls with the group size; here
-// 64 rows cost what one costs).  A wrong hint (bit 1 of stats[1]) sends every query to the canonical f32 scan.
+// distance, whatever the summation order and whichever lanes add which bytes — so the rows are re-evaluated on the
+// centred byte copies the coarse pass already made: d2 = ||q'||^2 + ||t'||^2 - 2 q'.t' with 32 v_dot4_i32_i8 per row
+// (128 B per row instead of 512 B and ~400 f32 operations), distance = sqrtf(float(d2)) (correctly rounded), key =
+// (distance bits, index) as everywhere.  Candidate groups hold GROUP = 4, 8 or 16 rows (the coarse kernel's selection
+// cost falls with the group size).  A wrong hint (bit 1 of stats[1]) sends every query to the canonical f32 scan.
+//
+// A row is read by EIGHT lanes, lane `sub` taking its 16-byte unit `sub` (with wide rows: of the row's first eight
+// units), so one load instruction of the wave fetches eight whole 128-byte rows in eight cache lines.  The first form let
+// one lane read one whole row as eight 16-byte loads 128 bytes apart: every instruction touched 64 lines and every line
+// was visited eight times (the pattern of coarse form 4).  Each lane multiplies its unit with the same unit of
+// the query (4 v_dot4_i32_i8) and three DPP adds inside the eight lanes leave the row's dot product in every one of them.
+// Eight such steps cover eight rows per eight lanes, and the lane with sub == step keeps that step's sum: every lane
+// still owns one row per pass, and everything after the sum (tnorm, sqrtf, the per-lane BestN) is what it was.  DPP needs
+// whole rows of lanes: a lane group with no row left loads from a valid row and drops the sum.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int u8_row_d2(const uint4 (&qv)[U8_ROW16], const uint4* __restrict__ T8, int row, int qn,
-                                         const float* __restrict__ tnorm, int t_row16)
+__device__ __forceinline__ int u8_unit_dot8(const uint4& qu, const uint4& tu)
 {
-    const uint4* tp = T8 + static_cast<size_t>(row) * t_row16;
-    uint4 tv[U8_ROW16];
-#pragma unroll
-    for (int i = 0; i < U8_ROW16; ++i) tv[i] = tp[i];
-    const int tn = static_cast<int>(tnorm[row]);
-    int d0 = 0, d1 = 0;
-#pragma unroll
-    for (int i = 0; i < U8_ROW16; ++i) {
-        d0 = __builtin_amdgcn_sdot4(static_cast<int>(qv[i].x), static_cast<int>(tv[i].x), d0, false);
-        d1 = __builtin_amdgcn_sdot4(static_cast<int>(qv[i].y), static_cast<int>(tv[i].y), d1, false);
-        d0 = __builtin_amdgcn_sdot4(static_cast<int>(qv[i].z), static_cast<int>(tv[i].z), d0, false);
-        d1 = __builtin_amdgcn_sdot4(static_cast<int>(qv[i].w), static_cast<int>(tv[i].w), d1, false);
-    }
-    return qn + tn - 2 * (d0 + d1);
+    int a = __builtin_amdgcn_sdot4(static_cast<int>(qu.x), static_cast<int>(tu.x), 0, false);
+    a = __builtin_amdgcn_sdot4(static_cast<int>(qu.y), static_cast<int>(tu.y), a, false);
+    a = __builtin_amdgcn_sdot4(static_cast<int>(qu.z), static_cast<int>(tu.z), a, false);
+    a = __builtin_amdgcn_sdot4(static_cast<int>(qu.w), static_cast<int>(tu.w), a, false);
+    // (pm::dpp_u32 with old = 0 and bound_ctrl: every source lane is live, and in this form the add takes the DPP operand
+    // itself — v_add_u32_dpp, three instructions for the three steps instead of six)
+    a += __builtin_amdgcn_update_dpp(0, a, 0xB1, 0xF, 0xF, true);          // quad_perm:[1,0,3,2]
+    a += __builtin_amdgcn_update_dpp(0, a, 0x4E, 0xF, 0xF, true);          // quad_perm:[2,3,0,1]
+    a += __builtin_amdgcn_update_dpp(0, a, 0x141, 0xF, 0xF, true);         // row_half_mirror: the other quad of the eight
+    return a;
 }
 
 // FOUR queries per wave, one 16-lane row each: the candidate slots of a query (32 at config C3) never filled a wave, and
 // the first form of this kernel (one wave per query, ~300 instructions, like knn_l2_refine) was issue-bound at ~5 us for
 // 8192 queries.  Here the k-th-smallest search and the final top-k are 4-step DPP reductions inside a row (row_ror: no
 // cross-row traffic, no v_readlane) shared by four queries, and the usual two candidate groups of 8 rows are exactly
-// one row of lanes.  A query with an overflowing list, fewer than k ranked groups or a wrong hint scans all train rows
-// (rare; 16 lanes wide).
+// one pass of a row of lanes: 16 candidate rows per query and pass.  The 16 lanes read them as two halves of eight
+// (u8_unit_dot8 above): in step j = 0..7 half hh = l >> 3 reads candidate r0 + 2j + hh, so a load instruction of the wave
+// covers 4 queries x 2 rows x 128 B, and lane (hh, sub) ends the pass owning candidate r0 + 2 sub + hh.  A lane holds
+// one 16-byte unit of its query, not the whole row.  A query with an overflowing list, fewer than k ranked groups or a
+// wrong hint scans all train rows (rare).
 __device__ __forceinline__ unsigned row_min_u32(unsigned v)          // minimum over the lane's 16-lane row, in every lane of it
 {
     v = min(v, pm::dpp_u32<0x121>(v));
@@ -1168,44 +1175,38 @@ __device__ __forceinline__ unsigned long long row_min_u64(unsigned long long v)
 // slowest wave the matcher call went from 23 to 225 us with 52 such queries among 8192 (1 ms at 32k x 32k).  Now only the
 // spilled SPLITS are evaluated, by all 64 lanes of the wave for one of its four queries at a time (a variant that handed
 // them to the whole workgroup cut the tail further but cost every launch a barrier: +1 us at config C3).
-template <int KM, int U, int LANES>
-__device__ __forceinline__ void r8_scan_rows(BestN<KM>& tb, const uint4 (&qv)[U8_ROW16], int qn, const uint4* __restrict__ T8,
-                                             const float* __restrict__ tnorm, int t_row16, int row_begin, int row_end, int me)
+//
+// The rows are read like the common path's (u8_unit_dot8): `qu` is unit lane & 7 of the owner's query, and in step
+// j = 0..7 the eight lanes of group g = lane >> 3 read row base + 8j + g, so a load instruction of the wave fetches eight
+// consecutive rows.  The lane with (lane & 7) == j keeps step j's sum: a lane inserts one row per 64, as before.  All eight
+// loads of an iteration are in flight at once: round 3 split a row into two halves because whole rows in flight cost the
+// common path a wave per SIMD (106 VGPRs); with one query unit per lane the compiler's resource report shows no
+// instantiation losing occupancy (82 VGPRs at most for k <= 2, 90 for k <= 4), so the split is gone.
+template <int KM>
+__device__ __forceinline__ void r8_scan_rows(BestN<KM>& tb, const uint4& qu, int qn, const uint4* __restrict__ T8,
+                                             const float* __restrict__ tnorm, int t_row16, int row_begin, int row_end, int lane)
 {
-    for (int base = row_begin; base < row_end; base += LANES * U) {
-        int d2[U];
-        bool ok[U];
+    const int sub = lane & 7, g = lane >> 3;
+    for (int base = row_begin; base < row_end; base += 64) {
+        const int row = base + 8 * sub + g;
+        const bool ok = row < row_end;
+        float tn = tnorm[ok ? row : row_begin];
+        uint4 tv[8];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int row = base + u * LANES + me;
-            ok[u] = row < row_end;
-            // the row in two halves of four 16-byte loads: the register peak of this rare path must not cost the common
-            // path a wave per SIMD (whole rows in flight: 106 VGPRs, 4 waves; measured +0.25 us per launch at config C3)
-            const uint4* tp = T8 + static_cast<size_t>(ok[u] ? row : row_begin) * t_row16;
-            int acc = 0;
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                uint4 tv[U8_ROW16 / 2];
-#pragma unroll
-                for (int i = 0; i < U8_ROW16 / 2; ++i) tv[i] = tp[hf * (U8_ROW16 / 2) + i];
-#pragma unroll
-                for (int i = 0; i < U8_ROW16 / 2; ++i) {
-                    const uint4 a = qv[hf * (U8_ROW16 / 2) + i];
-                    acc = __builtin_amdgcn_sdot4(static_cast<int>(a.x), static_cast<int>(tv[i].x), acc, false);
-                    acc = __builtin_amdgcn_sdot4(static_cast<int>(a.y), static_cast<int>(tv[i].y), acc, false);
-                    acc = __builtin_amdgcn_sdot4(static_cast<int>(a.z), static_cast<int>(tv[i].z), acc, false);
-                    acc = __builtin_amdgcn_sdot4(static_cast<int>(a.w), static_cast<int>(tv[i].w), acc, false);
-                }
-                asm volatile("" : "+v"(acc));                 // (keeps the second half's loads behind the first half's use)
-            }
-            d2[u] = qn + static_cast<int>(tnorm[ok[u] ? row : row_begin]) - 2 * acc;
+        for (int j = 0; j < 8; ++j) {                         // (all eight loads ahead of the first use)
+            const int rj = base + 8 * j + g;
+            tv[j] = T8[static_cast<size_t>(rj < row_end ? rj : row_begin) * t_row16 + sub];
         }
+        asm volatile("" : "+v"(tn));                          // (the norm travels with the rows)
+        int acc = 0;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int row = base + u * LANES + me;
-            const float d = __builtin_sqrtf(static_cast<float>(d2[u]));
-            if (ok[u]) tb.insert(knn_key(d, row), d);
+        for (int j = 0; j < 8; ++j) {
+            const int sum = u8_unit_dot8(qu, tv[j]);
+            acc = sub == j ? sum : acc;
         }
+        asm volatile("" : "+v"(acc));                         // (sums and selects stay with their DPP moves)
+        const float d = __builtin_sqrtf(static_cast<float>(qn + static_cast<int>(tn) - 2 * acc));
+        if (ok) tb.insert(knn_key(d, row), d);
     }
 }
 
@@ -1233,9 +1234,8 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
     if (diag && threadIdx.x == 0 && blockIdx.x == 0) diag[2] = 3u;
     const int qn = static_cast<int>(qnorm[qc]);
     const int* cv = cand + static_cast<size_t>(qc) * slots;
-    uint4 qv[U8_ROW16];                                      // the query's centred bytes (one address per row of lanes)
-#pragma unroll
-    for (int i = 0; i < U8_ROW16; ++i) qv[i] = Q8[static_cast<size_t>(qc) * U8_ROW16 + i];
+    const int sub = l & 7, hf = l >> 3;                      // 16-byte unit of a row, and half of the 16-lane row
+    const uint4 qu = Q8[static_cast<size_t>(qc) * U8_ROW16 + sub];         // the lane's unit of the query's centred bytes
 
     // slot s = l + 16*i: candidate (w << U8_SHIFT) | (group id << 1 | lane half); coarse squared distance
     // d2a = ||q'||^2 - 2w = d2 or d2 - 1 of the group's best row
@@ -1297,19 +1297,45 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
 
     BestN<KM> b;
     b.init();
-    auto take = [&](int row) {
-        const int d2 = u8_row_d2(qv, T8, row, qn, tnorm, t_row16);
-        const float d = __builtin_sqrtf(static_cast<float>(d2));
-        b.insert(knn_key(d, row), d);
-    };
-    const int nrows = full ? 0 : total * GROUP;
-    for (int r0 = 0; __any(r0 < nrows); r0 += 16) {          // one row per lane, 16 per query and pass
-        const int idx = r0 + l;
-        if (idx < nrows) {
-            const int cd = clist[wave][qi][idx / GROUP];
-            const int reg = ((cd >> 1) & 15) * GROUP + idx % GROUP;
-            const int row = (cd & ~31) + (reg & 3) + 8 * (reg >> 2) + 4 * (cd & 1);
-            if (row < nt) take(row);
+    // Candidate p = 0..15 of a pass is row p % GROUP of group p / GROUP of the pass; rows of a group come four in a run, the
+    // next four 8 further on.  Step j gives this half candidate 2j + hf, so that the lane ends up owning candidate 2 sub + hf.
+    constexpr unsigned NO_ROW = 0x7FFFFF00u;                 // first row of a group past the list: no train set has it
+    auto group_row = [](int pos) { return (pos & 3) + 8 * (pos >> 2); };
+    const int ngroups = full ? 0 : total;
+    const int own_grp = (2 * sub) / GROUP, own_off = group_row((2 * sub) % GROUP);
+    const char* tunit = reinterpret_cast<const char*>(T8 + sub);           // the lane's unit of row 0
+    const unsigned tpitch = 16u * static_cast<unsigned>(t_row16), last = static_cast<unsigned>(nt - 1);
+    for (int g0 = 0; __any(g0 < ngroups); g0 += GPB) {       // 16 rows per query and pass; a lane ends up owning one
+        unsigned first[GPB];                                 // first row of the pass's groups, + hf
+#pragma unroll
+        for (int g = 0; g < GPB; ++g) {
+            const int cd = clist[wave][qi][g0 + g];          // (past the list: whatever LDS held)
+            const unsigned r = static_cast<unsigned>((cd & ~31) + 8 * (GROUP / 4) * ((cd >> 1) & 15) + 4 * (cd & 1) + hf);
+            first[g] = g0 + g < ngroups ? r : NO_ROW;
+        }
+        unsigned mine = first[0];
+#pragma unroll
+        for (int g = 1; g < GPB; ++g) mine = own_grp == g ? first[g] : mine;
+        mine += own_off;
+        float tn = tnorm[min(mine, last)];
+        uint4 tv[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {                        // all eight loads ahead of the first use
+            const unsigned row = first[(2 * j) / GROUP] + group_row((2 * j) % GROUP);
+            // no such row (past the list, or past the train set in its last block): a valid address, the sum is dropped
+            tv[j] = *reinterpret_cast<const uint4*>(tunit + static_cast<size_t>(min(row, last)) * tpitch);
+        }
+        asm volatile("" : "+v"(tn));                         // (the norm travels with the rows, not behind the branch below)
+        int dot = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int sum = u8_unit_dot8(qu, tv[j]);
+            dot = sub == j ? sum : dot;
+        }
+        asm volatile("" : "+v"(dot));                        // (sums and selects stay with their DPP moves, outside the branch)
+        if (mine <= last) {
+            const float d = __builtin_sqrtf(static_cast<float>(qn + static_cast<int>(tn) - 2 * dot));
+            b.insert(knn_key(d, static_cast<int>(mine)), d);
         }
     }
     if (wrong_hint) {                                        // canonical scan of the f32 rows (a wrong hint only costs time)
@@ -1329,9 +1355,7 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
             const int src = __ffsll(static_cast<long long>(needy)) - 1;      // the owner row's first lane
             needy &= needy - 1ull;
             const int oqi = __shfl(qc, src, 64);                            // the owner's query: its bytes again (one address per wave)
-            uint4 oq[U8_ROW16];
-#pragma unroll
-            for (int i = 0; i < U8_ROW16; ++i) oq[i] = Q8[static_cast<size_t>(oqi) * U8_ROW16 + i];
+            const uint4 oq = Q8[static_cast<size_t>(oqi) * U8_ROW16 + (lane & 7)];      // (the lane's unit of them)
             const int oqn = __shfl(qn, src, 64);
             const int oall = __shfl(full ? 1 : 0, src, 64);
             const unsigned mlo = __shfl(static_cast<unsigned>(spill), src, 64), mhi = __shfl(static_cast<unsigned>(spill >> 32), src, 64);
@@ -1340,13 +1364,13 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
             tb.init();
             const int rows_per_split = tiles_per_split * H_TT;
             if (oall) {
-                r8_scan_rows<KM, 1, 64>(tb, oq, oqn, T8, tnorm, t_row16, 0, nt, lane);
+                r8_scan_rows<KM>(tb, oq, oqn, T8, tnorm, t_row16, 0, nt, lane);
             } else {
                 while (mm) {
                     const int sp = __ffsll(static_cast<long long>(mm)) - 1;
                     mm &= mm - 1ull;
                     const int r0 = sp * rows_per_split;
-                    r8_scan_rows<KM, 1, 64>(tb, oq, oqn, T8, tnorm, t_row16, r0, r0 + rows_per_split < nt ? r0 + rows_per_split : nt, lane);
+                    r8_scan_rows<KM>(tb, oq, oqn, T8, tnorm, t_row16, r0, r0 + rows_per_split < nt ? r0 + rows_per_split : nt, lane);
                 }
             }
             for (int j = 0; j < KM; ++j) {                               // the KM best of the wave's keys -> the owner's first lane
