@@ -824,6 +824,75 @@ int pm_solve_pnp_ransac(pm_ctx* ctx, const float* xyz, const float* uv, int n, c
 int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_kp_xy, int n_kp,
                       const float* d_obj_xyz, int n_obj, float* d_uv, float* d_xyz);
 
+/* ---- 3-D to 3-D alignment (cv::estimateAffine3D's slot for a rigid or similarity model, PCL's
+ * SampleConsensusModelRegistration, the Sim(3) step of a loop closer: the transform between two sets of corresponding 3-D
+ * rows, such as two outputs of pm_stereo_points_dev or pm_triangulate_dev for the same tracks) — docs/SPEC.md S97-S101.
+ * Correspondence i is xyz1[3i .. 3i+2] and xyz2[3i .. 3i+2] (f32); a row with a non-finite value in either array is never
+ * an inlier and never used by the refit.  Transform: x2 = s R x1 + t.  A model T is 13 doubles: R (9, row-major, det +1),
+ * t (3), s (1, > 0); PM_ALIGN3D_RIGID fixes s = 1 exactly.  pm_ransac_params with error_kind = PM_ERR_REPROJ and thresh_px
+ * the distance threshold in the points' own unit, finite and > 0; sample h in [hyp_begin, hyp_end) draws 3
+ * correspondences (S97) and the triad solve (S98) gives one model, invalid when two sampled points coincide, the three are
+ * collinear or a value is not finite in either frame; every model is scored with |s R x1 + t - x2|^2 <= thresh_px^2 in fp32
+ * (S99).  Winner: most inliers, ties -> lowest h; the key is (inliers << 32) | (0xFFFFFFFF - h), so hyp_end <= 2^32 (and
+ * hyp_end - hyp_begin <= 2^31 - 1).  Statuses: PM_E_INVALID (model not PM_ALIGN3D_*, bad threshold, range or error_kind,
+ * null params / points / outputs, null ctx), n < 3 -> PM_E_TOO_FEW, no valid sample -> PM_E_NO_MODEL with T = 0, mask = 0
+ * (*best_key = 0).  Graph capture: as the homography calls (no per-call state; the host forms synchronise). */
+enum { PM_ALIGN3D_RIGID = 0, PM_ALIGN3D_SIMILARITY = 1 };
+/* Plain arrays of correspondences on the device with an optional device-side count (clamped to [0, cap]; NULL: cap). */
+typedef struct pm_xyz_view {
+    const float*   xyz1;    /* cap x 3 rows of the first frame */
+    const float*   xyz2;    /* cap x 3 rows of the second frame */
+    const int32_t* count;
+    int32_t cap;
+    int32_t reserved;
+} pm_xyz_view;
+/* Host in, host out.  T is required; mask (n bytes), n_inliers, best_key may be NULL. */
+int pm_ransac_align3d(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n, const pm_ransac_params* p,
+                      double T[13], uint8_t* mask, int* n_inliers, uint64_t* best_key);
+/* T, mask and inlier count of ONE sample id (0 <= hyp < 2^32; p's range is ignored): the same launches over
+ * [hyp, hyp + 1).  An invalid sample -> PM_E_NO_MODEL with T = 0, mask = 0. */
+int pm_ransac_align3d_from_hyp(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n,
+                               const pm_ransac_params* p, int64_t hyp, double T[13], uint8_t* mask, int* n_inliers);
+/* Whole run on the device over a pm_xyz_view (count read on the device): writes *d_best_key, d_T (13 doubles),
+ * d_mask[0..mask_len) (zero beyond n) and *d_n_inliers; n < 3 or no valid model leaves key 0, T = 0, mask = 0, count 0.
+ * All four output pointers are required. */
+int pm_ransac_align3d_run_dev(pm_ctx* ctx, int model, const pm_xyz_view* view, const pm_ransac_params* p,
+                              uint64_t* d_best_key, double* d_T, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers);
+/* Least-squares refit of T on the correspondences with mask[i] != 0 and six finite values (S101): Horn's closed-form
+ * absolute orientation, the unit quaternion of the largest eigenvalue of a symmetric 4 x 4 matrix found by cyclic Jacobi
+ * with a fixed sweep count; the similarity takes Umeyama's least-squares scale.  Sums in S23's fixed order; the refit is
+ * kept only if its cost (the sum of squared distances) is not higher than T_in's, so cost_out <= cost_in.  The mask is not
+ * recomputed.  Info: pm_h_refine_info with iters = 0; status 0 = refitted, 1 = kept T_in (fewer than 3 usable inliers, a
+ * rotation that is not determined: collinear or coincident inliers, no finite positive scale, or no gain; T_out = T_in
+ * bit for bit), 2 = T_in is zero (no model).  Host in, host out; T_out may alias T_in; info may be NULL.
+ * Statuses: PM_E_INVALID (bad model, null arrays, null ctx), n < 3 -> PM_E_TOO_FEW (T_out = T_in), T_in zero ->
+ * PM_E_NO_MODEL (status 2).  One launch of one workgroup. */
+int pm_align3d_refine(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n, const uint8_t* mask,
+                      const double T_in[13], double T_out[13], pm_h_refine_info* info);
+/* Device form over a pm_xyz_view (count read on the device): chains after pm_ransac_align3d_run_dev with no host round
+ * trip.  d_T_out may equal d_T_in; d_info may be NULL; data outcomes are reported in *d_info only. */
+int pm_align3d_refine_dev(pm_ctx* ctx, int model, const pm_xyz_view* view, const uint8_t* d_mask, const double* d_T_in,
+                          double* d_T_out, pm_h_refine_info* d_info);
+/* Both in one call — pm_ransac_align3d, then (refine != 0) the refit, one synchronisation.  mask / n_inliers / best_key as
+ * the RANSAC call (the RANSAC mask).  info (may be NULL): the refit's; with refine == 0 it is zero but for status (1, or 2
+ * without a model).  Statuses as pm_ransac_align3d. */
+int pm_estimate_align3d(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n, const pm_ransac_params* p,
+                        int refine, double T[13], uint8_t* mask, int* n_inliers, uint64_t* best_key,
+                        pm_h_refine_info* info);
+/* Apply a 13-double model to rows: out = (float)(s R x + t), fp64 with one rounding to fp32 (S101); a row with a
+ * non-finite input or result is three quiet NaNs, so the NaN rows of pm_stereo_points_dev / pm_triangulate_dev stay NaN.
+ * Device form: rows [0, n), n = *d_n clamped to [0, cap] (d_n NULL: cap), rows beyond are not written; d_out may be d_xyz;
+ * one launch, no per-call state.  Statuses: PM_E_INVALID (null pointer, null ctx, negative size), size 0 ->
+ * PM_E_UNSUPPORTED.  pm_transform_points3: the blocking host form. */
+int pm_transform_points3_dev(pm_ctx* ctx, const double* d_T, const float* d_xyz, const int32_t* d_n, int cap, float* d_out);
+int pm_transform_points3(pm_ctx* ctx, const double* T, const float* xyz, int n, float* out);
+/* The device chain's gather, the twin of pm_gather_pnp_dev: the compacted match list (records d_matches[0 .. n), n =
+ * *d_count clamped to [0, cap], d_count NULL: cap) between two maps into rows: d_xyz1[i] = d_tab1[queryIdx], d_xyz2[i] =
+ * d_tab2[trainIdx] (tables of n1 and n2 rows of 3 floats).  The count passes through unchanged: the view {d_xyz1, d_xyz2,
+ * d_count, cap} feeds pm_ransac_align3d_run_dev.  An index out of range gives a NaN row (never an inlier). */
+int pm_gather_align3d_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_tab1, int n1,
+                          const float* d_tab2, int n2, float* d_xyz1, float* d_xyz2);
+
 /* ---- triangulation: map points from 2 .. 8 posed views (cv::triangulatePoints, then the step a map builder runs behind
  * it: refine the point on its reprojection error and keep it only if it lies in front of every camera, has enough
  * parallax and reprojects well) — docs/SPEC.md S93-S96.  The structure-only half of bundle adjustment; pm_pnp_refine* is

@@ -65,6 +65,9 @@ EXPORTS = [
     "pm_pose_refine", "pm_pose_refine_dev", "pm_estimate_pose_refined",
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
     "pm_solve_pnp_ransac", "pm_gather_pnp_dev", "pm_triangulate_dev", "pm_triangulate",
+    "pm_ransac_align3d", "pm_ransac_align3d_from_hyp", "pm_ransac_align3d_run_dev", "pm_align3d_refine",
+    "pm_align3d_refine_dev", "pm_estimate_align3d", "pm_transform_points3_dev", "pm_transform_points3",
+    "pm_gather_align3d_dev",
     "pm_filter_cross", "pm_filter_cross_gather_dev",
     "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
     "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
@@ -253,6 +256,14 @@ def stereo_rectify(R, t):
 class PnpView(C.Structure):
     """pm_pnp_view: world points (cap x 3) and pixels (cap x 2) on the device with an optional device-side count."""
     _fields_ = [("xyz", C.c_void_p), ("uv", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_int32), ("reserved", C.c_int32)]
+
+
+PM_ALIGN3D_RIGID, PM_ALIGN3D_SIMILARITY = 0, 1
+
+
+class XyzView(C.Structure):
+    """pm_xyz_view: rows of two frames (cap x 3 each) on the device with an optional device-side count."""
+    _fields_ = [("xyz1", C.c_void_p), ("xyz2", C.c_void_p), ("count", C.c_void_p), ("cap", C.c_int32), ("reserved", C.c_int32)]
 
 
 PM_TRI_MAX_VIEWS = 8
@@ -1546,6 +1557,89 @@ class Context:
         _check(lib().pm_gather_pnp_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dkp_ptr),
                                        n_kp, C.c_void_p(dobj_ptr), n_obj, C.c_void_p(duv_ptr), C.c_void_p(dxyz_ptr)))
 
+    # -- 3-D to 3-D alignment x2 = s R x1 + t (rigid or similarity, SPEC S97-S101) -----------------------------------------
+    # xyz1, xyz2: n x 3 rows; model: PM_ALIGN3D_RIGID or PM_ALIGN3D_SIMILARITY.  T is returned as 13 float64: R (9,
+    # row-major), t (3), s.
+    def ransac_align3d(self, xyz1, xyz2, iters, thresh, seed, model=PM_ALIGN3D_RIGID, hyp_begin=0, kind=PM_ERR_REPROJ):
+        """Samples [hyp_begin, iters).  Returns (status, T(13), mask, n_inliers, best_key); raises on anything other than
+        PM_OK / PM_E_NO_MODEL / PM_E_TOO_FEW (those are data outcomes, reported as status)."""
+        xyz1, xyz2, n = _xyz_pair(xyz1, xyz2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh, kind)
+        T = np.zeros(13, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        rc = _outcome(lib().pm_ransac_align3d(self._h, model, _p(xyz1), _p(xyz2), n, C.byref(prm), _p(T), _p(mask),
+                                              C.byref(ninl), C.byref(key)))
+        return rc, T, mask[:n], ninl.value, key.value
+
+    def ransac_align3d_from_hyp(self, xyz1, xyz2, hyp, thresh, seed, model=PM_ALIGN3D_RIGID, kind=PM_ERR_REPROJ):
+        """T, mask and count of one sample id: (status, T(13), mask, n_inliers)."""
+        xyz1, xyz2, n = _xyz_pair(xyz1, xyz2)
+        prm = RansacParams(0, 0, seed, thresh, kind)
+        T = np.zeros(13, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl = C.c_int()
+        rc = _outcome(lib().pm_ransac_align3d_from_hyp(self._h, model, _p(xyz1), _p(xyz2), n, C.byref(prm), C.c_int64(hyp),
+                                                       _p(T), _p(mask), C.byref(ninl)))
+        return rc, T, mask[:n], ninl.value
+
+    def ransac_align3d_run_dev(self, view, hyp_begin, hyp_end, thresh, seed, dkey_ptr, dT_ptr, dmask_ptr, mask_len, dninl_ptr,
+                               model=PM_ALIGN3D_RIGID, kind=PM_ERR_REPROJ):
+        """Device-resident run over an XyzView (count read on the device); outputs are device pointers (T: 13 doubles)."""
+        prm = RansacParams(hyp_begin, hyp_end, seed, thresh, kind)
+        _check(lib().pm_ransac_align3d_run_dev(self._h, model, C.byref(view), C.byref(prm), C.c_void_p(dkey_ptr),
+                                               C.c_void_p(dT_ptr), C.c_void_p(dmask_ptr), mask_len, C.c_void_p(dninl_ptr)))
+
+    def align3d_refine(self, xyz1, xyz2, mask, T_in, model=PM_ALIGN3D_RIGID):
+        """Closed-form refit on the inliers (SPEC S101): (status, T(13), HRefineInfo); raises on anything other than PM_OK /
+        PM_E_NO_MODEL / PM_E_TOO_FEW."""
+        xyz1, xyz2, n = _xyz_pair(xyz1, xyz2)
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        if mask.shape[0] != n:
+            raise ValueError("xyz1, xyz2 and mask must have the same length")
+        Tin = np.ascontiguousarray(T_in, np.float64).reshape(13)
+        T = np.zeros(13, np.float64)
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_align3d_refine(self._h, model, _p(xyz1), _p(xyz2), n, _p(mask), _p(Tin), _p(T), C.byref(info)))
+        return rc, T, info
+
+    def align3d_refine_dev(self, view, dmask_ptr, dTin_ptr, dTout_ptr, dinfo_ptr=None, model=PM_ALIGN3D_RIGID):
+        """Device form over an XyzView; dinfo_ptr (32 bytes, H_REFINE_INFO_DTYPE) may be None."""
+        _check(lib().pm_align3d_refine_dev(self._h, model, C.byref(view), C.c_void_p(dmask_ptr), C.c_void_p(dTin_ptr),
+                                           C.c_void_p(dTout_ptr), C.c_void_p(dinfo_ptr)))
+
+    def estimate_align3d(self, xyz1, xyz2, iters, thresh, seed, model=PM_ALIGN3D_RIGID, refine=True, hyp_begin=0,
+                         kind=PM_ERR_REPROJ):
+        """RANSAC + (refine) refit, one synchronisation: (status, T(13), mask, n_inliers, best_key, HRefineInfo)."""
+        xyz1, xyz2, n = _xyz_pair(xyz1, xyz2)
+        prm = RansacParams(hyp_begin, iters, seed, thresh, kind)
+        T = np.zeros(13, np.float64)
+        mask = np.zeros(max(n, 1), np.uint8)
+        ninl, key = C.c_int(), C.c_uint64()
+        info = HRefineInfo()
+        rc = _outcome(lib().pm_estimate_align3d(self._h, model, _p(xyz1), _p(xyz2), n, C.byref(prm), 1 if refine else 0,
+                                                _p(T), _p(mask), C.byref(ninl), C.byref(key), C.byref(info)))
+        return rc, T, mask[:n], ninl.value, key.value, info
+
+    def transform_points3_dev(self, dT_ptr, dxyz_ptr, dn_ptr, cap, dout_ptr):
+        """Device pointers; dT: 13 doubles; dn_ptr (device int32 count) may be None = cap; dout may equal dxyz."""
+        _check(lib().pm_transform_points3_dev(self._h, C.c_void_p(dT_ptr), C.c_void_p(dxyz_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                              C.c_void_p(dout_ptr)))
+
+    def transform_points3(self, T, xyz):
+        """Host form: rows (n, 3) through the 13-double model T -> (n, 3) f32; NaN rows stay NaN."""
+        T = np.ascontiguousarray(T, np.float64).reshape(13)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        out = np.zeros((max(n, 1), 3), np.float32)
+        _check(lib().pm_transform_points3(self._h, _p(T), _p(xyz), n, _p(out)))
+        return out[:n]
+
+    def gather_align3d_dev(self, dmatches_ptr, dcount_ptr, cap, dtab1_ptr, n1, dtab2_ptr, n2, dxyz1_ptr, dxyz2_ptr):
+        """Compacted matches -> two row arrays on the device (xyz1 = table 1 at queryIdx, xyz2 = table 2 at trainIdx)."""
+        _check(lib().pm_gather_align3d_dev(self._h, C.c_void_p(dmatches_ptr), C.c_void_p(dcount_ptr), cap, C.c_void_p(dtab1_ptr),
+                                           n1, C.c_void_p(dtab2_ptr), n2, C.c_void_p(dxyz1_ptr), C.c_void_p(dxyz2_ptr)))
+
     # -- triangulation (cv::triangulatePoints + refinement + the map builder's gates, SPEC S93-S96) ----------------------
     def triangulate_dev(self, views, K, params, dxyz_ptr, dstatus_ptr, dpoints4_ptr=None, derr2_ptr=None, dngood_ptr=None):
         """Device form over a TriViews: d_xyz cap x 3 f32 (NaN unless PM_TRI_OK; read under PM_TRI_USE_INITIAL), d_status
@@ -1614,6 +1708,15 @@ class Pyramid:
         out = np.zeros((h.value, w.value), np.uint8)
         _check(lib().pm_pyramid_level_get(self._ctx._h, self._h, l, _p(out), out.size, C.byref(w), C.byref(h)))
         return out
+
+
+def _xyz_pair(xyz1, xyz2):
+    """3D-3D correspondences as contiguous float32 (n, 3) arrays, and n."""
+    xyz1 = np.ascontiguousarray(xyz1, np.float32).reshape(-1, 3)
+    xyz2 = np.ascontiguousarray(xyz2, np.float32).reshape(-1, 3)
+    if xyz1.shape[0] != xyz2.shape[0]:
+        raise ValueError("xyz1 and xyz2 must have the same length")
+    return xyz1, xyz2, xyz1.shape[0]
 
 
 def _pnp_pair(xyz, uv):

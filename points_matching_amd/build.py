@@ -21,7 +21,8 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "essential_solve.hip", "ransac_e_fused.hip", "recover_pose.hip", "pnp_solve.hip", "ransac_p_fused.hip",
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
-           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip", "triangulate.hip"]
+           "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip", "triangulate.hip",
+           "align3d_solve.hip", "ransac_align3d_fused.hip", "align3d_refine.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -64,7 +65,12 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          "stereo_sgm.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # triangulation (S93-S96): a lane owns a point, its 2V x 4 fp64 system and V pixels in registers, one instantiation per
          # view count; none may use scratch or spill
-         "triangulate.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "triangulate.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # 3-D alignment (S97-S101): the lane-serial fp64 triad solve, the scorer with its 6-plane LDS tile and the one-workgroup
+         # refit with its 4 x 4 Jacobi in registers; none may use scratch or spill
+         "align3d_solve.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "ransac_align3d_fused.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         "align3d_refine.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

@@ -1,9 +1,10 @@
 // estimators.cpp — the C-ABI entry points of the robust model families of include/pm.h that share one call shape:
 // the homography (RANSAC-H, ransac_h_fused.hip, refined by homography_refine.hip), the affine / similarity model
 // (RANSAC-A, ransac_a_fused.hip, refitted by affine_refine.hip), the calibrated relative pose (RANSAC-E,
-// essential_solve.hip + ransac_e_fused.hip, followed by recover_pose.hip and, on request, pose_refine.hip) and the
-// absolute pose (RANSAC-PnP, pnp_solve.hip + ransac_p_fused.hip, refined by pnp_refine.hip); also the refinement of the
-// fundamental matrix (fundamental_refine.hip; its RANSAC is the one-launch kernel of ransac_fused.hip, whose other entry
+// essential_solve.hip + ransac_e_fused.hip, followed by recover_pose.hip and, on request, pose_refine.hip), the
+// absolute pose (RANSAC-PnP, pnp_solve.hip + ransac_p_fused.hip, refined by pnp_refine.hip) and the 3-D to 3-D
+// alignment (rigid / similarity transforms, align3d_solve.hip + ransac_align3d_fused.hip, refitted by
+// align3d_refine.hip); also the refinement of the fundamental matrix (fundamental_refine.hip; its RANSAC is the one-launch kernel of ransac_fused.hip, whose other entry
 // points live in ransac.hip) and of a relative pose alone (pose_refine.hip).  Those files hold the kernels and one enqueue
 // each.
 // Here: one description per family (Family), every argument check once, and one driver per call shape — run_host for
@@ -13,28 +14,29 @@
 #include <cmath>
 
 #include "affine_core.hpp"
+#include "align3d_core.hpp"
 #include "ransac_internal.hpp"
 
 namespace pm_ransac {
 namespace {
 
-enum Id { H, A, E, P, F, R };       // R: a relative pose (R, t) to refine, no RANSAC of its own
+enum Id { H, A, E, P, F, R, X };    // R: a relative pose (R, t) to refine, no RANSAC of its own; X: 3-D to 3-D alignment
 
 // One model family.  A sample yields `ids` candidate models (model ids ids * h + j); the minimal solvers of E and P write
-// them `stride` doubles apart with a non-zero flag at offset `flag`.  The second step is LM with max_iters (H, P), the
-// closed-form refit (A) or pose recovery with dist (E), which a third step may follow: LM on the recovered pose.
+// them `stride` doubles apart with a non-zero flag at offset `flag`, and so does the one of X for its one model.  The
+// second step is LM with max_iters (H, P), the closed-form refit (A, X) or pose recovery with dist (E), which a third step may follow: LM on the recovered pose.
 struct Family {
     Id id;
     const char* name;           // in messages
-    int words;                  // doubles of a model: H 9, A 6, E 9, P 12 (R, then t)
+    int words;                  // doubles of a model: H 9, A 6, E 9, P 12 (R, then t), X 13 (R, t, s)
     int min_pts;
-    int dim1;                   // floats per point of the first array (P: world points)
+    int dim1, dim2;             // floats per point of the first and the second array (P: world points; X: 3 and 3)
     int ids, stride, flag;
     int error_kind;
     const char* unit;           // what RANSAC draws, in messages
     const char* null_model;     // messages of the null checks
     const char* null_cands;
-    int model;                  // A: PM_AFFINE_FULL | PM_AFFINE_PARTIAL
+    int model;                  // A: PM_AFFINE_FULL | PM_AFFINE_PARTIAL; X: PM_ALIGN3D_RIGID | PM_ALIGN3D_SIMILARITY
     int max_iters;              // H, P, F, R; E: of the third step
     double dist;                // E
     bool third;                 // E: refine the recovered pose
@@ -45,30 +47,35 @@ struct Family {
 
 Family homography(int max_iters)
 {
-    return Family{H, "H", 9, 4, 2, 1, 0, 0, PM_ERR_REPROJ, "hypotheses", "null H", nullptr, 0, max_iters, 0.0};
+    return Family{H, "H", 9, 4, 2, 2, 1, 0, 0, PM_ERR_REPROJ, "hypotheses", "null H", nullptr, 0, max_iters, 0.0};
 }
 Family affine(int model)
 {
     using namespace pm_affine;
     const int k = model == PM_AFFINE_FULL ? Traits<FULL>::MIN_PTS : Traits<PARTIAL>::MIN_PTS;
-    return Family{A, "A", 6, k, 2, 1, 0, 0, PM_ERR_REPROJ, "hypotheses", "null A", nullptr, model, 0, 0.0};
+    return Family{A, "A", 6, k, 2, 2, 1, 0, 0, PM_ERR_REPROJ, "hypotheses", "null A", nullptr, model, 0, 0.0};
 }
 Family essential(double dist, bool third = false, int max_iters = 0)
 {
-    return Family{E, "E", 9, 5, 2, 10, 10, 9, PM_ERR_SAMPSON, "samples", "null E", "null E or counts", 0, max_iters, dist, third};
+    return Family{E, "E", 9, 5, 2, 2, 10, 10, 9, PM_ERR_SAMPSON, "samples", "null E", "null E or counts", 0, max_iters, dist, third};
 }
 Family fundamental(int max_iters)
 {
-    return Family{F, "F", 9, 8, 2, 1, 0, 0, PM_ERR_SAMPSON, "hypotheses", "null F", nullptr, 0, max_iters, 0.0};
+    return Family{F, "F", 9, 8, 2, 2, 1, 0, 0, PM_ERR_SAMPSON, "hypotheses", "null F", nullptr, 0, max_iters, 0.0};
 }
 Family relpose(int max_iters)
 {
-    return Family{R, "pose", 12, 5, 2, 1, 0, 0, PM_ERR_SAMPSON, "samples", "null R or t", nullptr, 0, max_iters, 0.0};
+    return Family{R, "pose", 12, 5, 2, 2, 1, 0, 0, PM_ERR_SAMPSON, "samples", "null R or t", nullptr, 0, max_iters, 0.0};
 }
 Family pnp(int max_iters)
 {
-    return Family{P, "pose", 12, 4, 3, 4, 20, 12, PM_ERR_REPROJ, "samples", "null R or t", "null Rt or counts", 0,
+    return Family{P, "pose", 12, 4, 3, 2, 4, 20, 12, PM_ERR_REPROJ, "samples", "null R or t", "null Rt or counts", 0,
                   max_iters, 0.0};
+}
+Family align3d(int model)
+{
+    using namespace pm_align3d;
+    return Family{X, "T", WORDS, 3, 3, 3, 1, SLOT_DOUBLES, FLAG, PM_ERR_REPROJ, "samples", "null T", nullptr, model, 0, 0.0};
 }
 
 // What a call runs: RANSAC, the second step (on RANSAC's winner, or on the caller's model), or both in that order;
@@ -98,8 +105,8 @@ int check_K(const pm_camera* K)
     return PM_OK;
 }
 
-// The family's own checks, in the order every entry point runs them: model (A); params: null, range, error_kind,
-// thresh_px (P); K, and for E the threshold normalised by it (S31, fp32); a null input model (no RANSAC); the second
+// The family's own checks, in the order every entry point runs them: model (A, X); params: null, range, error_kind,
+// thresh_px (P, X); K, and for E the threshold normalised by it (S31, fp32); a null input model (no RANSAC); the second
 // step's max_iters (H, P) or dist (E).  *thr: the threshold the scorer takes.
 int check_args(const Family& f, int steps, const pm_ransac_params* p, const pm_camera* K, const double* model_in,
                float* thr)
@@ -108,6 +115,9 @@ int check_args(const Family& f, int steps, const pm_ransac_params* p, const pm_c
     if (f.id == A)
         PM_REQUIRE(f.model == PM_AFFINE_FULL || f.model == PM_AFFINE_PARTIAL, PM_E_INVALID,
                    "model must be PM_AFFINE_FULL or PM_AFFINE_PARTIAL");
+    if (f.id == X)
+        PM_REQUIRE(f.model == PM_ALIGN3D_RIGID || f.model == PM_ALIGN3D_SIMILARITY, PM_E_INVALID,
+                   "model must be PM_ALIGN3D_RIGID or PM_ALIGN3D_SIMILARITY");
     if (ransac) {
         PM_REQUIRE(p != nullptr, PM_E_INVALID, "params is null");
         const int rc = check_range(p, f.ids);
@@ -118,7 +128,7 @@ int check_args(const Family& f, int steps, const pm_ransac_params* p, const pm_c
         else
             PM_REQUIRE(p->error_kind == f.error_kind, PM_E_INVALID,
                        f.error_kind == PM_ERR_SAMPSON ? "error_kind must be PM_ERR_SAMPSON" : "error_kind must be PM_ERR_REPROJ");
-        if (f.id == P)
+        if (f.id == P || f.id == X)
             PM_REQUIRE(p->thresh_px > 0.0f && std::isfinite(p->thresh_px), PM_E_INVALID, "thresh_px must be finite and > 0");
     }
     *thr = ransac ? p->thresh_px : 1.0f;
@@ -148,17 +158,17 @@ pm_ransac_params model_ids(const Family& f, const pm_ransac_params* p, float thr
 }
 
 // Arena bytes of a RANSAC run over a view of cap_total points: what enqueue_solve carves (E: the normalised copy and its
-// count; E, P: the candidates), the scorer's workgroup slots, 1 KiB of alignment slack.
+// count; E, P, X: the candidates), the scorer's workgroup slots, 1 KiB of alignment slack.
 size_t scratch_bytes(const pm_ctx* ctx, const Family& f, long long cap_total, const pm_ransac_params* p, float thr)
 {
     const pm_ransac_params q = model_ids(f, p, thr);
     const size_t nh = static_cast<size_t>(p->hyp_end - p->hyp_begin);
-    size_t solve = f.ids > 1 ? pm::align_up(sizeof(double) * f.ids * f.stride * nh, 256) : 0;
+    size_t solve = f.stride > 0 ? pm::align_up(sizeof(double) * f.ids * f.stride * nh, 256) : 0;
     if (f.id == E) solve += 2 * pm::align_up(sizeof(float) * 2 * static_cast<size_t>(cap_total), 256) + 256;
     return solve + fused_scratch_bytes(ctx, &q) + 1024;
 }
 
-// The minimal solver of samples [hyp_begin, hyp_end) of p, where it is a launch of its own (E, P; H and A solve inside
+// The minimal solver of samples [hyp_begin, hyp_end) of p, where it is a launch of its own (E, P, X; H and A solve inside
 // their scorer): *d_cand receives the candidates, ids * stride doubles per sample, and *vs the view the scorer reads
 // (E: the copy normalised by K).  Carves from the arena.
 int enqueue_solve(pm_ctx* ctx, const Family& f, const pm_points_view& v, const pm_camera* K, const pm_ransac_params* p,
@@ -186,6 +196,10 @@ int enqueue_solve(pm_ctx* ctx, const Family& f, const pm_points_view& v, const p
         *d_cand = static_cast<double*>(pm::arena_take(ctx, cand_bytes));
         PM_REQUIRE(*d_cand, PM_E_NOMEM, "scratch arena too small");
         return pnp_solve_enqueue(ctx, v, *K, p, *d_cand);
+    case X:
+        *d_cand = static_cast<double*>(pm::arena_take(ctx, cand_bytes));
+        PM_REQUIRE(*d_cand, PM_E_NOMEM, "scratch arena too small");
+        return align3d_solve_enqueue(ctx, f.model, v, p, *d_cand);
     }
     return PM_E_INVALID;
 }
@@ -200,6 +214,7 @@ int enqueue_score(pm_ctx* ctx, const Family& f, const pm_points_view& vs, const 
     case E: return ransac_e_enqueue(ctx, vs, q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
     case P: return ransac_p_enqueue(ctx, vs, q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
     case F: return fused_launch(ctx, vs, q, 0, nullptr, d_key, d_model, d_mask, mask_len, d_ninl, nullptr);
+    case X: return ransac_align3d_enqueue(ctx, vs, q, d_cand, d_key, d_model, d_mask, mask_len, d_ninl);
     case R: break;
     }
     return PM_E_INVALID;
@@ -228,6 +243,7 @@ int enqueue_refine(pm_ctx* ctx, const Family& f, const pm_points_view& v, const 
     case P: return pnp_refine_enqueue(ctx, v, *K, d_mask, d_in, f.max_iters, d_out, d_info);
     case F: return fundamental_refine_enqueue(ctx, v, d_mask, d_in, f.max_iters, d_out, d_info);
     case R: return pose_refine_enqueue(ctx, v, *K, d_mask, d_in, f.max_iters, d_out, d_E, d_info);
+    case X: return align3d_refine_enqueue(ctx, f.model, v, d_mask, d_in, d_out, d_info);
     case E: break;
     }
     return PM_E_INVALID;
@@ -240,7 +256,7 @@ int enqueue_refine(pm_ctx* ctx, const Family& f, const pm_points_view& v, const 
 struct Results {
     unsigned long long* key;
     int32_t *count, *n_good;
-    pm_h_refine_info* info;     // H, A, P
+    pm_h_refine_info* info;     // H, A, P, X
     double* pose;               // E: R (9), t (3)
     double* model;
     unsigned long long* keys;
@@ -249,7 +265,7 @@ struct Results {
     pm_h_refine_info* info3;
 };
 
-// H 120, A 96, E 1064 (1168 with a third step), P 816, F 120, R 216
+// H 120, A 96, E 1064 (1168 with a third step), P 816, F 120, R 216, X 152
 size_t results_bytes(const Family& f)
 {
     const size_t second = f.pose() ? sizeof(double) * 12 : sizeof(pm_h_refine_info);
@@ -300,7 +316,7 @@ struct HostOut {
     int* n_inliers;
     uint64_t* best_key;
     pm_h_refine_info* info;
-    double* tail;               // the rest of the model (P: t)
+    double* tail;               // the rest of the model (P: t; X: t, s)
     double *R, *t;              // pose recovery
     int* n_good;
     float* points4;             // 4 n
@@ -336,7 +352,7 @@ void reset_outputs(const Family& f, bool ransac, int n, const double* in, const 
     if (out.E_ref) memset(out.E_ref, 0, sizeof(double) * 9);
 }
 
-// Driver of every host-pointer form: n correspondences a1 (dim1 floats each), a2 (2 floats each).  RANSAC over p's
+// Driver of every host-pointer form: n correspondences a1 (dim1 floats each), a2 (dim2 floats each).  RANSAC over p's
 // samples (or CANDIDATES), then (SECOND) the second step on its winner and mask; SECOND alone: on the caller's model
 // (model_in, tail_in) and mask_in (pose recovery: mask_in may be null).  The outputs are reset before the first check,
 // except that a refit or refinement alone first needs its model pointers (out.model may alias model_in).
@@ -347,7 +363,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     const bool ransac = steps & (RANSAC | CANDIDATES), second = steps & SECOND, cands = steps & CANDIDATES;
     const bool refit_alone = !ransac && !f.pose();
     const size_t model_bytes = sizeof(double) * static_cast<size_t>(f.words), mask_bytes = n > 0 ? n : 0;
-    double in[12] = {};
+    double in[13] = {};
     if (refit_alone)
         PM_REQUIRE(model_in && out.model && (f.words <= 9 || (tail_in && out.tail)), PM_E_INVALID, f.null_model);
     if (!ransac && model_in) {
@@ -370,7 +386,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
 
     // Arena: the two point arrays, the mask, points4, the results block, then what RANSAC carves (one slot set more per
     // candidate scored alone) and 1 KiB of slack on top of scratch_bytes()'s own: the most any family needs.
-    const size_t b1 = sizeof(float) * f.dim1 * static_cast<size_t>(n), b2 = sizeof(float) * 2 * static_cast<size_t>(n);
+    const size_t b1 = sizeof(float) * f.dim1 * static_cast<size_t>(n), b2 = sizeof(float) * f.dim2 * static_cast<size_t>(n);
     const size_t pts = out.points4 ? sizeof(float) * 4 * static_cast<size_t>(n) : 0;
     const size_t res_bytes = results_bytes(f);
     rc = pm::arena_reserve(ctx, pm::align_up(b1, 256) + pm::align_up(b2, 256) + pm::align_up(mask_bytes, 256) +
@@ -394,8 +410,8 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     PM_HIP_CHECK(hipMemcpyAsync(d2, a2, b2, hipMemcpyHostToDevice, ctx->stream));
     if (!ransac) {
         memcpy(hres.model, in, model_bytes);
-        // H and A send the mask before the model, E and P after it
-        const bool mask_first = f.id == H || f.id == A || f.id == F;
+        // H, A and X send the mask before the model, E and P after it
+        const bool mask_first = f.id == H || f.id == A || f.id == F || f.id == X;
         if (mask_first) PM_HIP_CHECK(hipMemcpyAsync(dmask, mask_in, mask_bytes, hipMemcpyHostToDevice, ctx->stream));
         PM_HIP_CHECK(hipMemcpyAsync(dres.model, hres.model, model_bytes, hipMemcpyHostToDevice, ctx->stream));
         if (!mask_first && mask_in)
@@ -471,7 +487,7 @@ int run_host(pm_ctx* ctx, const Family& f, int steps, const float* a1, const flo
     return PM_OK;
 }
 
-// The model, mask and count of hypothesis id `hyp` alone (H, A): RANSAC over [hyp, hyp + 1)
+// The model, mask and count of hypothesis id `hyp` alone (H, A, X): RANSAC over [hyp, hyp + 1)
 int run_host_hyp(pm_ctx* ctx, const Family& f, const float* xy1, const float* xy2, int n, const pm_ransac_params* p,
                  int64_t hyp, double* model, uint8_t* mask, int* n_inliers)
 {
@@ -483,7 +499,7 @@ int run_host_hyp(pm_ctx* ctx, const Family& f, const float* xy1, const float* xy
     q.hyp_begin = hyp;
     q.hyp_end = hyp + 1;
     return run_host(ctx, f, RANSAC, xy1, xy2, n, nullptr, &q, nullptr, nullptr, nullptr,
-                    HostOut{model, mask, n_inliers, nullptr, nullptr});
+                    HostOut{model, mask, n_inliers, nullptr, nullptr, model && f.words > 9 ? model + 9 : nullptr});
 }
 
 // Every candidate of sample id `hyp` with its count (E, P): CANDIDATES over [hyp, hyp + 1).  E refuses a bad hyp itself,
@@ -508,10 +524,11 @@ int run_host_candidates(pm_ctx* ctx, const Family& f, const float* a1, const flo
     return run_host(ctx, f, CANDIDATES, a1, a2, n, K, p ? &q : nullptr, nullptr, nullptr, nullptr, o);
 }
 
-// The view of a device form: a pm_points_view (H, A, E) or a pm_pnp_view (P)
+// The view of a device form: a pm_points_view (H, A, E), a pm_pnp_view (P) or a pm_xyz_view (X)
 struct DevView {
     const pm_points_view* xy;
     const pm_pnp_view* pnp;
+    const pm_xyz_view* xyz;
 };
 
 // The device forms' checks after the family's: the view (*v: as the launches take it), ctx; then the device and
@@ -522,6 +539,10 @@ int dev_prologue(pm_ctx* ctx, const Family& f, const DevView& view, const pm_ran
         PM_REQUIRE(view.pnp != nullptr && view.pnp->xyz && view.pnp->uv && view.pnp->cap >= 1, PM_E_INVALID,
                    "need a view with points and cap >= 1");
         *v = pm_points_view{view.pnp->xyz, view.pnp->uv, view.pnp->count, 1, view.pnp->cap, 0, 1, 0};
+    } else if (f.id == X) {
+        PM_REQUIRE(view.xyz != nullptr && view.xyz->xyz1 && view.xyz->xyz2 && view.xyz->cap >= 1, PM_E_INVALID,
+                   "need a view with points and cap >= 1");
+        *v = pm_points_view{view.xyz->xyz1, view.xyz->xyz2, view.xyz->count, 1, view.xyz->cap, 0, 1, 0};
     } else {
         const int rc = check_view(view.xy);
         if (rc != PM_OK) return rc;
@@ -595,7 +616,7 @@ extern "C" int pm_ransac_homography_run_dev(pm_ctx* ctx, const pm_points_view* v
                                             uint64_t* d_best_key, double* d_H, uint8_t* d_mask, int mask_len,
                                             int32_t* d_n_inliers)
 {
-    return run_dev(ctx, homography(0), DevView{view, nullptr}, nullptr, p, d_best_key, d_H, d_mask, mask_len, d_n_inliers);
+    return run_dev(ctx, homography(0), DevView{view, nullptr, nullptr}, nullptr, p, d_best_key, d_H, d_mask, mask_len, d_n_inliers);
 }
 
 extern "C" int pm_homography_refine(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const uint8_t* mask,
@@ -608,7 +629,7 @@ extern "C" int pm_homography_refine(pm_ctx* ctx, const float* xy1, const float* 
 extern "C" int pm_homography_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask,
                                         const double* d_H_in, int max_iters, double* d_H_out, pm_h_refine_info* d_info)
 {
-    return refine_dev(ctx, homography(max_iters), DevView{view, nullptr}, nullptr, d_mask, d_H_in, d_H_out, d_info);
+    return refine_dev(ctx, homography(max_iters), DevView{view, nullptr, nullptr}, nullptr, d_mask, d_H_in, d_H_out, d_info);
 }
 
 extern "C" int pm_ransac_homography_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
@@ -639,7 +660,7 @@ extern "C" int pm_ransac_affine_run_dev(pm_ctx* ctx, int model, const pm_points_
                                         uint64_t* d_best_key, double* d_A, uint8_t* d_mask, int mask_len,
                                         int32_t* d_n_inliers)
 {
-    return run_dev(ctx, affine(model), DevView{view, nullptr}, nullptr, p, d_best_key, d_A, d_mask, mask_len, d_n_inliers);
+    return run_dev(ctx, affine(model), DevView{view, nullptr, nullptr}, nullptr, p, d_best_key, d_A, d_mask, mask_len, d_n_inliers);
 }
 
 extern "C" int pm_affine_refine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n, const uint8_t* mask,
@@ -652,7 +673,7 @@ extern "C" int pm_affine_refine(pm_ctx* ctx, int model, const float* xy1, const 
 extern "C" int pm_affine_refine_dev(pm_ctx* ctx, int model, const pm_points_view* view, const uint8_t* d_mask,
                                     const double* d_A_in, double* d_A_out, pm_h_refine_info* d_info)
 {
-    return refine_dev(ctx, affine(model), DevView{view, nullptr}, nullptr, d_mask, d_A_in, d_A_out, d_info);
+    return refine_dev(ctx, affine(model), DevView{view, nullptr, nullptr}, nullptr, d_mask, d_A_in, d_A_out, d_info);
 }
 
 extern "C" int pm_estimate_affine(pm_ctx* ctx, int model, const float* xy1, const float* xy2, int n,
@@ -682,7 +703,7 @@ extern "C" int pm_ransac_essential_run_dev(pm_ctx* ctx, const pm_points_view* vi
                                            const pm_ransac_params* p, uint64_t* d_best_key, double* d_E, uint8_t* d_mask,
                                            int mask_len, int32_t* d_n_inliers)
 {
-    return run_dev(ctx, essential(0.0), DevView{view, nullptr}, K, p, d_best_key, d_E, d_mask, mask_len, d_n_inliers);
+    return run_dev(ctx, essential(0.0), DevView{view, nullptr, nullptr}, K, p, d_best_key, d_E, d_mask, mask_len, d_n_inliers);
 }
 
 extern "C" int pm_recover_pose(pm_ctx* ctx, const float* xy1, const float* xy2, int n, const pm_camera* K, const double E[9],
@@ -698,7 +719,7 @@ extern "C" int pm_recover_pose_dev(pm_ctx* ctx, const pm_points_view* view, cons
                                    int32_t* d_n_good, float* d_points4)
 {
     pm_points_view v{};
-    const int rc = second_dev(ctx, essential(dist), DevView{view, nullptr}, K, d_E && d_R && d_t && d_mask_out && d_n_good,
+    const int rc = second_dev(ctx, essential(dist), DevView{view, nullptr, nullptr}, K, d_E && d_R && d_t && d_mask_out && d_n_good,
                               d_E, &v);
     if (rc != PM_OK) return rc;
     return recover_pose_enqueue(ctx, v, *K, d_E, d_mask_in, dist, d_R, d_t, d_mask_out, v.parts * v.cap, d_n_good,
@@ -737,7 +758,7 @@ extern "C" int pm_pose_refine_dev(pm_ctx* ctx, const pm_points_view* view, const
 {
     const Family f = relpose(max_iters);
     pm_points_view v{};
-    const int rc = second_dev(ctx, f, DevView{view, nullptr}, K, d_mask && d_Rt_in && d_Rt_out, d_Rt_in, &v);
+    const int rc = second_dev(ctx, f, DevView{view, nullptr, nullptr}, K, d_mask && d_Rt_in && d_Rt_out, d_Rt_in, &v);
     if (rc != PM_OK) return rc;
     return enqueue_refine(ctx, f, v, K, d_mask, d_Rt_in, d_Rt_out, d_info, d_E_out);
 }
@@ -753,7 +774,7 @@ extern "C" int pm_fundamental_refine(pm_ctx* ctx, const float* xy1, const float*
 extern "C" int pm_fundamental_refine_dev(pm_ctx* ctx, const pm_points_view* view, const uint8_t* d_mask,
                                          const double* d_F_in, int max_iters, double* d_F_out, pm_h_refine_info* d_info)
 {
-    return refine_dev(ctx, fundamental(max_iters), DevView{view, nullptr}, nullptr, d_mask, d_F_in, d_F_out, d_info);
+    return refine_dev(ctx, fundamental(max_iters), DevView{view, nullptr, nullptr}, nullptr, d_mask, d_F_in, d_F_out, d_info);
 }
 
 extern "C" int pm_ransac_fundamental_refined(pm_ctx* ctx, const float* xy1, const float* xy2, int n,
@@ -782,7 +803,7 @@ extern "C" int pm_ransac_pnp_from_hyp(pm_ctx* ctx, const float* xyz, const float
 extern "C" int pm_ransac_pnp_run_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const pm_ransac_params* p,
                                      uint64_t* d_best_key, double* d_Rt, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers)
 {
-    return run_dev(ctx, pnp(0), DevView{nullptr, view}, K, p, d_best_key, d_Rt, d_mask, mask_len, d_n_inliers);
+    return run_dev(ctx, pnp(0), DevView{nullptr, view, nullptr}, K, p, d_best_key, d_Rt, d_mask, mask_len, d_n_inliers);
 }
 
 extern "C" int pm_pnp_refine(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K, const uint8_t* mask,
@@ -796,7 +817,7 @@ extern "C" int pm_pnp_refine(pm_ctx* ctx, const float* xyz, const float* uv, int
 extern "C" int pm_pnp_refine_dev(pm_ctx* ctx, const pm_pnp_view* view, const pm_camera* K, const uint8_t* d_mask,
                                  const double* d_Rt_in, int max_iters, double* d_Rt_out, pm_h_refine_info* d_info)
 {
-    return refine_dev(ctx, pnp(max_iters), DevView{nullptr, view}, K, d_mask, d_Rt_in, d_Rt_out, d_info);
+    return refine_dev(ctx, pnp(max_iters), DevView{nullptr, view, nullptr}, K, d_mask, d_Rt_in, d_Rt_out, d_info);
 }
 
 extern "C" int pm_solve_pnp_ransac(pm_ctx* ctx, const float* xyz, const float* uv, int n, const pm_camera* K,
@@ -815,4 +836,78 @@ extern "C" int pm_gather_pnp_dev(pm_ctx* ctx, const pm_match* d_matches, const i
     PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     return gather_pnp_enqueue(ctx, d_matches, d_count, cap, d_kp_xy, n_kp, d_obj_xyz, n_obj, d_uv, d_xyz);
+}
+
+// ---- 3-D to 3-D alignment
+namespace {
+double* tail13(double* T) { return T ? T + 9 : nullptr; }
+const double* tail13(const double* T) { return T ? T + 9 : nullptr; }
+}  // namespace
+
+extern "C" int pm_ransac_align3d(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n, const pm_ransac_params* p,
+                                 double T[13], uint8_t* mask, int* n_inliers, uint64_t* best_key)
+{
+    const Family f = align3d(model);
+    if (!T) {
+        const double zero[13] = {};
+        reset_outputs(f, true, n, zero, HostOut{nullptr, mask, n_inliers, best_key, nullptr});
+        PM_REQUIRE(T != nullptr, PM_E_INVALID, "null T");
+    }
+    return run_host(ctx, f, RANSAC, xyz1, xyz2, n, nullptr, p, nullptr, nullptr, nullptr,
+                    HostOut{T, mask, n_inliers, best_key, nullptr, tail13(T)});
+}
+
+extern "C" int pm_ransac_align3d_from_hyp(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n,
+                                          const pm_ransac_params* p, int64_t hyp, double T[13], uint8_t* mask, int* n_inliers)
+{
+    if (!T) {
+        if (n_inliers) *n_inliers = 0;
+        if (mask && n > 0) memset(mask, 0, static_cast<size_t>(n));
+        PM_REQUIRE(T != nullptr, PM_E_INVALID, "null T");
+    }
+    return run_host_hyp(ctx, align3d(model), xyz1, xyz2, n, p, hyp, T, mask, n_inliers);
+}
+
+extern "C" int pm_ransac_align3d_run_dev(pm_ctx* ctx, int model, const pm_xyz_view* view, const pm_ransac_params* p,
+                                         uint64_t* d_best_key, double* d_T, uint8_t* d_mask, int mask_len, int32_t* d_n_inliers)
+{
+    return run_dev(ctx, align3d(model), DevView{nullptr, nullptr, view}, nullptr, p, d_best_key, d_T, d_mask, mask_len,
+                   d_n_inliers);
+}
+
+extern "C" int pm_align3d_refine(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n, const uint8_t* mask,
+                                 const double T_in[13], double T_out[13], pm_h_refine_info* info)
+{
+    return run_host(ctx, align3d(model), SECOND, xyz1, xyz2, n, nullptr, nullptr, mask, T_in, tail13(T_in),
+                    HostOut{T_out, nullptr, nullptr, nullptr, info, tail13(T_out)});
+}
+
+extern "C" int pm_align3d_refine_dev(pm_ctx* ctx, int model, const pm_xyz_view* view, const uint8_t* d_mask,
+                                     const double* d_T_in, double* d_T_out, pm_h_refine_info* d_info)
+{
+    return refine_dev(ctx, align3d(model), DevView{nullptr, nullptr, view}, nullptr, d_mask, d_T_in, d_T_out, d_info);
+}
+
+extern "C" int pm_estimate_align3d(pm_ctx* ctx, int model, const float* xyz1, const float* xyz2, int n,
+                                   const pm_ransac_params* p, int refine, double T[13], uint8_t* mask, int* n_inliers,
+                                   uint64_t* best_key, pm_h_refine_info* info)
+{
+    const Family f = align3d(model);
+    if (!T) {
+        const double zero[13] = {};
+        reset_outputs(f, true, n, zero, HostOut{nullptr, mask, n_inliers, best_key, info});
+        PM_REQUIRE(T != nullptr, PM_E_INVALID, "null T");
+    }
+    return run_host(ctx, f, refine ? RANSAC | SECOND : RANSAC, xyz1, xyz2, n, nullptr, p, nullptr, nullptr, nullptr,
+                    HostOut{T, mask, n_inliers, best_key, info, tail13(T)});
+}
+
+extern "C" int pm_gather_align3d_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t* d_count, int cap, const float* d_tab1,
+                                     int n1, const float* d_tab2, int n2, float* d_xyz1, float* d_xyz2)
+{
+    PM_REQUIRE(d_matches && d_tab1 && d_tab2 && d_xyz1 && d_xyz2, PM_E_INVALID, "null argument");
+    PM_REQUIRE(cap >= 1 && n1 >= 0 && n2 >= 0, PM_E_INVALID, "need cap >= 1, n1 >= 0, n2 >= 0");
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    PM_HIP_CHECK(hipSetDevice(ctx->device));
+    return gather_align3d_enqueue(ctx, d_matches, d_count, cap, d_tab1, n1, d_tab2, n2, d_xyz1, d_xyz2);
 }

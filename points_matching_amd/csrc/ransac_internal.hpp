@@ -68,4 +68,17 @@ int pnp_refine_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_camera& K,
 int gather_pnp_enqueue(pm_ctx* ctx, const pm_match* d_m, const int32_t* d_count, int cap, const float* d_kp_xy, int n_kp,
                        const float* d_obj, int n_obj, float* d_uv, float* d_xyz);
 
+// 3-D to 3-D alignment (S97-S101); model is PM_ALIGN3D_RIGID or PM_ALIGN3D_SIMILARITY.  align3d_solve_enqueue solves
+// samples [hyp_begin, hyp_end) of p into d_cand (20 doubles per sample) from the one-part view v (xy1, xy2: the rows of
+// the two frames, 3 floats each); ransac_align3d_enqueue scores model ids [q->hyp_begin, q->hyp_end) (one per sample,
+// d_cand at the first) over the same view (carves its slots like ransac_h_enqueue); align3d_refine_enqueue: S101 on the
+// same view, one workgroup; gather_align3d_enqueue: the device chain's match -> two row arrays.
+int align3d_solve_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const pm_ransac_params* p, double* d_cand);
+int ransac_align3d_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* q, const double* d_cand,
+                           unsigned long long* d_key, double* d_T, uint8_t* d_mask, int mask_len, int* d_ninl);
+int align3d_refine_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const uint8_t* d_mask, const double* d_T_in,
+                           double* d_T_out, pm_h_refine_info* d_info);
+int gather_align3d_enqueue(pm_ctx* ctx, const pm_match* d_m, const int32_t* d_count, int cap, const float* d_tab1, int n1,
+                           const float* d_tab2, int n2, float* d_xyz1, float* d_xyz2);
+
 }  // namespace pm_ransac

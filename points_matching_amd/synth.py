@@ -594,3 +594,40 @@ def pnp_scene_wide(n, seed=0, width=4000, height=3000, focal=3000.0, aspect=1.0,
         mirrored = (-Xc[bad[:n_beh]] - t) @ R                   # R X + t = -x_cam
         X32[bad[:n_beh]] = mirrored.astype(np.float32)
     return np.ascontiguousarray(X32), np.ascontiguousarray(uv.astype(np.float32)), K, R, t, inl
+
+
+def align3d_scene(n, seed=0xA3D, model=0, outlier_frac=0.3, noise=0.01, nan_frac=0.0):
+    """3D-3D correspondences of the same tracks in two frames (stereo odometry between two rig poses, two monocular maps
+    of different gauge): rows of frame 1 uniform in a box of +-4 units at depths 4-12, frame 2 = s R x1 + t plus
+    N(0, noise) on both sides.  R is a rotation of 0.1-0.6 rad about a random axis, t up to 2 units per axis, s = 1 for
+    `model` 0 (rigid) and 0.5-2 (log-uniform) for `model` 1 (similarity).  `outlier_frac` of the frame-2 rows are
+    replaced by uniform-random positions in the frame-2 box; `nan_frac` of the rows (outliers first) get a NaN row in
+    one of the two arrays, the way pm_stereo_points_dev and pm_triangulate_dev mark a missing point.
+
+    Returns xyz1, xyz2 (n x 3 float32), the planted (s, R, t) and the boolean ground-truth inlier flags (False for
+    outliers and NaN rows).
+    """
+    rng = np.random.default_rng([seed, 0xA13D])
+    R = _rodrigues(rng.normal(size=3), rng.uniform(0.1, 0.6))
+    t = rng.uniform(-2.0, 2.0, 3)
+    s = 1.0 if model == 0 else float(np.exp(rng.uniform(np.log(0.5), np.log(2.0))))
+    X1 = np.c_[rng.uniform(-4.0, 4.0, (n, 2)), rng.uniform(4.0, 12.0, n)]
+    X2 = s * X1 @ R.T + t
+    lo, hi = X2.min(axis=0) if n else np.zeros(3), X2.max(axis=0) if n else np.ones(3)
+    x1 = X1 + rng.normal(0, noise, (n, 3))
+    x2 = X2 + rng.normal(0, noise, (n, 3))
+    inl = np.ones(n, bool)
+    order = rng.permutation(n)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = order[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform(lo, hi, (n_out, 3))
+    n_nan = int(round(nan_frac * n))
+    if n_nan:
+        rows = order[:n_nan]
+        inl[rows] = False
+        side = rng.integers(0, 2, n_nan).astype(bool)
+        x1[rows[side]] = np.nan
+        x2[rows[~side]] = np.nan
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), s, R, t, inl
