@@ -11,7 +11,11 @@
  *   - plain C: pointers + sizes, no C++/torch types; every function returns a pm_status
  *     (0 = ok, <0 = error) and never throws across the boundary (the reference's OpenCV calls
  *     raise cv::Exception instead).
- *   - caller owns every buffer; the library owns only the context's scratch arena.
+ *   - caller owns every buffer; the library owns only the context's scratch arena.  The arena grows on demand
+ *     (one stream synchronisation and a reallocation) and never shrinks.  A block from which a call on a
+ *     capturing stream took memory is not freed when the arena grows later: it is retired and freed by
+ *     pm_ctx_destroy, so a recorded graph stays valid for the life of the context ("Graph capture of the
+ *     estimator calls" below; pm_ctx_scratch_info).
  *   - a context is bound to one HIP device + one HIP stream and is NOT thread-safe; distinct
  *     contexts are independent.
  *   - functions without a `_dev` suffix take HOST pointers and block until the result is in
@@ -79,10 +83,34 @@ int  pm_device_download(pm_ctx* ctx, void* dst, const void* d_src, size_t bytes)
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
  * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine", "feat_blur", "feat_decimate",
- * "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather". */
+ * "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather".
+ * On a capturing stream no event is recorded, whatever enable says: a call that is captured, and every replay of the
+ * graph, adds nothing to pm_ctx_timing_get (time a replay with events of your own around the graph launch). */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
 int  pm_ctx_timing_reset(pm_ctx* ctx);
 int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* launches);
+/* Graph capture of the estimator calls.  These _dev calls keep no per-call state on the host and may be recorded into a
+ * HIP graph on a capturing stream, and the graph replayed after the rows and the device-side counts in the recorded
+ * buffers have changed: pm_ransac_run_dev, pm_ransac_{homography,affine,essential,pnp,align3d}_run_dev, the six
+ * *_refine_dev calls, pm_recover_pose_dev, pm_triangulate_dev, pm_gather_pnp_dev, pm_gather_align3d_dev and
+ * pm_transform_points3_dev (pm_transform_points_dev belongs to the image family and refuses capture like the rest of it).
+ *   Before recording: the *_run_dev calls take workgroup slots, candidate buffers and (E) a normalised copy from the
+ *     context's scratch arena, and a context's first such call allocates the arrival words.  Neither can happen on a
+ *     capturing stream, so make ONE EAGER CALL of the same or a larger shape (capacity, id range, PM_OPT_RANSAC_WG_IDS)
+ *     on this context first.  A call that finds the stream capturing and would have to grow the arena or allocate the
+ *     words returns PM_E_UNSUPPORTED, with a message that says so, before it allocates, synchronises or enqueues
+ *     anything; the capture stays valid, the outputs are untouched and the context works as before.  The refinements,
+ *     pose recovery, triangulation, the gathers and the transform take no scratch and need no such call.
+ *   What a recorded graph may outlive: any later call on the context, including one that grows the arena (a larger frame
+ *     of pm_stereo_sgm_dev, a larger matcher call, a larger capacity here).  The block the graph's nodes point into is then
+ *     retired, not freed; the new block is at least twice as large, so the retired blocks together stay below the live
+ *     one.  They are freed by pm_ctx_destroy: destroy the graph first.  Calls recorded in one graph share the arena the
+ *     way eager calls do: each *_run_dev carves it from the start, so only stream order (a single chain, one stream)
+ *     keeps two of them apart.
+ *   Timing: see pm_ctx_timing_enable: nothing is recorded on a capturing stream.
+ * pm_ctx_scratch_info: the arena's capacity in bytes and the number of retired blocks (either pointer may be NULL).
+ * Reads the context only: no device call, allowed during a capture. */
+int  pm_ctx_scratch_info(pm_ctx* ctx, size_t* capacity_bytes, int* retired_blocks);
 /* Diagnostics of the MFMA route of pm_bf_knn_l2_f32[_dev]: while enabled, each call records how
  * many queries took the exact re-scan branch of the refinement and whether a non-finite input
  * was seen; pm_ctx_knn_stats returns the values of the last such call (synchronises). */
@@ -549,8 +577,10 @@ static inline uint32_t pm_ransac_key_inliers(uint64_t key) { return (uint32_t)(k
  *   H        : 3x3 row-major, x2 ~ H x1, unit Frobenius norm, H[8] >= 0 (pm_f_scale_f33 gives OpenCV's H[8] = 1)
  *   best_key : pm_ransac_key(inliers, h) of the winner, 0 = no valid model
  * One launch per call (solve + score + winner + mask).  Graph capture: as the RANSAC-F entry points — no per-call
- * epoch argument (the arrival ticket returns to zero in the launch), so the call is not refused on a capturing
- * stream; the host forms synchronise and therefore cannot be captured. */
+ * epoch argument (the arrival ticket returns to zero in the launch), so the device form records on a capturing
+ * stream once an eager call of at least its shape has been made on the context ("Graph capture of the estimator
+ * calls" above: otherwise PM_E_UNSUPPORTED, before any side effect); the host forms synchronise and therefore cannot
+ * be captured. */
 enum { PM_ERR_REPROJ = 2 };
 /* Host in, host out (mirrors pm_ransac_fundamental).  mask (n bytes), n_inliers, best_key may be NULL.
  * Statuses: PM_E_INVALID (null params or points, bad range, error_kind != PM_ERR_REPROJ, null ctx),

@@ -37,7 +37,7 @@ PM_OK, PM_E_INVALID, PM_E_TOO_FEW, PM_E_NO_MODEL, PM_E_HIP, PM_E_NOMEM, PM_E_UNS
 EXPORTS = [
     "pm_ctx_create", "pm_ctx_destroy", "pm_ctx_set_stream", "pm_ctx_synchronize",
     "pm_ctx_timing_enable", "pm_ctx_timing_reset", "pm_ctx_timing_get", "pm_ctx_knn_diag_enable", "pm_ctx_knn_stats", "pm_ctx_knn_route",
-    "pm_ctx_filter_fusion_status",
+    "pm_ctx_filter_fusion_status", "pm_ctx_scratch_info",
     "pm_last_error",
     "pm_status_string", "pm_version",
     "pm_bf_knn_l2_f32", "pm_bf_knn_l2_f32_dev", "pm_bf_knn_hamming_u8", "pm_bf_knn_hamming_u8_dev",
@@ -572,6 +572,13 @@ class Context:
         v = C.c_int()
         _check(lib().pm_ctx_get_option(self._h, option, C.byref(v)))
         return v.value
+
+    def scratch_info(self):
+        """(capacity of the scratch arena in bytes, blocks retired because a recorded graph may hold them): reads the
+        context only, no device call."""
+        cap, retired = C.c_size_t(), C.c_int()
+        _check(lib().pm_ctx_scratch_info(self._h, C.byref(cap), C.byref(retired)))
+        return cap.value, retired.value
 
     def ransac_shard_parts_dev(self, view, hyp_begin, hyp_end, thresh_px, seed, drec_ptr, kind=PM_ERR_SAMPSON):
         prm = RansacParams(hyp_begin, hyp_end, seed, thresh_px, kind)

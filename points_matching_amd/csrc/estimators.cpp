@@ -551,7 +551,9 @@ int dev_prologue(pm_ctx* ctx, const Family& f, const DevView& view, const pm_ran
     PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
     PM_HIP_CHECK(hipSetDevice(ctx->device));
     if (!p) return PM_OK;
-    const int rc = pm::arena_reserve(ctx, scratch_bytes(ctx, f, static_cast<long long>(v->parts) * v->cap, p, thr));
+    // both before anything is enqueued: on a capturing stream either may refuse (E, P and X launch their solver first)
+    int rc = pm::arena_reserve(ctx, scratch_bytes(ctx, f, static_cast<long long>(v->parts) * v->cap, p, thr));
+    if (rc == PM_OK) rc = pm::sync_words_reserve(ctx);
     if (rc != PM_OK) return rc;
     pm::arena_reset(ctx);
     return PM_OK;

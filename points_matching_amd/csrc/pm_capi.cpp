@@ -22,11 +22,25 @@ void set_error(const char* fmt, ...)
 int arena_reserve(pm_ctx* ctx, size_t bytes)
 {
     if (bytes <= ctx->arena_cap) return PM_OK;
+    // growing synchronises the stream and allocates: neither may happen on a capturing stream (the first would end the capture)
+    if (stream_is_capturing(ctx->stream)) {
+        set_error("the stream is capturing a graph and this call needs %zu bytes of scratch where the context holds %zu: make one "
+                  "eager call of the same or a larger shape on this context first, then record", bytes, ctx->arena_cap);
+        return PM_E_UNSUPPORTED;
+    }
     PM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->arena) PM_HIP_CHECK(hipFree(ctx->arena));
+    size_t cap = align_up(bytes + bytes / 4, size_t(1) << 20);
+    if (ctx->arena && ctx->arena_in_graph) {
+        // a recorded graph may hold addresses inside this block: keep it until pm_ctx_destroy.  Doubling keeps the sum of the
+        // retired blocks below the size of the live one.
+        ctx->arena_retired.push_back(ctx->arena);
+        if (cap < 2 * ctx->arena_cap) cap = 2 * ctx->arena_cap;
+    } else if (ctx->arena) {
+        PM_HIP_CHECK(hipFree(ctx->arena));
+    }
     ctx->arena = nullptr;
     ctx->arena_cap = 0;
-    size_t cap = align_up(bytes + bytes / 4, size_t(1) << 20);
+    ctx->arena_in_graph = false;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&ctx->arena), cap);
     if (e != hipSuccess) {
         set_error("hipMalloc(%zu) failed: %s", cap, hipGetErrorString(e));
@@ -36,14 +50,39 @@ int arena_reserve(pm_ctx* ctx, size_t bytes)
     return PM_OK;
 }
 
-void arena_reset(pm_ctx* ctx) { ctx->arena_off = 0; }
+void arena_reset(pm_ctx* ctx)
+{
+    ctx->arena_off = 0;
+    ctx->arena_capturing = stream_is_capturing(ctx->stream);     // every call resets before it carves: asked once per call
+}
 
 void* arena_take(pm_ctx* ctx, size_t bytes)
 {
     size_t off = align_up(ctx->arena_off, 256);
     if (off + bytes > ctx->arena_cap) return nullptr;
     ctx->arena_off = off + bytes;
+    if (ctx->arena_capturing) ctx->arena_in_graph = true;        // the address goes into a graph node
     return ctx->arena + off;
+}
+
+int sync_words_reserve(pm_ctx* ctx)
+{
+    if (ctx->sync_words) return PM_OK;
+    // under capture the memset would become a node and clear the words on every replay, and hipMalloc is not for a capture
+    if (stream_is_capturing(ctx->stream)) {
+        set_error("the stream is capturing a graph and this is the context's first RANSAC call, which allocates its arrival "
+                  "words: make one eager call of the same or a larger shape on this context first, then record");
+        return PM_E_UNSUPPORTED;
+    }
+    int* w = nullptr;
+    PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w), 256));
+    const hipError_t e = hipMemsetAsync(w, 0, 256, ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(w);
+        PM_HIP_CHECK(e);
+    }
+    ctx->sync_words = w;
+    return PM_OK;
 }
 
 int pinned_reserve(pm_ctx* ctx, size_t bytes)
@@ -96,7 +135,8 @@ StagedBlock::~StagedBlock()
 
 ScopedKernelTime::ScopedKernelTime(pm_ctx* c, const char* n) : ctx(c), name(n)
 {
-    if (!ctx->timing) return;
+    // no events into a graph: they would be recorded again on every replay and could not be read (pm.h, timing)
+    if (!ctx->timing || stream_is_capturing(ctx->stream)) return;
     auto grab = [&]() -> hipEvent_t {
         if (!ctx->event_pool.empty()) {
             hipEvent_t e = ctx->event_pool.back();
@@ -200,6 +240,7 @@ int pm_ctx_destroy(pm_ctx* ctx)
     drain_timers(ctx);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
     if (ctx->arena) (void)hipFree(ctx->arena);
+    for (char* block : ctx->arena_retired) (void)hipFree(block);
     if (ctx->knn_stats) (void)hipFree(ctx->knn_stats);
     if (ctx->fg_counts) (void)hipFree(ctx->fg_counts);
     if (ctx->sync_words) (void)hipFree(ctx->sync_words);
@@ -302,6 +343,14 @@ int pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* lau
     }
     if (mean_ms) *mean_ms = ms;
     if (launches) *launches = n;
+    return PM_OK;
+}
+
+int pm_ctx_scratch_info(pm_ctx* ctx, size_t* capacity_bytes, int* retired_blocks)
+{
+    PM_REQUIRE(ctx != nullptr, PM_E_INVALID, "ctx is null");
+    if (capacity_bytes) *capacity_bytes = ctx->arena_cap;
+    if (retired_blocks) *retired_blocks = static_cast<int>(ctx->arena_retired.size());
     return PM_OK;
 }
 

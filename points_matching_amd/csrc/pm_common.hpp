@@ -74,6 +74,12 @@ struct pm_ctx {
     char* arena = nullptr;
     size_t arena_cap = 0;
     size_t arena_off = 0;
+    // Graph capture (pm.h, "Graph capture of the estimator calls"): arena_capturing is what arena_reset saw on the stream;
+    // a carve made under it sets arena_in_graph, after which a growth retires the block instead of freeing it (a recorded
+    // graph holds its addresses).  Retired blocks are freed in pm_ctx_destroy.
+    bool arena_capturing = false;
+    bool arena_in_graph = false;
+    std::vector<char*> arena_retired;
     // pinned host staging for small results
     void* pinned = nullptr;
     size_t pinned_cap = 0;
@@ -115,9 +121,14 @@ struct pm_ctx {
 
 namespace pm {
 
-int arena_reserve(pm_ctx* ctx, size_t bytes);          // ensure capacity (may sync + realloc)
-void arena_reset(pm_ctx* ctx);
+// ensure capacity (may sync + realloc).  A growth on a capturing stream is refused before anything is touched
+// (PM_E_UNSUPPORTED); a block that a captured graph may hold is retired, not freed, and the new one is at least twice as large.
+int arena_reserve(pm_ctx* ctx, size_t bytes);
+void arena_reset(pm_ctx* ctx);                          // also notes whether the stream is capturing, for arena_take
 void* arena_take(pm_ctx* ctx, size_t bytes);            // 256-B aligned carve; nullptr if over cap
+// The arrival words of the one-launch RANSAC kernels (ctx->sync_words), allocated and zeroed on a context's first such call;
+// on a capturing stream that first call is refused (PM_E_UNSUPPORTED) before anything is allocated or enqueued.
+int sync_words_reserve(pm_ctx* ctx);
 int pinned_reserve(pm_ctx* ctx, size_t bytes);
 // The private device block of a host-pointer entry point around its _dev form (the _dev form resets the arena, so the
 // staged rows cannot live there): add() the parts, alloc(), upload(), rc = the _dev form, download(), sync().  The first

@@ -678,6 +678,7 @@ extern "C" int pm_ransac_run_dev(pm_ctx* ctx, const float* d_xy1, const float* d
         PM_REQUIRE(p->hyp_end > p->hyp_begin, PM_E_INVALID, "empty hypothesis range");
         PM_HIP_CHECK(hipSetDevice(ctx->device));
         rc = pm::arena_reserve(ctx, fused_scratch_bytes(ctx, p) + 1024);
+        if (rc == PM_OK) rc = pm::sync_words_reserve(ctx);
         if (rc != PM_OK) return rc;
         pm::arena_reset(ctx);
         const pm_points_view v{d_xy1, d_xy2, d_n, 1, n_max, 0, 1, 0};

@@ -889,10 +889,8 @@ __global__ __launch_bounds__(RL_THREADS) void ransac_fused_lds(pm_points_view v,
 
 int sync_words(pm_ctx* ctx, int** out)
 {
-    if (!ctx->sync_words) {
-        PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ctx->sync_words), 256));
-        PM_HIP_CHECK(hipMemsetAsync(ctx->sync_words, 0, 256, ctx->stream));
-    }
+    const int rc = pm::sync_words_reserve(ctx);      // the entry points ask before they enqueue; here it is a lookup
+    if (rc != PM_OK) return rc;
     *out = ctx->sync_words;
     return PM_OK;
 }
