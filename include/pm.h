@@ -1536,6 +1536,53 @@ int pm_stereo_sgm_dev(pm_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right
 int pm_stereo_sgm(pm_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int lstride, int rstride,
                   const pm_sgm_params* p, int lr_max_diff16, int16_t* disp, int dstride, pm_stereo_info* info);
 
+/* ---- visual vocabularies: k-means / k-majority training and bag-of-words encoding — docs/SPEC.md S102-S106 ---------------
+ * Which earlier image does this one resemble?  Cluster a training set of descriptor rows into K words (cv::kmeans,
+ * cv::BOWKMeansTrainer::cluster; k-majority on binary rows as in DBoW2 / ORB-SLAM), then describe an image by the histogram
+ * of its rows' nearest words (cv::BOWImgDescriptorExtractor::compute).  The vocabulary is flat: the quantiser is the
+ * brute-force matcher with the K words as its train set, so a label is the trainIdx of pm_bf_knn_l2_u8_dev /
+ * pm_bf_knn_hamming_u8_dev with k = 1 (ties: the lowest word), and d_dist is that record's distance, bit for bit.
+ * Everything is integer arithmetic: every output is a function of the inputs alone (tests/vocab_ref.c restates it).
+ *   kind, bytes   PM_VOCAB_L2_U8: rows of `bytes` u8 values (the 128-byte rows of pm_detect_describe*), squared L2;
+ *                 PM_VOCAB_BITS: rows of bytes * 8 bits (the 32-byte rows of pm_detect_describe_bits*), Hamming.
+ *   pm_vocab      owns its device memory (words, u32 accumulators, the matcher's records and labels for max_rows rows);
+ *                 pm_vocab_create is the only allocation of the path.  Bound to the context's device.
+ *   pm_vocab_set / _set_dev / _get   the K x bytes words, row-major; _set and _get synchronise, _set_dev does not.
+ *   pm_vocab_init_stride_dev         word i <- row floor(i * n / K) (rows repeat when n < K).  Timing name "vocab_init".
+ *   pm_vocab_train[_dev]             `iters` iterations of { assign every row, then per word the rounded mean of its rows'
+ *                 bytes (halves up) / the majority of their bits (an even split gives 0); a word without rows keeps its
+ *                 bytes }.  d_labels: the n labels of the LAST iteration (those of the returned words iff its n_moved == 0).
+ *                 d_info: one pm_vocab_iter per iteration: n_changed = rows whose label differs from the previous iteration
+ *                 (n in iteration 0), n_empty = words without rows, n_moved = words whose bytes changed, cost = the exact sum
+ *                 of the integer distances (squared L2 / bit count) of the rows to their words before the update.  Both may
+ *                 be NULL.  iters == 0 runs nothing and writes nothing.  Timing names "vocab_update", "vocab_finish" and
+ *                 the matcher's own.
+ *   pm_vocab_assign[_dev]            m = n when d_n is NULL, else *d_n clamped to [0, n] (so the call chains after
+ *                 pm_detect_describe[_bits]_dev with n = max_kp, and an overflow count of -1 counts nothing).  d_words[i] /
+ *                 d_dist[i] = label / distance for i < m, -1 / NaN for m <= i < n; d_hist[w] = rows i < m with label w,
+ *                 exactly K words, overwritten.  Each may be NULL.  Timing name "vocab_hist".
+ * The _dev forms enqueue on the context's stream and do not synchronise; row pointers are 4-byte aligned.  The host forms
+ * stage their rows and outputs in a device block of their own.
+ * PM_E_INVALID: null required pointers, an unknown kind, bytes not a multiple of 4 in [4, 256] (bits: [4, 64]), K outside
+ * [1, 262144], max_rows < 1, n outside [1, max_rows], iters outside [0, 1000], a vocabulary of another device.
+ * PM_E_UNSUPPORTED: max_rows above 2^24 (a u32 sum could overflow), and a capturing stream, refused before anything is
+ * allocated or enqueued (the matcher inside refuses capture). */
+#define PM_VOCAB_L2_U8 0
+#define PM_VOCAB_BITS  1
+typedef struct pm_vocab pm_vocab;   /* opaque */
+typedef struct pm_vocab_iter { int32_t n_changed, n_empty, n_moved, reserved; uint64_t cost; } pm_vocab_iter;   /* 24 bytes */
+int pm_vocab_create(pm_ctx* ctx, int kind, int bytes, int K, int max_rows, pm_vocab** out);
+int pm_vocab_destroy(pm_vocab* v);
+int pm_vocab_set(pm_ctx* ctx, pm_vocab* v, const uint8_t* words);
+int pm_vocab_set_dev(pm_ctx* ctx, pm_vocab* v, const uint8_t* d_words);
+int pm_vocab_get(pm_ctx* ctx, const pm_vocab* v, uint8_t* words);
+int pm_vocab_init_stride_dev(pm_ctx* ctx, pm_vocab* v, const uint8_t* d_rows, int n);
+int pm_vocab_train_dev(pm_ctx* ctx, pm_vocab* v, const uint8_t* d_rows, int n, int iters, int32_t* d_labels, pm_vocab_iter* d_info);
+int pm_vocab_train(pm_ctx* ctx, pm_vocab* v, const uint8_t* rows, int n, int iters, int32_t* labels, pm_vocab_iter* info);
+int pm_vocab_assign_dev(pm_ctx* ctx, const pm_vocab* v, const uint8_t* d_rows, int n, const int32_t* d_n, int32_t* d_words,
+                        float* d_dist, uint32_t* d_hist);
+int pm_vocab_assign(pm_ctx* ctx, const pm_vocab* v, const uint8_t* rows, int n, int32_t* words, float* dist, uint32_t* hist);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

@@ -68,6 +68,8 @@ EXPORTS = [
     "pm_ransac_align3d", "pm_ransac_align3d_from_hyp", "pm_ransac_align3d_run_dev", "pm_align3d_refine",
     "pm_align3d_refine_dev", "pm_estimate_align3d", "pm_transform_points3_dev", "pm_transform_points3",
     "pm_gather_align3d_dev",
+    "pm_vocab_create", "pm_vocab_destroy", "pm_vocab_set", "pm_vocab_set_dev", "pm_vocab_get", "pm_vocab_init_stride_dev",
+    "pm_vocab_train_dev", "pm_vocab_train", "pm_vocab_assign_dev", "pm_vocab_assign",
     "pm_filter_cross", "pm_filter_cross_gather_dev",
     "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
     "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
@@ -1715,6 +1717,84 @@ class Pyramid:
         out = np.zeros((h.value, w.value), np.uint8)
         _check(lib().pm_pyramid_level_get(self._ctx._h, self._h, l, _p(out), out.size, C.byref(w), C.byref(h)))
         return out
+
+
+PM_VOCAB_L2_U8 = 0         # visual vocabularies (S102): rows of u8 values, squared L2
+PM_VOCAB_BITS = 1          # rows of bits, Hamming
+VOCAB_ITER_DTYPE = np.dtype([("n_changed", "<i4"), ("n_empty", "<i4"), ("n_moved", "<i4"), ("reserved", "<i4"),
+                             ("cost", "<u8")])                             # pm_vocab_iter, 24 bytes
+
+
+class Vocab:
+    """pm_vocab: K words of `nbytes` bytes on the device, trained by k-means (u8 rows) or k-majority (bit rows) and used to
+    encode row sets as bag-of-words histograms (SPEC S102-S106).  Owns its device memory; rows of a call: at most max_rows."""
+
+    def __init__(self, ctx, kind, nbytes, K, max_rows):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.kind, self.nbytes, self.K, self.max_rows = kind, nbytes, K, max_rows
+        _check(lib().pm_vocab_create(ctx._h, kind, nbytes, K, max_rows, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().pm_vocab_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, rows):
+        rows = np.ascontiguousarray(rows, np.uint8)
+        if rows.ndim != 2 or rows.shape[1] != self.nbytes:
+            raise PmError(PM_E_INVALID, "rows must be (n, %d) uint8" % self.nbytes)
+        return rows
+
+    def set(self, words):
+        words = self._rows(words)
+        if words.shape[0] != self.K:
+            raise PmError(PM_E_INVALID, "need %d words" % self.K)
+        _check(lib().pm_vocab_set(self._ctx._h, self._h, _p(words)))
+
+    def set_dev(self, dwords_ptr):
+        _check(lib().pm_vocab_set_dev(self._ctx._h, self._h, C.c_void_p(dwords_ptr)))
+
+    def get(self):
+        """The (K, nbytes) uint8 words; synchronises."""
+        words = np.zeros((self.K, self.nbytes), np.uint8)
+        _check(lib().pm_vocab_get(self._ctx._h, self._h, _p(words)))
+        return words
+
+    def init_stride_dev(self, drows_ptr, n):
+        _check(lib().pm_vocab_init_stride_dev(self._ctx._h, self._h, C.c_void_p(drows_ptr), n))
+
+    def train_dev(self, drows_ptr, n, iters, dlabels_ptr=0, dinfo_ptr=0):
+        """Enqueues `iters` iterations; dlabels_ptr (n int32) and dinfo_ptr (iters x 24 bytes) may be 0."""
+        _check(lib().pm_vocab_train_dev(self._ctx._h, self._h, C.c_void_p(drows_ptr), n, iters, C.c_void_p(dlabels_ptr or 0),
+                                        C.c_void_p(dinfo_ptr or 0)))
+
+    def train(self, rows, iters):
+        """Blocking: (labels int32 (n,), records VOCAB_ITER_DTYPE (iters,)); the words stay in the object (get())."""
+        rows = self._rows(rows)
+        labels = np.zeros(rows.shape[0], np.int32)
+        info = np.zeros(iters, VOCAB_ITER_DTYPE)
+        _check(lib().pm_vocab_train(self._ctx._h, self._h, _p(rows), rows.shape[0], iters, _p(labels), _p(info)))
+        return labels, info
+
+    def assign_dev(self, drows_ptr, n, dn_ptr=0, dwords_ptr=0, ddist_ptr=0, dhist_ptr=0):
+        """Enqueues the encoding of n rows (dn_ptr: device count, 0 = all n); every output pointer may be 0."""
+        _check(lib().pm_vocab_assign_dev(self._ctx._h, self._h, C.c_void_p(drows_ptr), n, C.c_void_p(dn_ptr or 0),
+                                         C.c_void_p(dwords_ptr or 0), C.c_void_p(ddist_ptr or 0), C.c_void_p(dhist_ptr or 0)))
+
+    def assign(self, rows):
+        """Blocking: (words int32 (n,), dist float32 (n,), hist uint32 (K,))."""
+        rows = self._rows(rows)
+        n = rows.shape[0]
+        words, dist, hist = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(self.K, np.uint32)
+        _check(lib().pm_vocab_assign(self._ctx._h, self._h, _p(rows), n, _p(words), _p(dist), _p(hist)))
+        return words, dist, hist
 
 
 def _xyz_pair(xyz1, xyz2):
