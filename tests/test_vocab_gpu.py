@@ -3,7 +3,8 @@ tests/vocab_ref.c: the words after every iteration count tested, the labels, eve
 distances and histogram of the encoding.  Row widths cover every layout of the update kernel (16 rows per wave-instruction,
 a lane count per row that does not divide 64, two rows per instruction, a whole wave per row; 1, 4 and 8 bit counters per
 lane) and every matcher route behind it; shapes cover one run longer than a wave or workgroup holds, runs of length 1, a
-skewed set, a partial wave and a single row."""
+skewed set, a partial wave and a single row.  test_vocab_limits_gpu.py goes on from here: the remaining lane layouts, float-shared
+distances, K of 2^16 and more, and 2^24 rows."""
 import gc
 import os
 
@@ -13,6 +14,7 @@ import pytest
 import points_matching_amd as pm
 import vocab_ref as R
 from points_matching_amd import api
+from vocab_cases import make_rows                   # (moved there unchanged: test_vocab_limits_cpu.py needs it without a device)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,17 +25,6 @@ KIND_NAME = {R.L2_U8: "l2", R.BITS: "bits"}
 WIDTHS = [(R.L2_U8, 4), (R.L2_U8, 36), (R.L2_U8, 128), (R.L2_U8, 256), (R.BITS, 8), (R.BITS, 32), (R.BITS, 64)]
 BOTH = [(R.L2_U8, 128), (R.BITS, 32)]
 _ids = lambda kb: "%s%d" % (KIND_NAME[kb[0]], kb[1])
-
-
-def make_rows(kind, n, nbytes, seed, protos=40, sigma=20.0, flip=0.15):
-    """Rows with cluster structure: prototypes plus noise of `sigma` (u8) or bits flipped with probability `flip`."""
-    rng = np.random.default_rng(seed)
-    lab = rng.integers(0, protos, n)
-    if kind == R.L2_U8:
-        p = rng.integers(0, 256, (protos, nbytes))
-        return np.clip(np.rint(p[lab] + rng.normal(0, sigma, (n, nbytes))), 0, 255).astype(np.uint8)
-    p = rng.integers(0, 256, (protos, nbytes)).astype(np.uint8)
-    return p[lab] ^ np.packbits((rng.random((n, nbytes * 8)) < flip).astype(np.uint8), axis=-1, bitorder="little")
 
 
 class Dev:

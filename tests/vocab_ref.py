@@ -1,6 +1,7 @@
 """ctypes loader of tests/vocab_ref.c, the plain-C restatement of docs/SPEC.md S102-S106 (visual vocabularies: stride
 initialisation, assignment by the matcher's rule, rounded-mean / majority update, the training loop and its records, the
-bag-of-words encoding).  Built on first use by cref.py; shared by test_vocab_cpu.py, test_vocab_gpu.py and tools/prof_vocab.py."""
+bag-of-words encoding).  Built on first use by cref.py; shared by test_vocab_cpu.py, test_vocab_gpu.py, vocab_cases.py
+(with test_vocab_limits_cpu.py and test_vocab_limits_gpu.py) and tools/prof_vocab.py."""
 import ctypes as C
 
 import numpy as np
