@@ -1583,6 +1583,58 @@ int pm_vocab_assign_dev(pm_ctx* ctx, const pm_vocab* v, const uint8_t* d_rows, i
                         float* d_dist, uint32_t* d_hist);
 int pm_vocab_assign(pm_ctx* ctx, const pm_vocab* v, const uint8_t* rows, int n, int32_t* words, float* dist, uint32_t* hist);
 
+/* ---- image database: tf-idf bag-of-words scoring and top-N retrieval — docs/SPEC.md S107-S112 ----------------------------
+ * The question the histogram of pm_vocab_assign exists for: which earlier image does this one resemble?  An append-only
+ * forward index on the device (per image its (word, tf) entries in ascending word order), per-word weights (1, given, or
+ * idf), and a query that scores EVERY image with DBoW2's L1 score of the two L1-normalised tf-idf vectors and selects the
+ * best `top` (DBoW2::Database::add / query with L1 scoring; the "score and rank" half of a retrieval system built on
+ * cv::BOWImgDescriptorExtractor).  Everything up to the one fp64 division per image is integer arithmetic: every output is
+ * a function of the inputs alone (tests/bowdb_ref.c restates it).  There is no inverted file.
+ *   pm_bowdb      owns one device block (offsets and norms of max_images images, max_entries entries, df / weight / the
+ *                 dense query table of K words, counts, selection scratch); pm_bowdb_create is the only allocation of the
+ *                 _dev path.  Bound to the context's device.  Weights start at 1.
+ *   pm_bowdb_clear_dev   removes all images, entries and df; keeps the weights (train the idf on a corpus, clear, use).
+ *   pm_bowdb_add[_dev]   d_hist: the K u32 counts that pm_vocab_assign_dev writes; T = their sum, nnz = the non-zero ones.
+ *                 Accepted iff 1 <= T <= 65535, images < max_images and entries + nnz <= max_entries, decided on the device:
+ *                 the entries (w, hist[w]) are appended in ascending w, df[w] += 1 for each, the norm is
+ *                 Nd = sum tf * weight[w] under the current weights, and *d_id = the previous image count.  Refused: nothing
+ *                 changes and *d_id = -1 (empty or T > 65535) or -2 (full).  d_id may be NULL.  Timing name "bow_add".
+ *   pm_bowdb_set_weights / _get_weights   K u32 in [0, 8191]; host calls, both synchronise.
+ *   pm_bowdb_idf_dev     weight[w] = floor(256 * log2(N / max(df[w], 1))) for the current image count N, by S109's integer
+ *                 algorithm (no transcendental function); N == 0 changes nothing.  After either setter the norm of every
+ *                 image is recomputed on the device.  Timing names "bow_idf" and "bow_norms".
+ *   pm_bowdb_query[_dev] q_w = hist[w] * weight[w], Nq = sum q_w; for an image d_w = tf * weight[w], Nd its norm;
+ *                 S = sum over the image's entries of min(q_w * Nd, d_w * Nq) in u64, score = (double)S / (double)(Nq * Nd),
+ *                 0 when Nq or Nd is 0.  A query with T = 0 or T > 65535 scores 0 everywhere.  Candidates: images with
+ *                 S > 0 and an id outside [excl_lo, excl_hi) (an empty window when excl_hi <= excl_lo), ordered by score
+ *                 descending, then id ascending; the selection is exact and does not depend on arrival order.
+ *                 d_ids / d_scores: `top` int32 / double, the first min(top, candidates) of them, then -1 / quiet NaN;
+ *                 d_count: that number; d_all: the score of every image 0 .. N-1, excluded ones included.  Each may be
+ *                 NULL.  The host form's `all` has room for the image count (pm_bowdb_get).  Timing names "bow_query_vec",
+ *                 "bow_score", "bow_top".
+ *   pm_bowdb_get  synchronises and copies out the counts and, where the pointer is not NULL, n_images + 1 offsets,
+ *                 n_entries words and tfs, n_images norms, K df and K weights (call it once for the counts).
+ * The _dev forms enqueue on the context's stream and do not synchronise: add and query chain behind pm_vocab_assign_dev
+ * with no host round trip (an overflow count of -1 there gives an all-zero histogram: the image is refused as empty).
+ * PM_E_INVALID: null required pointers (ctx, db, histogram, weights), K outside [1, 262144], max_images outside [1, 2^22],
+ * max_entries outside [1, 2^28], top outside [1, 256], a weight above 8191, a database of another device.
+ * PM_E_UNSUPPORTED: a capturing stream, refused by every call before anything is allocated or enqueued. */
+typedef struct pm_bowdb pm_bowdb;   /* opaque */
+int pm_bowdb_create(pm_ctx* ctx, int K, int max_images, int max_entries, pm_bowdb** out);
+int pm_bowdb_destroy(pm_bowdb* db);
+int pm_bowdb_clear_dev(pm_ctx* ctx, pm_bowdb* db);
+int pm_bowdb_add_dev(pm_ctx* ctx, pm_bowdb* db, const uint32_t* d_hist, int32_t* d_id);
+int pm_bowdb_add(pm_ctx* ctx, pm_bowdb* db, const uint32_t* hist, int32_t* id);
+int pm_bowdb_set_weights(pm_ctx* ctx, pm_bowdb* db, const uint32_t* weights);
+int pm_bowdb_get_weights(pm_ctx* ctx, const pm_bowdb* db, uint32_t* weights);
+int pm_bowdb_idf_dev(pm_ctx* ctx, pm_bowdb* db);
+int pm_bowdb_query_dev(pm_ctx* ctx, pm_bowdb* db, const uint32_t* d_hist, int top, int excl_lo, int excl_hi, int32_t* d_ids,
+                       double* d_scores, int32_t* d_count, double* d_all);
+int pm_bowdb_query(pm_ctx* ctx, pm_bowdb* db, const uint32_t* hist, int top, int excl_lo, int excl_hi, int32_t* ids, double* scores,
+                   int32_t* count, double* all);
+int pm_bowdb_get(pm_ctx* ctx, const pm_bowdb* db, int32_t* n_images, int32_t* n_entries, uint32_t* offsets, uint32_t* words,
+                 uint16_t* tfs, uint32_t* norms, uint32_t* df, uint32_t* weights);
+
 /* ---- residual report (main.cpp:103-123) -----------------------------------------------------
  * r[i] = [xa ya 1] * F * [xb yb 1]^T in fp64.  transposed != 0 reproduces the reference
  * literally ((xa,ya) = image-1 point, (xb,yb) = image-2 point: x1^T F x2, main.cpp:110-117);

@@ -70,6 +70,8 @@ EXPORTS = [
     "pm_gather_align3d_dev",
     "pm_vocab_create", "pm_vocab_destroy", "pm_vocab_set", "pm_vocab_set_dev", "pm_vocab_get", "pm_vocab_init_stride_dev",
     "pm_vocab_train_dev", "pm_vocab_train", "pm_vocab_assign_dev", "pm_vocab_assign",
+    "pm_bowdb_create", "pm_bowdb_destroy", "pm_bowdb_clear_dev", "pm_bowdb_add_dev", "pm_bowdb_add", "pm_bowdb_set_weights",
+    "pm_bowdb_get_weights", "pm_bowdb_idf_dev", "pm_bowdb_query_dev", "pm_bowdb_query", "pm_bowdb_get",
     "pm_filter_cross", "pm_filter_cross_gather_dev",
     "pm_bf_match_cross_l2_f32_dev", "pm_bf_match_cross_l2_u8_dev", "pm_bf_match_cross_hamming_u8_dev",
     "pm_bf_match_cross_l2_f32", "pm_bf_match_cross_l2_u8", "pm_bf_match_cross_hamming_u8",
@@ -1795,6 +1797,93 @@ class Vocab:
         words, dist, hist = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(self.K, np.uint32)
         _check(lib().pm_vocab_assign(self._ctx._h, self._h, _p(rows), n, _p(words), _p(dist), _p(hist)))
         return words, dist, hist
+
+
+class BowDb:
+    """pm_bowdb: an append-only database of bag-of-words histograms over K words on the device, scored by DBoW2's L1 score
+    under per-word weights and queried for its best `top` images (SPEC S107-S112).  Owns its device memory."""
+
+    def __init__(self, ctx, K, max_images, max_entries):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.K, self.max_images, self.max_entries = K, max_images, max_entries
+        _check(lib().pm_bowdb_create(ctx._h, K, max_images, max_entries, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().pm_bowdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _hist(self, hist):
+        hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+        if hist.size != self.K:
+            raise PmError(PM_E_INVALID, "need %d counts" % self.K)
+        return hist
+
+    def clear_dev(self):
+        _check(lib().pm_bowdb_clear_dev(self._ctx._h, self._h))
+
+    def add_dev(self, dhist_ptr, did_ptr=0):
+        """Enqueues the add of a device histogram (K uint32); did_ptr (one int32: the id, -1 or -2) may be 0."""
+        _check(lib().pm_bowdb_add_dev(self._ctx._h, self._h, C.c_void_p(dhist_ptr), C.c_void_p(did_ptr or 0)))
+
+    def add(self, hist):
+        """Blocking: the id of the image, -1 (empty or more than 65535 rows) or -2 (full)."""
+        hist = self._hist(hist)
+        i = C.c_int32(-9)
+        _check(lib().pm_bowdb_add(self._ctx._h, self._h, _p(hist), C.byref(i)))
+        return i.value
+
+    def set_weights(self, weights):
+        _check(lib().pm_bowdb_set_weights(self._ctx._h, self._h, _p(self._hist(weights))))
+
+    def get_weights(self):
+        w = np.zeros(self.K, np.uint32)
+        _check(lib().pm_bowdb_get_weights(self._ctx._h, self._h, _p(w)))
+        return w
+
+    def idf_dev(self):
+        _check(lib().pm_bowdb_idf_dev(self._ctx._h, self._h))
+
+    def query_dev(self, dhist_ptr, top, excl_lo=0, excl_hi=0, dids_ptr=0, dscores_ptr=0, dcount_ptr=0, dall_ptr=0):
+        """Enqueues a query; dids_ptr (top int32), dscores_ptr (top float64), dcount_ptr (one int32) and dall_ptr (a float64
+        per image) may each be 0."""
+        _check(lib().pm_bowdb_query_dev(self._ctx._h, self._h, C.c_void_p(dhist_ptr), top, excl_lo, excl_hi, C.c_void_p(dids_ptr or 0),
+                                        C.c_void_p(dscores_ptr or 0), C.c_void_p(dcount_ptr or 0), C.c_void_p(dall_ptr or 0)))
+
+    def query(self, hist, top, excl_lo=0, excl_hi=0, all_scores=False):
+        """Blocking: (ids int32 (count,), scores float64 (count,)) and, with all_scores, the score of every image."""
+        hist = self._hist(hist)
+        ids, scores, count = np.zeros(top, np.int32), np.zeros(top, np.float64), C.c_int32(0)
+        n_images = self.counts()[0] if all_scores else 0
+        every = np.zeros(max(n_images, 1), np.float64) if all_scores else None
+        _check(lib().pm_bowdb_query(self._ctx._h, self._h, _p(hist), top, excl_lo, excl_hi, _p(ids), _p(scores), C.byref(count), _p(every)))
+        n = count.value
+        if all_scores:
+            return ids[:n].copy(), scores[:n].copy(), every[:n_images].copy()
+        return ids[:n].copy(), scores[:n].copy()
+
+    def counts(self):
+        """(images, entries); synchronises."""
+        n, e = C.c_int32(), C.c_int32()
+        _check(lib().pm_bowdb_get(self._ctx._h, self._h, C.byref(n), C.byref(e), None, None, None, None, None, None))
+        return n.value, e.value
+
+    def get(self):
+        """The whole database as a dict: n_images, n_entries, offsets (n_images + 1), words, tfs (n_entries), norms (n_images),
+        df, weights (K); synchronises."""
+        n, e = self.counts()
+        d = dict(n_images=n, n_entries=e, offsets=np.zeros(n + 1, np.uint32), words=np.zeros(e, np.uint32), tfs=np.zeros(e, np.uint16),
+                 norms=np.zeros(n, np.uint32), df=np.zeros(self.K, np.uint32), weights=np.zeros(self.K, np.uint32))
+        _check(lib().pm_bowdb_get(self._ctx._h, self._h, None, None, _p(d["offsets"]), _p(d["words"]), _p(d["tfs"]), _p(d["norms"]),
+                                  _p(d["df"]), _p(d["weights"])))
+        return d
 
 
 def _xyz_pair(xyz1, xyz2):

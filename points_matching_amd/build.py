@@ -22,7 +22,7 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
            "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip", "triangulate.hip",
-           "align3d_solve.hip", "ransac_align3d_fused.hip", "align3d_refine.hip", "vocab.hip"]
+           "align3d_solve.hip", "ransac_align3d_fused.hip", "align3d_refine.hip", "vocab.hip", "bowdb.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -73,7 +73,10 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          "align3d_refine.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # visual vocabularies (S102-S106): the scatter-reduction keeps a run's sums in registers (8 counters per lane on 512-bit
          # rows); no kernel may use scratch or spill
-         "vocab.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "vocab.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # image database (S107-S112): one wave per image with four entry loads in flight, and a 1024-thread selection with
+         # its 2048 keys in LDS; no kernel may use scratch or spill
+         "bowdb.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
