@@ -154,7 +154,7 @@ enum {
     PM_OPT_KNN_RING_PROLOGUE = 14, /* u8 ring kernel: train tiles requested before the sweep starts, 2 .. 8 (default 2)    */
     PM_OPT_KNN_WIDE       = 15, /* L2 matcher beyond dim % 4 == 0 && dim <= 128 && 16-byte aligned rows: 1 = exact VALU kernel (round 2),
                                    2 = f16 matrix passes on padded copies, up to 256 dimensions (default)             */
-    PM_OPT_KNN_PREP_ROWS  = 16, /* u8 route, prep kernel: 1 = 64 rows per workgroup, 2 = 16 rows per workgroup (default)         */
+    PM_OPT_KNN_PREP_ROWS  = 16, /* u8 route, prep kernel: 1 = 64 rows per workgroup, 2 = 16 rows per workgroup (default), 3 = 32 */
     PM_OPT_RANSAC_FORM    = 17, /* one-launch RANSAC kernel: 1 = correspondences in registers, two teams of four waves (round 2),
                                    2 = correspondences in LDS, one wave per hypothesis, 12 waves (default)           */
     PM_OPT_RANSAC_WG_IDS  = 18, /* one-launch RANSAC kernel: hypothesis ids per workgroup.  0 = automatic (ids spread over ALL

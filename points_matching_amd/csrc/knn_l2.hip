@@ -327,7 +327,17 @@ __global__ __launch_bounds__(256) void knn_l2_prep16(const float* __restrict__ Q
 // the seeds, and VERIFIES the premise (integers in [0, 255]); a wrong hint raises bit 1 of stats[1] and the refinement
 // re-scans exactly, as on the f16 hint route.
 // ---------------------------------------------------------------------------------------------
-template <int ITERS>
+// Body (r6): per element one v_cvt_pk_u8_f32 (round, saturate to [0, 255], place the byte) and the premise checked by
+// converting the byte back (v_cvt_f32_ubyteN) and ONE compare with the loaded value: equal exactly for the integers in
+// [0, 255] (-0.0 included), unequal for NaN, +-inf, negatives, 256 and up and every non-integer, whichever way the pack
+// rounded a tie.  Centring is one XOR per dword, ||x - 128||^2 one v_dot4_i32_i8 per dword (an exact integer, < 2^24, so
+// float(sum) has the bits of the fmaf chain it replaces), the row sum four DPP row rotations; a wave publishes the flag
+// itself, after one ballot, so clean data meet no LDS instruction and no barrier.
+// Rows that FAIL the premise: their bytes, norms and seeds are saturated values and may differ from what a clamp-then-
+// truncate would give.  Nothing reads them for a result (the raised epoch flag sends the refinement to the canonical
+// f32 scan) and no index or address is derived from them: they only rank candidates nobody uses.
+// FULL: dim == 128, no column guards.
+template <int ITERS, bool FULL>
 __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q, int nq, int nq_pad,
                                                     const float* __restrict__ T, int nt, int nt_pad, int dim,
                                                     float* __restrict__ qnorm, float* __restrict__ tnorm,
@@ -335,7 +345,6 @@ __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q,
                                                     int* __restrict__ seeds, unsigned long long* __restrict__ stats,
                                                     unsigned epoch, int t_wide, uint2* __restrict__ Qf)
 {
-    __shared__ unsigned wbad[4];
     const int sub = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const int qblocks = nq_pad / (16 * ITERS);
     const bool is_t = static_cast<int>(blockIdx.x) >= qblocks;
@@ -343,7 +352,6 @@ __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q,
     const int n = is_t ? nt : nq;
     uint2* x8 = is_t ? T8 : Q8;
     const int row0 = (is_t ? blockIdx.x - qblocks : blockIdx.x) * (16 * ITERS);
-    unsigned bad = 0u;
     const int c0 = 8 * sub;
     f32x4 ld[ITERS][2];
 #pragma unroll
@@ -352,51 +360,50 @@ __global__ __launch_bounds__(256) void knn_l2_prep8(const float* __restrict__ Q,
         const float* p = x + static_cast<size_t>(row < n ? row : n - 1) * dim;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const int c = c0 + 4 * e < dim ? c0 + 4 * e : dim - 4;
+            const int c = (FULL || c0 + 4 * e < dim) ? c0 + 4 * e : dim - 4;
             ld[it][e] = *reinterpret_cast<const f32x4*>(p + c);
         }
     }
+    bool ok = true;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int row = row0 + it * 16 + grp;                 // < n_pad by construction
         const bool live = row < n;
-        float s = 0.f;
-        bool okrow = true;
-        unsigned w[2] = {0u, 0u};
+        unsigned w[2];
+        int si = 0;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const bool col = live && c0 + (e & ~3) < dim;
-            const float v = ld[it][e >> 2][e & 3];
-            okrow &= !col || ((v == __builtin_rintf(v)) && v >= 0.f && v <= 255.f);
-            const float vc = __builtin_fminf(__builtin_fmaxf(v, 0.f), 255.f);      // (NaN -> 0; the row is flagged anyway)
-            const float c = col ? vc - 128.f : 0.f;
-            s = fmaf(c, c, s);                                // exact: 128 * 128^2 < 2^24
-            const unsigned b = col ? (static_cast<unsigned>(static_cast<int>(vc)) ^ 0x80u) : 0u;   // x - 128 as a signed byte
-            w[e >> 2] |= b << (8 * (e & 3));
+        for (int e = 0; e < 2; ++e) {
+            const f32x4 v = ld[it][e];
+            unsigned u = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) u = __builtin_amdgcn_cvt_pk_u8_f32(v[b], b, u);
+            bool same = true;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) same &= static_cast<float>((u >> (8 * b)) & 0xffu) == v[b];
+            const bool col = live && (FULL || c0 + 4 * e < dim);
+            ok &= same || !col;
+            w[e] = col ? (u ^ 0x80808080u) : 0u;              // x - 128 as signed bytes
+            si = __builtin_amdgcn_sdot4(static_cast<int>(w[e]), static_cast<int>(w[e]), si, false);
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-        if (!okrow) bad |= 2u;
+        si += __builtin_amdgcn_update_dpp(0, si, 0x121, 0xF, 0xF, true);       // row_ror:1, 2, 4, 8: the 16 lanes of the row
+        si += __builtin_amdgcn_update_dpp(0, si, 0x122, 0xF, 0xF, true);
+        si += __builtin_amdgcn_update_dpp(0, si, 0x124, 0xF, 0xF, true);
+        si += __builtin_amdgcn_update_dpp(0, si, 0x128, 0xF, 0xF, true);
         x8[static_cast<size_t>(row) * ((is_t && t_wide) ? U8_WIDE_ROW16 * 2 : U8_DP / 8) + sub] = uint2{w[0], w[1]};
         if (!is_t && Qf) Qf[u8_qfrag_index2(row, sub)] = uint2{w[0], w[1]};      // (the coarse kernel's B-fragment order)
         if (sub == 0) {
-            const int si = static_cast<int>(s);
+            const float s = static_cast<float>(si);           // ||x - 128||^2 (an exact integer: the integer refinement's row term)
             if (is_t) {
                 seeds[seed_pos(row)] = live ? -(si >> 1) : U8_PAD_SEED;
                 if (t_wide) reinterpret_cast<int*>(T8)[u8_wide_seed_index(row)] = live ? -(si >> 1) : U8_PAD_SEED;
-                if (live) tnorm[row] = s;                     // ||t - 128||^2 (an exact integer: the integer refinement's row term)
+                if (live) tnorm[row] = s;
             } else if (live) {
                 qnorm[row] = s;
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bad |= static_cast<unsigned>(__shfl_xor(static_cast<int>(bad), o, 64));
-    if ((threadIdx.x & 63) == 0) wbad[threadIdx.x >> 6] = bad;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        bad = wbad[0] | wbad[1] | wbad[2] | wbad[3];
-        if (bad) atomicMax(&stats[1], (static_cast<unsigned long long>(epoch) << 32) | 3ull);   // not u8-valued: scan exactly
+    if (__builtin_amdgcn_ballot_w64(!ok) != 0ull) {           // wave-uniform; not u8-valued: scan exactly
+        if (!ok) atomicMax(&stats[1], (static_cast<unsigned long long>(epoch) << 32) | 3ull);
     }
 }
 
@@ -1766,22 +1773,21 @@ int knn_l2_enqueue(pm_ctx* ctx, const KnnL2Plan& p, const float* dq, int nq, con
 #define PM_PREP16G(DP_, AL_)                                                                                              \
     hipLaunchKernelGGL((knn_l2_prep16g<DP_, AL_>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm,   \
                        tnorm, Qh, Th, stats, epoch)
+#define PM_PREP8_(IT_, FULL_)                                                                                             \
+    hipLaunchKernelGGL((knn_l2_prep8<IT_, FULL_>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm,   \
+                       tnorm, reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), stats, epoch, \
+                       t_wide, static_cast<uint2*>(Qf))
+#define PM_PREP8(IT_)                                                                                                     \
+    do { if (dim == U8_DP) PM_PREP8_(IT_, true); else PM_PREP8_(IT_, false); } while (0)
         switch (p.prep) {
         case KNN_PREP_U8ROWS:
             hipLaunchKernelGGL(knn_l2_prep8_u8, grid, dim3(256), 0, ctx->stream, uq, nq, nq_pad, ut, nt, nt_pad, dim, qnorm, tnorm,
                                reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), t_wide,
                                static_cast<uint2*>(Qf));
             break;
-        case KNN_PREP8_16:
-            hipLaunchKernelGGL(knn_l2_prep8<1>, grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm,
-                               reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), stats, epoch,
-                               t_wide, static_cast<uint2*>(Qf));
-            break;
-        case KNN_PREP8_64:
-            hipLaunchKernelGGL(knn_l2_prep8<4>, grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim, qnorm, tnorm,
-                               reinterpret_cast<uint2*>(Qh), reinterpret_cast<uint2*>(Th), static_cast<int*>(seeds), stats, epoch,
-                               t_wide, static_cast<uint2*>(Qf));
-            break;
+        case KNN_PREP8_16: PM_PREP8(1); break;
+        case KNN_PREP8_32: PM_PREP8(2); break;
+        case KNN_PREP8_64: PM_PREP8(4); break;
         case KNN_PREP16_SEEDED:
             hipLaunchKernelGGL((knn_l2_prep16<true, 128, true>), grid, dim3(256), 0, ctx->stream, dq, nq, nq_pad, dt, nt, nt_pad, dim,
                                qnorm, tnorm, Qh, Th, static_cast<float*>(seeds), stats, epoch);
@@ -1794,6 +1800,8 @@ int knn_l2_enqueue(pm_ctx* ctx, const KnnL2Plan& p, const float* dq, int nq, con
         }
         if (p.prep_gen == KNN_GEN_PREP16G) PM_PREP_DP_AL(PM_PREP16G);
         else if (p.prep_gen == KNN_GEN_OFF) hipLaunchKernelGGL(knn_gen_off, dim3(1), dim3(64), 0, ctx->stream, stats, epoch);
+#undef PM_PREP8
+#undef PM_PREP8_
 #undef PM_PREP16G
 #undef PM_PREP16
 #undef PM_PREP16U

@@ -28,12 +28,13 @@ enum KnnVerdict {
 // first prep launch
 enum KnnPrep {
     KNN_PREP_U8ROWS,              // knn_l2_prep8_u8, 64 rows per workgroup
-    KNN_PREP8_16,                 // knn_l2_prep8<1>, 16 rows per workgroup
-    KNN_PREP8_64,                 // knn_l2_prep8<4>, 64 rows per workgroup
+    KNN_PREP8_16,                 // knn_l2_prep8<1, dim == 128>, 16 rows per workgroup
+    KNN_PREP8_64,                 // knn_l2_prep8<4, dim == 128>, 64 rows per workgroup
     KNN_PREP16_SEEDED,            // knn_l2_prep16<true, 128, true>
     KNN_PREP16_UNIT,              // knn_l2_prep16u<dp16, vec>
     KNN_PREP16,                   // knn_l2_prep16<false, dp16, vec>
-    KNN_PREP32                    // knn_l2_prep (norms only)
+    KNN_PREP32,                   // knn_l2_prep (norms only)
+    KNN_PREP8_32                  // knn_l2_prep8<2, dim == 128>, 32 rows per workgroup (PM_OPT_KNN_PREP_ROWS = 3)
 };
 // what follows it on the automatic route
 enum KnnPrepGen { KNN_GEN_NONE, KNN_GEN_PREP16G /* knn_l2_prep16g<dp16, vec> */, KNN_GEN_OFF /* knn_gen_off */ };
@@ -249,7 +250,13 @@ __attribute__((visibility("hidden"))) inline KnnL2Plan knn_l2_plan(const KnnL2Re
 
     p.prep_grid = nq_pad / 64 + nt_pad / 64;
     if (u8in) p.prep = KNN_PREP_U8ROWS;
-    else if (u8r && opts[PM_OPT_KNN_PREP_ROWS] != 1) {        // 16 rows per workgroup: matcher call 23.5 -> 22.2 us at C3, 15.1 -> 14.2 at C2
+    else if (u8r && opts[PM_OPT_KNN_PREP_ROWS] == 3) {
+        p.prep = KNN_PREP8_32;
+        p.prep_grid = nq_pad / 32 + nt_pad / 32;
+    }
+    else if (u8r && opts[PM_OPT_KNN_PREP_ROWS] != 1) {
+        // 16 rows per workgroup: matcher call 23.5 -> 22.2 us at C3, 15.1 -> 14.2 at C2; with the r6 body 16 / 32 / 64 rows
+        // give 19.7-20.2 / 20.0 / 21.1-21.3 us at C3 and 133.0-133.8 us alike at 32k (profiles/r06_bench_c3_ab.txt): 16 stays
         p.prep = KNN_PREP8_16;
         p.prep_grid = nq_pad / 16 + nt_pad / 16;
     }
