@@ -92,8 +92,8 @@ int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* la
 /* Graph capture of the estimator calls.  These _dev calls keep no per-call state on the host and may be recorded into a
  * HIP graph on a capturing stream, and the graph replayed after the rows and the device-side counts in the recorded
  * buffers have changed: pm_ransac_run_dev, pm_ransac_{homography,affine,essential,pnp,align3d}_run_dev, the six
- * *_refine_dev calls, pm_recover_pose_dev, pm_triangulate_dev, pm_gather_pnp_dev, pm_gather_align3d_dev and
- * pm_transform_points3_dev (pm_transform_points_dev belongs to the image family and refuses capture like the rest of it).
+ * *_refine_dev calls, pm_recover_pose_dev, pm_triangulate_dev, pm_bundle_adjust_dev, pm_gather_pnp_dev,
+ * pm_gather_align3d_dev and pm_transform_points3_dev (pm_transform_points_dev belongs to the image family and refuses capture like the rest of it).
  *   Before recording: the *_run_dev calls take workgroup slots, candidate buffers and (E) a normalised copy from the
  *     context's scratch arena, and a context's first such call allocates the arrival words.  Neither can happen on a
  *     capturing stream, so make ONE EAGER CALL of the same or a larger shape (capacity, id range, PM_OPT_RANSAC_WG_IDS)
@@ -926,7 +926,7 @@ int pm_gather_align3d_dev(pm_ctx* ctx, const pm_match* d_matches, const int32_t*
 /* ---- triangulation: map points from 2 .. 8 posed views (cv::triangulatePoints, then the step a map builder runs behind
  * it: refine the point on its reprojection error and keep it only if it lies in front of every camera, has enough
  * parallax and reprojects well) — docs/SPEC.md S93-S96.  The structure-only half of bundle adjustment; pm_pnp_refine* is
- * the motion-only half, and a caller can alternate them on one stream.  Point i is seen at pixel uv[v][2i .. 2i+1] (f32)
+ * the motion-only half, and a caller can alternate them on one stream (pm_bundle_adjust* below moves both at once).  Point i is seen at pixel uv[v][2i .. 2i+1] (f32)
  * of view v, whose pose is x_cam = R X + t as for PnP; one pinhole pm_camera K for every view, no distortion (pixels of a
  * real lens go through pm_undistort_points* first).  Per point, all fp64: the linear solution of the 2V x 4 DLT system
  * (S35's, generalised; a view that does not observe the point contributes zero rows), Levenberg-Marquardt over (X, Y, Z)
@@ -976,6 +976,60 @@ int pm_triangulate_dev(pm_ctx* ctx, const pm_tri_views* views, const pm_camera* 
  * synchronisation.  Under PM_TRI_USE_INITIAL xyz is read as well as written. */
 int pm_triangulate(pm_ctx* ctx, const float* const* uv, const double* const* Rt, int n_views, int n, const pm_camera* K,
                    const pm_tri_params* p, float* xyz, uint8_t* status, float* points4, float* err2, int* n_good);
+
+/* ---- local bundle adjustment: free poses and points of 2 .. 8 views refined together (the step a map builder runs after
+ * it inserts a keyframe) — docs/SPEC.md S113-S117.  pm_triangulate* moves the points alone and pm_pnp_refine* one pose
+ * alone; this call moves both at once: Levenberg-Marquardt on the summed squared pixel error over the used observations,
+ * solved through the Schur complement on the 6 F parameters of the F free poses (S40's rotation step on the left and its
+ * Cayley update, S95's point Jacobian, S24's damped Cholesky and acceptance rule, S23's summation order).  The views are
+ * the pm_tri_views a caller built for pm_triangulate_dev, passed on unchanged: row i of uv[v] is point i, a row S31 turns
+ * into NaN means "not seen", Rt[v] == NULL is [I|0] exactly, the device-side count is clamped to [0, cap]; one pinhole K
+ * for every view.  fixed_mask holds poses: with one held pose the scale is free and only the damping holds it, with two it
+ * is fixed.  The used set is decided once, at the start, so the cost function never changes and the accepted cost only
+ * falls: observation (i, v) is used iff row i of d_xyz is finite, the pixel is seen, the depth at the start is in (0, inf)
+ * and, with gate_px > 0, the squared pixel error at the start is <= gate_px^2; a point is used iff it has at least two used
+ * observations, and its observations count only then.  Points live in fp64 in the workspace for the whole run and are
+ * rounded to f32 once at the end, and only when a step was accepted: cost_out is the cost of the fp64 state, and a second
+ * call starts from the rounded rows, whose cost_in is therefore not this call's cost_out.  One launch of one workgroup: a
+ * latency design for a local window, not for a whole map. */
+#define PM_BA_MAX_POINTS 65536
+
+typedef struct pm_ba_params {
+    double   gate_px;     /* 0: use every observation; finite > 0: drop observations whose pixel error at the START exceeds it */
+    int32_t  max_iters;   /* [0, 100]; 0 = evaluate only (cost_in, the used set), nothing moves */
+    uint32_t fixed_mask;  /* bit v set: pose v is held.  At least one view held, at least one free. */
+    int32_t  flags, reserved;   /* 0 */
+} pm_ba_params;
+
+typedef struct pm_ba_info {
+    double  cost_in, cost_out;            /* sum of squared pixel errors over the used observations, fp64 state */
+    int32_t n_points, n_obs, iters, accepted, status, reserved;
+} pm_ba_info;
+
+/* Bytes of device workspace pm_bundle_adjust_dev needs for these views and this cap: pure host arithmetic (no context, no
+ * device), a multiple of 16, never decreasing in either argument; 0 for n_views outside [2, 8] or cap outside
+ * [0, PM_BA_MAX_POINTS]. */
+size_t pm_bundle_adjust_workspace(int n_views, int cap);
+/* Device form.  d_Rt_out: n_views x 12 doubles — a held pose bit for bit (a NULL pose as the exact identity), a free pose
+ * refined; d_Rt_out + 12 v may be the very pointer views->Rt[v] (every pose is read before any is written).  d_xyz: cap x 3
+ * f32, read and written: the map rows of pm_triangulate_dev, NaN rows included; used points are rewritten, every other row
+ * keeps its bytes, rows at or beyond the count are not touched.  d_used (may be NULL): cap bytes, bit v of byte i says
+ * observation (i, v) is in the cost.  d_work: work_bytes >= pm_bundle_adjust_workspace(n_views, cap) of device memory the
+ * call may scribble on (no alignment asked for).  *d_info: the costs, the used points and observations, iters = trial
+ * evaluations, accepted = accepted ones, status 0 = at least one step accepted; 1 = nothing improved (every output equals
+ * its input bit for bit; max_iters = 0 ends here); 2 = not enough data (a free view with fewer than 4 used observations,
+ * or no used point — cap == 0 and a count of 0 among them: outputs equal inputs, cost_out = cost_in).  Data outcomes are
+ * reported there only and the return value stays PM_OK.  PM_E_INVALID: a null context, struct, K, params, d_Rt_out, d_xyz,
+ * d_work, d_info or uv[v] of a view below n_views, n_views outside [2, 8], cap < 0, a bad K (S31's rule), max_iters outside
+ * [0, 100], gate_px negative or not finite, a fixed_mask holding no view or every view or with a bit at or above n_views,
+ * non-zero flags, work_bytes too small.  PM_E_UNSUPPORTED: cap > PM_BA_MAX_POINTS.  In every refusal nothing is written.
+ * No per-call state and no allocation: the call may be captured. */
+int pm_bundle_adjust_dev(pm_ctx* ctx, const pm_tri_views* views, const pm_camera* K, const pm_ba_params* p,
+                         double* d_Rt_out, float* d_xyz, uint8_t* d_used, void* d_work, size_t work_bytes, pm_ba_info* d_info);
+/* Host in, host out: uv and Rt are arrays of n_views host pointers (Rt[v] may be NULL), n points; xyz is read and written,
+ * used may be NULL.  One staged block (the workspace inside it), the device form, one synchronisation. */
+int pm_bundle_adjust(pm_ctx* ctx, const float* const* uv, const double* const* Rt, int n_views, int n, const pm_camera* K,
+                     const pm_ba_params* p, double* Rt_out, float* xyz, uint8_t* used, pm_ba_info* info);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

@@ -65,6 +65,7 @@ EXPORTS = [
     "pm_pose_refine", "pm_pose_refine_dev", "pm_estimate_pose_refined",
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
     "pm_solve_pnp_ransac", "pm_gather_pnp_dev", "pm_triangulate_dev", "pm_triangulate",
+    "pm_bundle_adjust_workspace", "pm_bundle_adjust_dev", "pm_bundle_adjust",
     "pm_ransac_align3d", "pm_ransac_align3d_from_hyp", "pm_ransac_align3d_run_dev", "pm_align3d_refine",
     "pm_align3d_refine_dev", "pm_estimate_align3d", "pm_transform_points3_dev", "pm_transform_points3",
     "pm_gather_align3d_dev",
@@ -306,6 +307,36 @@ def tri_views(uv_ptrs, Rt_ptrs, cap, count_ptr=None):
     return v
 
 
+PM_BA_MAX_POINTS = 65536
+
+
+class BaParams(C.Structure):
+    """pm_ba_params (include/pm.h, SPEC S113-S117); ba_params() fills it."""
+    _fields_ = [("gate_px", C.c_double), ("max_iters", C.c_int32), ("fixed_mask", C.c_uint32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class BaInfo(C.Structure):
+    """pm_ba_info (include/pm.h): costs in px^2 over the used observations, counts, status 0/1/2."""
+    _fields_ = [("cost_in", C.c_double), ("cost_out", C.c_double), ("n_points", C.c_int32), ("n_obs", C.c_int32),
+                ("iters", C.c_int32), ("accepted", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+BA_INFO_DTYPE = np.dtype([("cost_in", "<f8"), ("cost_out", "<f8"), ("n_points", "<i4"), ("n_obs", "<i4"), ("iters", "<i4"),
+                          ("accepted", "<i4"), ("status", "<i4"), ("reserved", "<i4")])   # the same record, 40 bytes
+
+
+def ba_params(fixed_mask=1, max_iters=10, gate_px=0.0, flags=0):
+    """fixed_mask: bit v holds pose v (at least one held, one free); max_iters 0 only evaluates; gate_px 0 keeps every
+    observation."""
+    return BaParams(gate_px, max_iters, fixed_mask, flags, 0)
+
+
+def bundle_adjust_workspace(n_views, cap):
+    """Bytes of device workspace for bundle_adjust_dev; 0 for bad arguments.  Needs no GPU."""
+    return int(lib().pm_bundle_adjust_workspace(n_views, cap))
+
+
 class HRefineInfo(C.Structure):
     """pm_h_refine_info (include/pm.h): costs in px^2, inliers used, LM iterations, status 0/1/2."""
     _fields_ = [("cost_in", C.c_double), ("cost_out", C.c_double), ("n_used", C.c_int32), ("iters", C.c_int32),
@@ -358,6 +389,7 @@ def lib():
         _lib.pm_last_error.restype = C.c_char_p
         _lib.pm_status_string.restype = C.c_char_p
         _lib.pm_format_match_list.restype = C.c_long
+        _lib.pm_bundle_adjust_workspace.restype = C.c_size_t
     return _lib
 
 
@@ -1679,6 +1711,36 @@ class Context:
         _check(lib().pm_triangulate(self._h, up, rp, len(uv), n, C.byref(_camera(K)), C.byref(params), _p(xyz), _p(status),
                                     _p(p4), _p(e2), C.byref(ng)))
         return xyz[:n], status[:n], p4[:n], e2[:n], ng.value
+
+    # -- local bundle adjustment (joint poses and points, Schur LM in one launch, SPEC S113-S117) -------------------------
+    def bundle_adjust_dev(self, views, K, params, dRt_out_ptr, dxyz_ptr, dused_ptr, dwork_ptr, work_bytes, dinfo_ptr):
+        """Device form over the TriViews of triangulate_dev: d_Rt_out n_views x 12 f64 (may be the input poses), d_xyz cap x 3
+        f32 read and written, optional d_used (cap bytes), a workspace of bundle_adjust_workspace(n_views, cap) bytes and
+        *d_info (BA_INFO_DTYPE).  Asynchronous on the stream."""
+        _check(lib().pm_bundle_adjust_dev(self._h, C.byref(views), C.byref(_camera(K)), C.byref(params), C.c_void_p(dRt_out_ptr),
+                                          C.c_void_p(dxyz_ptr), C.c_void_p(dused_ptr), C.c_void_p(dwork_ptr),
+                                          C.c_size_t(work_bytes), C.c_void_p(dinfo_ptr)))
+
+    def bundle_adjust(self, uv, Rt, K, xyz, params=None):
+        """uv: one (n, 2) pixel array per view (a NaN row: not seen there); Rt: one pose per view (12 doubles or None for
+        [I|0]); xyz: the map rows (n, 3), NaN rows allowed.  Returns (Rt_out (V, 12), xyz (n, 3) f32, used (n) u8, info (a
+        BA_INFO_DTYPE record))."""
+        params = params if params is not None else ba_params()
+        uv = [np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in uv]
+        n = uv[0].shape[0] if uv else 0
+        if any(u.shape[0] != n for u in uv) or len(Rt) != len(uv):
+            raise ValueError("every view needs n pixel rows and a pose")
+        poses = [None if r is None else np.ascontiguousarray(r, np.float64).reshape(12) for r in Rt]
+        up = (C.c_void_p * max(len(uv), 1))(*[_p(u) for u in uv])
+        rp = (C.c_void_p * max(len(uv), 1))(*[_p(r) for r in poses])
+        out = np.zeros((max(len(uv), 1), 12), np.float64)
+        rows = np.zeros((max(n, 1), 3), np.float32)
+        rows[:n] = np.asarray(xyz, np.float32).reshape(-1, 3)[:n]
+        used = np.zeros(max(n, 1), np.uint8)
+        info = np.zeros(1, BA_INFO_DTYPE)
+        _check(lib().pm_bundle_adjust(self._h, up, rp, len(uv), n, C.byref(_camera(K)), C.byref(params), _p(out), _p(rows),
+                                      _p(used), _p(info)))
+        return out[:len(uv)], rows[:n], used[:n], info[0]
 
 
 class Pyramid:
