@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import features_bits_ref as ref
+from features_ref import bits, blobs, image
 from points_matching_amd import api, build, io
 
 pytestmark = pytest.mark.gpu
@@ -23,50 +24,6 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = ["97x131", "129x128", "160x65", "golden1", "golden2", "tiled"]
 MAX_KP = 512        # above the candidate count of every input here (at most 315)
 CPU_BITS_INLIERS = 131
-
-
-def blobs(w, h, seed, n):
-    r = np.random.default_rng(seed)
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    im = np.full((h, w), 0.5)
-    for _ in range(n):
-        cx, cy, s = r.uniform(0, w), r.uniform(0, h), r.uniform(1.2, 3.5)
-        a = r.choice([-1, 1]) * r.uniform(0.2, 0.45)
-        im += a * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * s * s))
-    return np.clip(np.rint(255 * im), 0, 255).astype(np.uint8)
-
-
-def read_pgm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P5"
-        line = f.readline()
-        while line.startswith(b"#"):
-            line = f.readline()
-        w, h = (int(v) for v in line.split())
-        assert int(f.readline()) == 255
-        return np.frombuffer(f.read(w * h), np.uint8).reshape(h, w).copy()
-
-
-_IMG = {}
-
-
-def image(name):
-    """The inputs of tests/test_features_device_gpu.py."""
-    if name not in _IMG:
-        if name == "golden1":
-            _IMG[name] = read_pgm(os.path.join(GOLD, "img01_half.pgm"))
-        elif name == "golden2":
-            _IMG[name] = read_pgm(os.path.join(GOLD, "img02_half.pgm"))
-        elif name == "tiled":
-            _IMG[name] = np.tile(blobs(64, 64, 5, 40), (3, 3))
-        else:
-            w, h = (int(v) for v in name.split("x"))
-            _IMG[name] = blobs(w, h, 11, w * h // 60)
-    return _IMG[name]
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

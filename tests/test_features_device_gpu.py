@@ -12,43 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from features_ref import bits, blobs, candidate_responses, check_descriptors, gaussian_np, image
 from points_matching_amd import api, build, io
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def blobs(w, h, seed, n):
-    r = np.random.default_rng(seed)
-    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
-    im = np.full((h, w), 0.5)
-    for _ in range(n):
-        cx, cy, s = r.uniform(0, w), r.uniform(0, h), r.uniform(1.2, 3.5)
-        a = r.choice([-1, 1]) * r.uniform(0.2, 0.45)
-        im += a * np.exp(-((x - cx) ** 2 + (y - cy) ** 2) / (2 * s * s))
-    return np.clip(np.rint(255 * im), 0, 255).astype(np.uint8)
-
-
-def read_pgm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P5"
-        line = f.readline()
-        while line.startswith(b"#"):
-            line = f.readline()
-        w, h = (int(v) for v in line.split())
-        assert int(f.readline()) == 255
-        return np.frombuffer(f.read(w * h), np.uint8).reshape(h, w).copy()
-
-
-def image(name):
-    if name == "golden1":
-        return read_pgm(os.path.join(GOLD, "img01_half.pgm"))
-    if name == "golden2":
-        return read_pgm(os.path.join(GOLD, "img02_half.pgm"))
-    if name == "tiled":
-        return np.tile(blobs(64, 64, 5, 40), (3, 3))
-    w, h = (int(v) for v in name.split("x"))
-    return blobs(w, h, 11, w * h // 60)
 
 
 _HOST = {}
@@ -114,24 +82,6 @@ def dev_extract(ctx, img, max_kp=MAX_KP):
     return res
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def descriptor_shares(dev_f32, host_f32):
-    diff = np.abs(dev_f32.astype(np.int32) - host_f32.astype(np.int32)).max(axis=1)
-    return int((diff > 0).sum()), int((diff > 1).sum())
-
-
-def check_descriptors(name, dev_f32, host_f32):
-    n = host_f32.shape[0]
-    any_diff, big_diff = descriptor_shares(dev_f32, host_f32)
-    print("features parity %s: rows %d, rows that differ %d (%.4f), rows off by more than 1: %d (%.4f)" %
-          (name, n, any_diff, any_diff / n, big_diff, big_diff / n))
-    assert any_diff <= max(1, int(0.02 * n)), (name, any_diff, n)
-    assert big_diff <= max(1, int(0.005 * n)), (name, big_diff, n)
-
-
 @pytest.mark.parametrize("name", ["97x131", "129x128", "160x65", "golden1", "golden2", "tiled"])
 def test_keypoints_bit_equal_and_descriptors_within_caps(ctx, host, name):
     kp_h, desc_h = host(name)
@@ -157,37 +107,6 @@ def test_small_image_gives_no_keypoints(ctx):
     assert n == 0
     kp_b, u8_b, f32_b, meta_b = ctx.detect_describe(img, 64)
     assert kp_b.shape == (0, 2) and u8_b.shape == (0, 128)
-
-
-def candidate_responses(ctx, n_oct, contrast=0.03, edge_r=10.0):
-    """The extrema scan of the host file restated in numpy float32 on the Gaussian levels of the last device call:
-    |response| of every candidate in selection order (descending, ties in scan order)."""
-    contrast, edge_r, two, four = np.float32(contrast), np.float32(edge_r), np.float32(2), np.float32(4)
-    out = []
-    for o in range(n_oct):
-        L = [ctx.detect_level(o, i) for i in range(6)]
-        dog = [L[i + 1] - L[i] for i in range(5)]
-        h, w = dog[0].shape
-        for i in (1, 2, 3):
-            def sh(d, dy, dx):
-                return d[8 + dy:h - 8 + dy, 8 + dx:w - 8 + dx]
-            c = sh(dog[i], 0, 0)
-            is_max, is_min = np.ones(c.shape, bool), np.ones(c.shape, bool)
-            for d in dog[i - 1:i + 2]:
-                for dy in (-1, 0, 1):
-                    for dx in (-1, 0, 1):
-                        is_max &= ~(sh(d, dy, dx) > c)
-                        is_min &= ~(sh(d, dy, dx) < c)
-            d = dog[i]
-            dxx = sh(d, 0, 1) + sh(d, 0, -1) - two * c
-            dyy = sh(d, 1, 0) + sh(d, -1, 0) - two * c
-            dxy = (sh(d, 1, 1) - sh(d, 1, -1) - sh(d, -1, 1) + sh(d, -1, -1)) / four
-            tr, det = dxx + dyy, dxx * dyy - dxy * dxy
-            ok = (np.abs(c) > contrast / np.float32(3)) & (is_max | is_min) & ~((det <= 0) | (tr * tr * edge_r >= (edge_r + 1) * (edge_r + 1) * det))
-            ys, xs = np.nonzero(ok)
-            out += [(-float(abs(c[y, x])), o, i, y, x) for y, x in zip(ys, xs)]
-    out.sort()
-    return np.array([-v[0] for v in out], np.float32)
 
 
 def test_cap_inside_a_tie(ctx, host):
@@ -218,36 +137,6 @@ def test_cap_cuts_the_candidates_of_a_photograph(ctx, host):
     assert 5 <= kp_h.shape[0] <= 100 and n == kp_h.shape[0]
     assert (bits(kp) == bits(kp_h)).all()
     check_descriptors("golden1, max_kp 100", f32, desc_h)
-
-
-# ---- Gaussian levels: a numpy restatement of gaussian() of the host file, double accumulation in the same order
-
-def reflect_index(i, n):
-    i = np.array(i)
-    for _ in range(4):
-        i = np.where(i < 0, -i - 1, i)
-        i = np.where(i >= n, 2 * n - 1 - i, i)
-    return i
-
-
-def gaussian_np(plane, sigma):
-    r = int(4.0 * sigma + 0.5)
-    k = [math.exp(-0.5 * i * i / (sigma * sigma)) for i in range(-r, r + 1)]        # libm exp, like the host
-    s = 0.0
-    for v in k:
-        s += v
-    k = [v / s for v in k]
-    h, w = plane.shape
-    ys = reflect_index(np.arange(-r, h + r), h)
-    a = np.zeros((h, w), np.float64)
-    for i in range(-r, r + 1):
-        a = a + np.float64(k[i + r]) * plane[ys[r + i:r + i + h], :].astype(np.float64)
-    tmp = a.astype(np.float32)
-    xs = reflect_index(np.arange(-r, w + r), w)
-    a = np.zeros((h, w), np.float64)
-    for i in range(-r, r + 1):
-        a = a + np.float64(k[i + r]) * tmp[:, xs[r + i:r + i + w]].astype(np.float64)
-    return a.astype(np.float32)
 
 
 def test_gaussian_levels_bit_equal_to_the_host_arithmetic(ctx):
