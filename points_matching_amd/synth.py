@@ -631,3 +631,144 @@ def align3d_scene(n, seed=0xA3D, model=0, outlier_frac=0.3, noise=0.01, nan_frac
         x1[rows[side]] = np.nan
         x2[rows[~side]] = np.nan
     return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), s, R, t, inl
+
+
+def multiview_scene_wide(n, n_views, seed=0, width=4000, height=3000, focal=3000.0, aspect=1.0, pp_offset=(0.0, 0.0),
+                         offset=0.0, world_rot=False, angle=0.1, baseline=0.25, depth=(4.0, 12.0), forward=False,
+                         noise_px=0.5, blank_frac=0.0, swap_every=0, first_identity=False):
+    """Tracks of n map points over n_views posed views at hard geometry (the scenes of the triangulation and bundle
+    adjustment tests): a map far from the origin, any world frame, turns up to 60 degrees between views, small
+    parallax, depths of 1:1000, narrow and wide fields, motion along the optical axis.
+
+    K as calibrated_view_wide.  The points are drawn in the frame of view 0: a uniform pixel and a depth log-uniform over
+    `depth`.  View v > 0 sits `baseline` times depth[0] (the nearest depth) from view 0, sideways on a ring, or
+    (`forward`) on view 0's optical axis towards the points, and is turned by `angle` * v / (n_views - 1) radians about an
+    axis 0.3 off the optical axis (mostly roll, so that the points stay in front).  A point is kept if every view sees it
+    at least 0.1 * depth[0] in front and within one image size of the image; ValueError if that leaves too few.  Then the
+    world frame: with `world_rot` a uniform-random rotation of the whole scene, and a shift of all points and camera
+    centres by a vector of length `offset`, so that |t| ~ offset.  Every pixel gets N(0, noise_px); `blank_frac` of the
+    observations become NaN rows; with swap_every = k, every k-th track has the pixel of one view (not view 0) replaced
+    by a uniform-random one.  `first_identity` gives view 0 the pose None and needs offset = 0 and no world_rot.
+
+    Returns K (fx, fy, cx, cy), uv (a list of (n, 2) f32), Rt (a list of 12 doubles, R row-major then t, x_cam = R X + t;
+    None for view 0 with first_identity), X (n x 3 float64 world points) and the boolean flags of the swapped tracks.
+    """
+    if first_identity and (offset or world_rot):
+        raise ValueError("a None pose for view 0 needs offset = 0 and no world rotation")
+    rng = np.random.default_rng([seed, 0x3D1E])
+    Km = _wide_camera(width, height, focal, aspect, pp_offset)
+    K = np.array([Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2]])
+    Ki = np.linalg.inv(Km)
+    spread = baseline * depth[0]
+    Rv, cv = [np.eye(3)], [np.zeros(3)]
+    for v in range(1, n_views):
+        a = 2 * np.pi * (v + rng.uniform(-0.3, 0.3)) / max(n_views - 1, 1)
+        if forward:
+            c = np.array([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), 1.0]) * spread * v / (n_views - 1)
+        else:
+            c = np.array([np.cos(a), 0.6 * np.sin(a), rng.uniform(-0.15, 0.15)]) * spread * rng.uniform(0.7, 1.0)
+        axis = np.array([0.3 * rng.normal(), 0.3 * rng.normal(), 1.0])
+        Rv.append(_rodrigues(axis, angle * v / (n_views - 1)))
+        cv.append(c)
+    X0 = np.zeros((0, 3))
+    for _ in range(200):
+        if X0.shape[0] >= n:
+            break
+        m = 4 * n + 64
+        ray = np.c_[rng.uniform([0, 0], [width, height], (m, 2)), np.ones(m)] @ Ki.T
+        P = ray * _log_uniform(rng, depth[0], depth[1], m)[:, None]
+        ok = np.ones(m, bool)
+        for Rm, c in zip(Rv, cv):
+            Pc = (P - c) @ Rm.T
+            with np.errstate(all="ignore"):
+                p = Pc @ Km.T
+                p = p[:, :2] / p[:, 2:3]
+            ok &= ((Pc[:, 2] > 0.1 * depth[0]) & (p[:, 0] > -width) & (p[:, 0] < 2 * width) & (p[:, 1] > -height) &
+                   (p[:, 1] < 2 * height))
+        X0 = np.r_[X0, P[ok]]
+    if X0.shape[0] < n:
+        raise ValueError("the fields of view barely overlap: no scene")
+    X0 = X0[:n]
+    Rw = _rodrigues(rng.normal(size=3), rng.uniform(0.0, np.pi)) if world_rot else np.eye(3)
+    shift = rng.normal(size=3)
+    shift *= offset / np.linalg.norm(shift)
+    X = X0 @ Rw.T + shift
+    Rt = []
+    for v, (Rm, c) in enumerate(zip(Rv, cv)):
+        Rv_w = Rm @ Rw.T
+        Rt.append(None if (v == 0 and first_identity) else np.r_[Rv_w.reshape(-1), -Rv_w @ (Rw @ c + shift)])
+    uv = []
+    for Rm, c in zip(Rv, cv):
+        Pc = (X0 - c) @ Rm.T
+        p = Pc @ Km.T
+        uv.append(p[:, :2] / p[:, 2:3] + rng.normal(0, noise_px, (n, 2)))
+    swapped = np.zeros(n, bool)
+    if swap_every:
+        swapped[::swap_every] = True
+        for i in np.nonzero(swapped)[0]:
+            uv[1 + rng.integers(0, n_views - 1)][i] = rng.uniform([0, 0], [width, height])
+    if blank_frac:
+        for v in range(n_views):
+            uv[v][rng.random(n) < blank_frac] = np.nan
+    return K, [np.ascontiguousarray(u.astype(np.float32)) for u in uv], Rt, X, swapped
+
+
+def align3d_scene_wide(n, seed=0, model=0, offset=0.0, scale=None, angle=None, span=8.0, flat=1.0, line=1.0, noise=0.01,
+                       outlier_frac=0.3, nan_frac=0.0):
+    """align3d_scene at hard geometry: frames far from the origin, scales of 1e-3 .. 1e3, rotations of exactly pi or of
+    1e-6 rad, flat, thin and collinear clouds, clouds 1e-3 units wide.
+
+    Frame-1 rows are uniform in a cube of side `span` about the origin, its third axis shrunk by `flat` and its second and
+    third by `line` (1e-4: a slab or a needle that thin), the cube then turned by a random rotation.  With flat = 0 or
+    line = 0 the rows are A + j d1 + k d2 (or A + k d) with A, d1, d2 on a grid of 2^-10 units and integer j, k, so that
+    they are EXACTLY coplanar (collinear) in float32; that needs offset = 0 and span = 8.  The rows are then shifted by a
+    vector of length `offset`, which frame 2 = s R x1 + t inherits.  R is a rotation by `angle` radians (None: uniform in
+    [0, pi]) about a random axis, t up to span / 4 per axis, s = 1 for `model` 0; for `model` 1 `scale`, or log-uniform in
+    [0.5, 2] when None.  Frame 1 gets N(0, noise), frame 2 N(0, s * noise) (the same relative noise); `outlier_frac` of
+    the frame-2 rows become uniform-random positions in the frame-2 box; `nan_frac` as in align3d_scene.
+
+    Returns xyz1, xyz2 (n x 3 float32), the planted (s, R, t) and the boolean ground-truth inlier flags, as
+    align3d_scene does.  With flat = 0 or line = 0 frame 1 carries no noise (it would leave the plane).
+    """
+    exact = flat == 0 or line == 0
+    if exact and (offset or span != 8.0):
+        raise ValueError("exactly coplanar or collinear rows need offset = 0 and span = 8")
+    rng = np.random.default_rng([seed, 0xA13E])
+    R = _rodrigues(rng.normal(size=3), rng.uniform(0.0, np.pi) if angle is None else float(angle))
+    t = rng.uniform(-span / 4.0, span / 4.0, 3)
+    s = 1.0 if model == 0 else (float(np.exp(rng.uniform(np.log(0.5), np.log(2.0)))) if scale is None else float(scale))
+    att = _rodrigues(rng.normal(size=3), rng.uniform(0.0, np.pi))
+    if exact:
+        g = 2.0 ** -10
+        A = np.rint(rng.uniform(-1.0, 1.0, 3) / g) * g
+        d1 = np.rint(att[:, 0] * span / 1024.0 / g) * g
+        d2 = np.rint(att[:, 1] * span / 1024.0 / g) * g
+        j = rng.integers(-512, 513, n)[:, None]
+        k = rng.integers(-512, 513, n)[:, None]
+        X1 = A + j * d1 + (0 if line == 0 else 1) * k * d2
+    else:
+        X1 = rng.uniform(-span / 2.0, span / 2.0, (n, 3)) * np.array([1.0, line, line * flat])
+        X1 = X1 @ att.T
+    shift = rng.normal(size=3)
+    shift *= offset / np.linalg.norm(shift)
+    X1 = X1 + shift
+    X2 = s * X1 @ R.T + t
+    lo, hi = X2.min(axis=0) if n else np.zeros(3), X2.max(axis=0) if n else np.ones(3)
+    hi = np.maximum(hi, lo + s * span / 8.0)                   # a flat cloud still has outliers off its plane
+    x1 = X1 + (0.0 if exact else rng.normal(0, noise, (n, 3)))
+    x2 = X2 + rng.normal(0, s * noise, (n, 3))
+    inl = np.ones(n, bool)
+    order = rng.permutation(n)
+    n_out = int(round(outlier_frac * n))
+    if n_out:
+        bad = order[:n_out]
+        inl[bad] = False
+        x2[bad] = rng.uniform(lo, hi, (n_out, 3))
+    n_nan = int(round(nan_frac * n))
+    if n_nan:
+        rows = order[:n_nan]
+        inl[rows] = False
+        side = rng.integers(0, 2, n_nan).astype(bool)
+        x1[rows[side]] = np.nan
+        x2[rows[~side]] = np.nan
+    return np.ascontiguousarray(x1.astype(np.float32)), np.ascontiguousarray(x2.astype(np.float32)), s, R, t, inl

@@ -155,7 +155,10 @@ def np_dense(K, uv, Rt0, X0, used, fixed_mask, iters=200):
     cost, mu, small = float(r @ r), 1e-3 * float((J * J).sum(0).max()), 0
     for _ in range(iters):
         A = np.vstack([J, np.sqrt(mu) * np.eye(J.shape[1])])
-        d = np.linalg.lstsq(A, np.r_[-r, np.zeros(J.shape[1])], rcond=None)[0]
+        try:
+            d = np.linalg.lstsq(A, np.r_[-r, np.zeros(J.shape[1])], rcond=None)[0]
+        except np.linalg.LinAlgError:                       # LAPACK gives up at a huge mu, after the last gain: the end
+            break
         trial = list(poses)
         for a, v in enumerate(free):
             trial[v] = (T._rot(d[6 * a:6 * a + 3]) @ poses[v][0], poses[v][1] + d[6 * a + 3:6 * a + 6])

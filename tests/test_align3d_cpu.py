@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import align3d_ref as R
+from backend_cases import np_fit            # SVD Kabsch / Umeyama with the reflection fix, float64
 from points_matching_amd import api, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,19 +124,6 @@ def test_three_inliers_among_500_rows_is_deterministic():
 
 
 # -- S101 against numpy ---------------------------------------------------------------------------------------------------------
-def np_fit(model, a, b):
-    """Kabsch / Umeyama by SVD with the reflection fix, float64: (T 13, singular values with the fix's sign)."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    ca, cb = a.mean(axis=0), b.mean(axis=0)
-    A, B = a - ca, b - cb
-    U, S, Vt = np.linalg.svd(B.T @ A)
-    d = np.sign(np.linalg.det(U) * np.linalg.det(Vt))
-    D = np.array([1.0, 1.0, d])
-    Rm = U @ np.diag(D) @ Vt
-    s = float((S * D).sum() / (A * A).sum()) if model == R.SIMILARITY else 1.0
-    return R.pack(s, Rm, cb - s * Rm @ ca), S * D
-
-
 def _fit_scenes():
     """(name, model, xyz1, xyz2, mask): clean, noisy and near-planar inlier sets, offsets from the origin included."""
     out = []
