@@ -13,13 +13,15 @@
 // that view's terms to the point blocks and, for a free view, sums the 21 + 6 pose terms through the tree, so the 27 F pose
 // sums never sit in registers together.  The reduced system (6F <= 42 parameters) is summed one pair of free views at a time,
 // its 36 + 6 sums in two passes of 21 partials per thread, re-reading Y and W and not the observations; its Cholesky spreads
-// a column's rows over the first 6F threads (each L_ij keeps S24's ascending chain), thread 0 substitutes.
+// a column's rows over the first 6F threads (each L_ij keeps S24's ascending chain), thread 0 substitutes.  The point blocks'
+// 3 x 3 factor and substitutions (lm_factor, lm_subst) and S40's pose update (pose_update) are lm_core.hpp's.
 //
 // The launch keeps no per-call state and allocates nothing, so the device form may be captured; the host form stages its
 // rows and the workspace through pm::StagedBlock and synchronises once.
 #include <cmath>
 
 #include "essential_core.hpp"
+#include "lm_core.hpp"
 #include "pm_common.hpp"
 #include "refine_reduce.hpp"
 
@@ -29,6 +31,11 @@ namespace {
 using pm_essential::Cam;
 using pm_hrefine::HR_CH;
 using pm_hrefine::HR_P;
+using pm_hrefine::LM_LAMBDA0;
+using pm_hrefine::LM_STEP_TOL;
+using pm_hrefine::lm_factor;
+using pm_hrefine::lm_subst;
+using pm_hrefine::pose_update;
 using pm_hrefine::tree;
 
 constexpr int BA_MAXV = PM_TRI_MAX_VIEWS;
@@ -38,8 +45,6 @@ constexpr int BA_NU = 27;                 // per free view: U (21 entries j <= k
 constexpr int BA_NS = 42;                 // per pair of free views: 36 entries of Y W^T and 6 of Y gp ...
 constexpr int BA_NH = BA_NS / 2;          // ... summed as two halves of three rows
 constexpr int BA_PT = 10;                 // per point: Vp (6), gp (3), its cost
-constexpr double BA_LAMBDA0 = 1e-3;       // S115: S24's damping start
-constexpr double BA_STEP_TOL = 1e-15;     // S115: S40's step tolerance
 
 // The workspace in doubles, every part a multiple of 16 bytes from a 16-byte aligned base: cp = cap rounded up to even;
 // X[2] (3 cp each, point i at 3 i), lin[2] ((10 + 18 Fm) cp each: point i's Vp, gp, cost at 10 i, then its W of free view f
@@ -107,66 +112,6 @@ __device__ __forceinline__ void observe(const Cam& k, const double (&P)[12], con
         o.cu[c] = fa * P[c] - a * P[6 + c];
         o.cv[c] = fb * P[3 + c] - b * P[6 + c];
     }
-}
-
-// S24's Cholesky of the damped 3 x 3 (H: entries j <= k, row-major)
-__device__ __forceinline__ bool chol3(const double (&H)[6], double lam, double (&L)[3][3])
-{
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double ajj = H[j * 3 - j * (j - 1) / 2];
-        double dd = ajj + lam * ajj;
-#pragma unroll
-        for (int q = 0; q < j; ++q) dd = fma(-L[j][q], L[j][q], dd);
-        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
-        L[j][j] = sqrt(dd);
-#pragma unroll
-        for (int i = j + 1; i < 3; ++i) {
-            double v = H[j * 3 - j * (j - 1) / 2 + (i - j)];
-#pragma unroll
-            for (int q = 0; q < j; ++q) v = fma(-L[i][q], L[j][q], v);
-            L[i][j] = v / L[j][j];
-        }
-    }
-    return true;
-}
-
-// L L^T x = b in S24's order
-__device__ __forceinline__ void solve3(const double (&L)[3][3], const double (&b)[3], double (&x)[3])
-{
-    double y[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double v = b[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) v = fma(-L[i][q], y[q], v);
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 2; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 3; ++q) v = fma(-L[q][i], x[q], v);
-        x[i] = v / L[i][i];
-    }
-}
-
-// S40 step 4: R' = C(d[0..2] / 2) R (Cayley), t' = t + d[3..5]
-__device__ __forceinline__ void update(const double* Rt, const double* d, double* out)
-{
-    const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-    const double cc = (h0 * h0 + h1 * h1) + h2 * h2;
-    const double s = 1.0 / (1.0 + cc), m = 1.0 - cc;
-    double C[9];
-    C[0] = (m + 2.0 * (h0 * h0)) * s; C[1] = (2.0 * (h0 * h1 - h2)) * s; C[2] = (2.0 * (h0 * h2 + h1)) * s;
-    C[3] = (2.0 * (h0 * h1 + h2)) * s; C[4] = (m + 2.0 * (h1 * h1)) * s; C[5] = (2.0 * (h1 * h2 - h0)) * s;
-    C[6] = (2.0 * (h0 * h2 - h1)) * s; C[7] = (2.0 * (h1 * h2 + h0)) * s; C[8] = (m + 2.0 * (h2 * h2)) * s;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 * r + c] = (C[3 * r] * Rt[c] + C[3 * r + 1] * Rt[3 + c]) + C[3 * r + 2] * Rt[6 + c];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[9 + i] = Rt[9 + i] + d[3 + i];
 }
 
 // The poses in LDS change only between passes, so the compiler would hoist their loads out of the point loops and hold 12
@@ -347,7 +292,7 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
 
     int cl = 0, cx = 0, iters = 0, accepted = 0;  // which linearisation and which X hold the current state
     linearise(s_in, wd + lay.X, wd + lay.lin, s_U[0]);
-    if (tid == 0) { s_st[ST_COST_IN] = s_st[ST_COST]; s_st[ST_CUR] = s_st[ST_COST]; s_st[ST_LAM] = BA_LAMBDA0; }
+    if (tid == 0) { s_st[ST_COST_IN] = s_st[ST_COST]; s_st[ST_CUR] = s_st[ST_COST]; s_st[ST_LAM] = LM_LAMBDA0; }
     __syncthreads();
 
     if (!few && a.max_iters > 0) {
@@ -364,7 +309,7 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                 double H[6], L[3][3];
 #pragma unroll
                 for (int e = 0; e < 6; ++e) H[e] = Lc[BA_PT * static_cast<size_t>(i) + e];
-                if (!chol3(H, lam, L)) { fail = 1; continue; }
+                if (!lm_factor<3>(H, lam, L)) { fail = 1; continue; }
                 for (int f = 0; f < F; ++f) {
                     if (!((ub >> s_fview[f]) & 1u)) continue;
                     const double* W = Lc + BA_PT * cp + 18 * (static_cast<size_t>(f) * cp + i);
@@ -373,7 +318,7 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                     for (int j = 0; j < 6; ++j) {
                         const double w[3] = {W[3 * j], W[3 * j + 1], W[3 * j + 2]};
                         double y[3];
-                        solve3(L, w, y);
+                        lm_subst<3>(L, w, y);
 #pragma unroll
                         for (int c = 0; c < 3; ++c) Y[3 * j + c] = y[c];
                     }
@@ -477,7 +422,7 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                 double H[6], L[3][3], r[3], dp[3];
 #pragma unroll
                 for (int e = 0; e < 6; ++e) H[e] = Lc[BA_PT * static_cast<size_t>(i) + e];
-                chol3(H, lam, L);              // succeeded above on the same numbers
+                lm_factor<3>(H, lam, L);              // succeeded above on the same numbers
 #pragma unroll
                 for (int c = 0; c < 3; ++c) r[c] = -Lc[BA_PT * static_cast<size_t>(i) + 6 + c];
                 for (int f = 0; f < F; ++f) {
@@ -490,7 +435,7 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                         for (int c = 0; c < 3; ++c) r[c] = fma(-W[3 * j + c], dj, r[c]);
                     }
                 }
-                solve3(L, r, dp);
+                lm_subst<3>(L, r, dp);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const double xc = Xc[3 * static_cast<size_t>(i) + c];
@@ -510,9 +455,9 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                 hmax = s_max[1][w] > hmax ? s_max[1][w] : hmax;
                 nonfin = s_max[2][w] > nonfin ? s_max[2][w] : nonfin;
             }
-            if (nonfin > 0.0 || !(dmax > BA_STEP_TOL * hmax)) break;
+            if (nonfin > 0.0 || !(dmax > LM_STEP_TOL * hmax)) break;
             // ---- steps 7-9: the trial poses, their linearisation, accept or reject
-            if (tid < F) update(s_cur[s_fview[tid]], s_d + 6 * tid, s_tr[s_fview[tid]]);
+            if (tid < F) pose_update(s_cur[s_fview[tid]], s_d + 6 * tid, s_tr[s_fview[tid]]);
             __syncthreads();
             linearise(s_tr, Xt, wd + lay.lin + (1 - cl) * lay.lin_size, s_U[1 - cl]);
             ++iters;

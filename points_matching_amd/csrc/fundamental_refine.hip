@@ -7,11 +7,16 @@
 // partial p of S23's fixed reduction order, walks the correspondences i = p, p + 512, ... of the view from global memory
 // and keeps its partial sums in fp64 registers (45 in the normal-matrix pass, 36 in the LM passes).  The 9 x 9 Jacobi
 // eigen-solve runs lane-parallel in wave 0 (homography_refine_core.hpp); the 3 x 3 Jacobi SVDs, the 7 x 7 Cholesky and
-// the Cayley update of each LM step run in thread 0, which leaves the model of the next pass in LDS for everyone.
+// the Cayley update of each LM step (lm_solve_n and cayley, lm_core.hpp) run in thread 0, which leaves the model of the
+// next pass in LDS for everyone.
 // Passes: sums + cost of F_in, centroid distances, normal matrix, cost of the refit, then the LM passes (one at the start
 // point, one per iteration) and the cost of the LM result.
 //
 // The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp) synchronise.
+#include "homography_refine_core.hpp"
+#include "lm_core.hpp"
+#include "ransac_fused_kernels.hpp"
+#include "refine_reduce.hpp"
 #include "twoview_refine_core.hpp"
 
 namespace pm_hrefine {
@@ -154,7 +159,7 @@ __device__ __forceinline__ void lm_model(const double* st, double* lc)
 __device__ __attribute__((noinline)) bool lm_step(const double* st, const double* d, double* tr, double* lc)
 {
     double C[9];
-    if (!(step_max<7>(d) > TV_STEP_TOL)) return false;
+    if (!(step_max<7>(d) > LM_STEP_TOL)) return false;
     cayley(d, C);
     rot3(C, st, tr);
     rot3(C, st + 3, tr + 3);
@@ -331,10 +336,10 @@ __global__ __launch_bounds__(HR_P) void fundamental_refine(pm_points_view v, con
         lm_pass();
         if (tid < FR_LM) s_jg[tid] = s_red[tid];
         double cur = s_red[FR_LM - 1];
-        double lam = TV_LAMBDA0;
+        double lam = LM_LAMBDA0;
         __syncthreads();
         for (int it = 0; it < max_iters; ++it) {
-            if (tid == 0) s_ok[2] = (lm_solve_n<7>(s_jg, lam, s_d) && lm_step(s_st, s_d, s_tr, s_lc)) ? 1 : 0;
+            if (tid == 0) [[clang::noinline]] s_ok[2] = (lm_solve_n<7>(s_jg, s_jg + 28, lam, s_d) && lm_step(s_st, s_d, s_tr, s_lc)) ? 1 : 0;
             __syncthreads();
             if (!s_ok[2]) break;
             lm_pass();

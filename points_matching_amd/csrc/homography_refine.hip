@@ -7,7 +7,8 @@
 // LDS), skips the ones the mask rejects and keeps its partial sums in fp64 registers (45 in the widest pass).  The
 // stride-halving tree runs its three cross-wave steps through LDS, HR_CH accumulators at a time, and its six in-wave
 // steps with cross-lane moves.  Between passes, every thread reads the sums back from LDS and takes the same control
-// decisions; the Jacobi eigen-solve runs lane-parallel in wave 0, the 8 x 8 Cholesky of each LM step in thread 0.
+// decisions; the Jacobi eigen-solve runs lane-parallel in wave 0, the 8 x 8 Cholesky of each LM step (S24's lm_solve_n,
+// lm_core.hpp) in thread 0.
 // Passes: sums + cost of H_in, centroid distances, normal matrix, cost of the refit, then the LM passes (one at the
 // start point, one per iteration).
 //
@@ -15,6 +16,7 @@
 // synchronise.
 #include "homography_core.hpp"
 #include "homography_refine_core.hpp"
+#include "lm_core.hpp"
 #include "ransac_fused_kernels.hpp"
 #include "refine_reduce.hpp"
 
@@ -141,9 +143,9 @@ __global__ __launch_bounds__(HR_P) void homography_refine(pm_points_view v, cons
             }
             __syncthreads();
         }
-        double lam = HR_LAMBDA0;
+        double lam = LM_LAMBDA0;
         for (int it = 0; it < max_iters; ++it) {
-            if (tid == 0) s_jok = lm_solve(s_jtjg, lam, s_d) ? 1 : 0;
+            if (tid == 0) [[clang::noinline]] s_jok = lm_solve_n<8>(s_jtjg, s_jtjg + 36, lam, s_d) ? 1 : 0;
             __syncthreads();
             if (!s_jok) break;
             double dmax = 0.0, hmax = 1.0;
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(HR_P) void homography_refine(pm_points_view v, cons
                 ht[i] = hi + di;
             }
             ht[8] = 1.0;
-            if (!(dmax > HR_STEP_TOL * hmax)) break;
+            if (!(dmax > LM_STEP_TOL * hmax)) break;
             pass<HR_LM>(v, s_offs, n, mask, tid, s_x, s_red,
                         [&](double (&a)[HR_LM], double x1, double y1, double x2, double y2) { lm_term(a, ht, x1, y1, x2, y2); });
             ++iters;

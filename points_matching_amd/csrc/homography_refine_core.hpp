@@ -1,13 +1,11 @@
 // homography_refine_core.hpp — device arithmetic of the refinement of a robust homography on its inliers (docs/SPEC.md
 // S23 least-squares DLT refit, S24 Levenberg-Marquardt on the forward transfer error, S25 result), the step
-// cv::findHomography runs after its RANSAC loop.  Built with -ffp-contract=off like every unit: the only fused
-// multiply-adds are the explicit fma() calls, so tests/homography_refine_ref.c (the CPU restatement) reproduces the bits.
-// Sums over correspondences follow S23's fixed order (HR_P partials, stride-halving tree), independent of the grid.
+// cv::findHomography runs after its RANSAC loop: the per-correspondence terms of the passes and S23's 9 x 9 Jacobi on a
+// wave (which fundamental_refine.hip uses too).  S24's damped Cholesky solve is lm_solve_n in lm_core.hpp.  Built with
+// -ffp-contract=off like every unit: the only fused multiply-adds are the explicit fma() calls, so
+// tests/homography_refine_ref.c (the CPU restatement) reproduces the bits.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <cstdint>
-#include "pm.h"
-#include "refine_reduce.hpp"
 
 namespace pm_hrefine {
 
@@ -15,9 +13,7 @@ constexpr int HR_NORMAL = 45;             // unique entries of the 9 x 9 normal 
 constexpr int HR_LM = 45;                 // 36 of J^T J, 8 of J^T r, the cost
 constexpr int HR_SWEEPS = 16;             // S23 Jacobi sweep cap
 constexpr double HR_JACOBI_SKIP = 1e-17;  // S23: rotation (p, q) skipped unless |a_pq| > HR_JACOBI_SKIP * trace(M)
-constexpr double HR_LAMBDA0 = 1e-3;       // S24 initial damping
 constexpr double HR_MIN_H8 = 1e-8;        // S24: LM needs |H[8]| >= this (H of unit norm)
-constexpr double HR_STEP_TOL = 1e-15;     // S24: stop when max|delta| <= HR_STEP_TOL * max(1, max|h|)
 
 // S24: squared forward transfer error of one correspondence under the 9 entries of h.
 __device__ __forceinline__ double cost_term(const double (&h)[9], double x, double y, double xp, double yp)
@@ -144,46 +140,6 @@ __device__ __forceinline__ bool jacobi_min_wave(const double* m45, int lane, dou
     for (int j = 1; j < 9; ++j)
         if (mi == j) vm = V[j];
     hn = vm;
-    return true;
-}
-
-// S24: (J^T J + lam * diag(J^T J)) d = -g by an 8 x 8 Cholesky in a fixed order.  jtjg: 36 upper-triangle entries of
-// J^T J (row-major) then the 8 of g = J^T r; d: 8 doubles (LDS).  false = not positive definite.  Not inlined: one
-// thread runs it between two passes, and inlined into the LM loop it pushes the kernel past 256 VGPRs.
-__device__ __attribute__((noinline)) bool lm_solve(const double* jtjg, double lam, double* d)
-{
-    // A[i][j] (i >= j) is read from the packed upper triangle as needed: jtjg[j*8 - j*(j-1)/2 + (i - j)]
-    double L[8][8], y[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const double ajj = jtjg[j * 8 - j * (j - 1) / 2];
-        double dd = ajj + lam * ajj;
-#pragma unroll
-        for (int k = 0; k < j; ++k) dd = fma(-L[j][k], L[j][k], dd);
-        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
-        L[j][j] = sqrt(dd);
-#pragma unroll
-        for (int i = j + 1; i < 8; ++i) {
-            double v = jtjg[j * 8 - j * (j - 1) / 2 + (i - j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
-            L[i][j] = v / L[j][j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        double v = -jtjg[36 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v = fma(-L[i][k], y[k], v);
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 8; ++k) v = fma(-L[k][i], d[k], v);
-        d[i] = v / L[i][i];
-    }
     return true;
 }
 

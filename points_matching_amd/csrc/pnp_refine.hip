@@ -6,12 +6,14 @@
 // One workgroup of HR_P = 512 threads, built on refine_reduce.hpp as homography_refine.hip is: thread p owns partial p of
 // S23's fixed reduction order and walks the correspondences i = p, p + 512, ... from global memory, keeping its 28 fp64
 // partial sums (21 of J^T J, 6 of J^T r, the cost) in registers; the stride-halving tree closes every pass.  The 6 x 6
-// Cholesky of each step runs in thread 0; every thread then applies the same step (a Cayley rotation update: no
-// transcendental function) and the next pass runs at the trial pose.
+// Cholesky of each step runs in thread 0 (S24's lm_solve_n, lm_core.hpp); every thread then applies the same step (S40's
+// Cayley rotation update, pose_update in lm_core.hpp: no transcendental function) and the next pass runs at the trial pose.
 //
 // The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp)
 // synchronise.
-#include "pnp_core.hpp"
+#include "essential_core.hpp"
+#include "lm_core.hpp"
+#include "ransac_fused_kernels.hpp"
 #include "refine_reduce.hpp"
 
 namespace pm_hrefine {
@@ -22,8 +24,6 @@ using pm_ransac::view_count1;
 
 constexpr int PR_NJ = 21;                 // J^T J entries j <= k, row-major
 constexpr int PR_LM = PR_NJ + 6 + 1;      // + J^T r + cost
-constexpr double PR_LAMBDA0 = 1e-3;       // S40: S24's damping start
-constexpr double PR_STEP_TOL = 1e-15;     // S40: stop when max|d| <= PR_STEP_TOL * max(1, max|t|)
 
 struct Pt {
     double x, y, z, u, v;
@@ -77,61 +77,6 @@ __device__ __forceinline__ void lm_term(double (&a)[PR_LM], const Cam& k, const 
 #pragma unroll
     for (int j = 0; j < 6; ++j) a[PR_NJ + j] = a[PR_NJ + j] + fma(ju[j], ru, jv[j] * rv);
     a[PR_NJ + 6] = a[PR_NJ + 6] + fma(ru, ru, rv * rv);
-}
-
-// S40 step 3: Cholesky of (JtJ + lam diag JtJ) d = -g (thread 0)
-__device__ __attribute__((noinline)) bool lm_solve6(const double* jtjg, double lam, double* d)
-{
-    double L[6][6], y[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const double ajj = jtjg[j * 6 - j * (j - 1) / 2];
-        double dd = ajj + lam * ajj;
-#pragma unroll
-        for (int q = 0; q < j; ++q) dd = fma(-L[j][q], L[j][q], dd);
-        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
-        L[j][j] = sqrt(dd);
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = jtjg[j * 6 - j * (j - 1) / 2 + (i - j)];
-#pragma unroll
-            for (int q = 0; q < j; ++q) v = fma(-L[i][q], L[j][q], v);
-            L[i][j] = v / L[j][j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = -jtjg[PR_NJ + i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) v = fma(-L[i][q], y[q], v);
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 6; ++q) v = fma(-L[q][i], d[q], v);
-        d[i] = v / L[i][i];
-    }
-    return true;
-}
-
-// S40 step 4: R' = C(d[0..2] / 2) R (Cayley), t' = t + d[3..5]
-__device__ __forceinline__ void update(const double* Rt, const double* d, double (&out)[12])
-{
-    const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-    const double cc = (h0 * h0 + h1 * h1) + h2 * h2;
-    const double s = 1.0 / (1.0 + cc), m = 1.0 - cc;
-    double C[9];
-    C[0] = (m + 2.0 * (h0 * h0)) * s; C[1] = (2.0 * (h0 * h1 - h2)) * s; C[2] = (2.0 * (h0 * h2 + h1)) * s;
-    C[3] = (2.0 * (h0 * h1 + h2)) * s; C[4] = (m + 2.0 * (h1 * h1)) * s; C[5] = (2.0 * (h1 * h2 - h0)) * s;
-    C[6] = (2.0 * (h0 * h2 - h1)) * s; C[7] = (2.0 * (h1 * h2 + h0)) * s; C[8] = (m + 2.0 * (h2 * h2)) * s;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[3 * r + c] = (C[3 * r] * Rt[c] + C[3 * r + 1] * Rt[3 + c]) + C[3 * r + 2] * Rt[6 + c];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) out[9 + i] = Rt[9 + i] + d[3 + i];
 }
 
 // v: one-part view, xy1 = world points (3 floats each), xy2 = pixels
@@ -194,9 +139,9 @@ __global__ __launch_bounds__(HR_P) void pnp_refine(pm_points_view v, Cam k, cons
         if (tid < PR_LM) s_jg[tid] = s_red[tid];
         if (tid < 12) s_cur[tid] = in[tid];
         __syncthreads();
-        double lam = PR_LAMBDA0;
+        double lam = LM_LAMBDA0;
         for (int it = 0; it < max_iters; ++it) {
-            if (tid == 0) s_ok = lm_solve6(s_jg, lam, s_d) ? 1 : 0;
+            if (tid == 0) [[clang::noinline]] s_ok = lm_solve_n<6>(s_jg, s_jg + PR_NJ, lam, s_d) ? 1 : 0;
             __syncthreads();
             if (!s_ok) break;
             double dmax = 0.0, hmax = 1.0;
@@ -206,9 +151,9 @@ __global__ __launch_bounds__(HR_P) void pnp_refine(pm_points_view v, Cam k, cons
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 if (!(fabs(s_cur[9 + i]) <= hmax)) hmax = fabs(s_cur[9 + i]);
-            if (!(dmax > PR_STEP_TOL * hmax)) break;
+            if (!(dmax > LM_STEP_TOL * hmax)) break;
             double tr[12];
-            update(s_cur, s_d, tr);
+            pose_update(s_cur, s_d, tr);
             lm_pass(tr);
             ++iters;
             const double ct = s_red[PR_LM - 1];

@@ -6,11 +6,14 @@
 // One workgroup of HR_P = 512 threads, built on refine_reduce.hpp as pnp_refine.hip is: thread p owns partial p of S23's
 // fixed reduction order and walks the correspondences i = p, p + 512, ... of the view from global memory, keeping its 21
 // fp64 partial sums (15 of J^T J, 5 of J^T r, the cost) in registers; the stride-halving tree closes every pass.  The
-// 5 x 5 Cholesky and the update of each step run in thread 0, which leaves the trial pose, its E and its tangent basis in
-// LDS for everyone.
+// 5 x 5 Cholesky and the update of each step (lm_solve_n, cayley and left_rot of lm_core.hpp) run in thread 0, which leaves
+// the trial pose, its E and its tangent basis in LDS for everyone.
 //
 // The launch keeps no per-call state, so the device form may be captured; the host forms (estimators.cpp) synchronise.
 #include "essential_core.hpp"
+#include "lm_core.hpp"
+#include "ransac_fused_kernels.hpp"
+#include "refine_reduce.hpp"
 #include "twoview_refine_core.hpp"
 
 namespace pm_hrefine {
@@ -86,12 +89,9 @@ __device__ __attribute__((noinline)) bool lm_start(const double* in, double* mo)
 __device__ __attribute__((noinline)) bool lm_step(const double* cur, const double* d, double* mo)
 {
     double C[9], tr[12], q[3];
-    if (!(step_max<5>(d) > TV_STEP_TOL)) return false;
+    if (!(step_max<5>(d) > LM_STEP_TOL)) return false;
     cayley(d, C);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) tr[3 * r + c] = (C[3 * r] * cur[c] + C[3 * r + 1] * cur[3 + c]) + C[3 * r + 2] * cur[6 + c];
+    left_rot(C, cur, tr);
 #pragma unroll
     for (int i = 0; i < 3; ++i) q[i] = fma(d[4], cur[24 + i], fma(d[3], cur[21 + i], cur[9 + i]));
     const double iq = 1.0 / sqrt(dot3f(q, q));
@@ -223,9 +223,9 @@ __global__ __launch_bounds__(HR_P) void pose_refine(pm_points_view v, Cam k, con
         lm_pass(s_cur);
         if (tid < PO_LM) s_jg[tid] = s_red[tid];
         __syncthreads();
-        double lam = TV_LAMBDA0;
+        double lam = LM_LAMBDA0;
         for (int it = 0; it < max_iters; ++it) {
-            if (tid == 0) s_ok = (lm_solve_n<5>(s_jg, lam, s_d) && lm_step(s_cur, s_d, s_tr)) ? 1 : 0;
+            if (tid == 0) [[clang::noinline]] s_ok = (lm_solve_n<5>(s_jg, s_jg + 15, lam, s_d) && lm_step(s_cur, s_d, s_tr)) ? 1 : 0;
             __syncthreads();
             if (!s_ok) break;
             lm_pass(s_tr);

@@ -8,7 +8,7 @@
 // point contributes two zero rows, which change no bit of any sum: S94).  Pixels are coalesced float2 loads from the
 // view-major arrays.  The poses are wave-uniform: the workgroup copies them (and the camera centres of S96) into LDS once
 // and every lane reads them from there, a broadcast read.  All arithmetic is lane-local fp64, unfused except the explicit
-// fma()s, so tests/triangulate_ref.c reproduces the bits.  *d_n_good is a ballot count per wave and one integer atomic per
+// fma()s, so tests/triangulate_ref.c reproduces the bits; the 3 x 3 damped Cholesky of S95 is S24's lm_solve_n (lm_core.hpp).  *d_n_good is a ballot count per wave and one integer atomic per
 // wave after a hipMemsetAsync on the stream: an integer sum, so the order does not matter.
 //
 // The launch keeps no per-call state, so the device form may be captured; the host form stages its rows through
@@ -16,17 +16,19 @@
 #include <cmath>
 
 #include "essential_core.hpp"
+#include "lm_core.hpp"
 #include "pm_common.hpp"
 
 namespace pm_tri {
 namespace {
 
 using pm_essential::Cam;
+using pm_hrefine::LM_LAMBDA0;
+using pm_hrefine::LM_STEP_TOL;
+using pm_hrefine::lm_solve_n;
 
 constexpr int TR_THREADS = 256;
 constexpr int TR_MAX_WG = 2048;
-constexpr double TR_LAMBDA0 = 1e-3;       // S95: S24's damping start
-constexpr double TR_STEP_TOL = 1e-15;     // S95: S40's step tolerance
 
 struct Args {
     const float* uv[PM_TRI_MAX_VIEWS];
@@ -94,43 +96,6 @@ __device__ __forceinline__ void lm_pass(const Cam& k, const double* sP, const fl
         o.cost = o.cost + fma(ru, ru, rv * rv);
     }
     if (!o.depth_ok) o.cost = __builtin_inf();
-}
-
-// S95: Cholesky of (H + lam diag H) d = -g in S24's form, 3 parameters; H holds the entries j <= k, row-major
-__device__ __forceinline__ bool lm_solve3(const double (&H)[6], const double (&g)[3], double lam, double (&d)[3])
-{
-    double L[3][3], y[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double ajj = H[j * 3 - j * (j - 1) / 2];
-        double dd = ajj + lam * ajj;
-#pragma unroll
-        for (int q = 0; q < j; ++q) dd = fma(-L[j][q], L[j][q], dd);
-        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
-        L[j][j] = sqrt(dd);
-#pragma unroll
-        for (int i = j + 1; i < 3; ++i) {
-            double v = H[j * 3 - j * (j - 1) / 2 + (i - j)];
-#pragma unroll
-            for (int q = 0; q < j; ++q) v = fma(-L[i][q], L[j][q], v);
-            L[i][j] = v / L[j][j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) v = fma(-L[i][q], y[q], v);
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 2; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 3; ++q) v = fma(-L[q][i], d[q], v);
-        d[i] = v / L[i][i];
-    }
-    return true;
 }
 
 template <int V>
@@ -213,18 +178,18 @@ __global__ __launch_bounds__(TR_THREADS) void triangulate_kernel(Args a)
                 Pass cur;
                 lm_pass<V>(a.k, s_P, pix, obs, X, cur);
                 if (cur.depth_ok && a.max_iters > 0) {
-                    double lam = TR_LAMBDA0;
+                    double lam = LM_LAMBDA0;
                     for (int it = 0; it < a.max_iters; ++it) {
                         double d[3];
                         pose_fence();
-                        if (!lm_solve3(cur.H, cur.g, lam, d)) break;
+                        [[clang::always_inline]] if (!lm_solve_n<3>(cur.H, cur.g, lam, d)) break;
                         double dmax = 0.0, hmax = 1.0;
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {          // NaN propagates into dmax and stops the loop
                             if (!(fabs(d[c]) <= dmax)) dmax = fabs(d[c]);
                             if (!(fabs(X[c]) <= hmax)) hmax = fabs(X[c]);
                         }
-                        if (!(dmax > TR_STEP_TOL * hmax)) break;
+                        if (!(dmax > LM_STEP_TOL * hmax)) break;
                         const double Xt[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
                         Pass tr;
                         lm_pass<V>(a.k, s_P, pix, obs, Xt, tr);

@@ -1,17 +1,14 @@
 // twoview_refine_core.hpp — device arithmetic shared by the two refinements of a two-view model on its inliers: the
 // fundamental matrix (fundamental_refine.hip, docs/SPEC.md S43-S45) and the calibrated relative pose (pose_refine.hip,
 // S46-S47).  Both minimise the Sampson distance by Levenberg-Marquardt over a minimal parametrisation whose steps are
-// Cayley rotations (S40 step 4), so this header holds the Sampson residual with its gradient in the 9 model entries, the
-// chain rule of a left rotation, the LM sums and S24's damped Cholesky at N parameters.  Built with -ffp-contract=off
-// like every unit: the only fused multiply-adds are the explicit fma() calls, so tests/twoview_refine_ref.c (the CPU
-// restatement) reproduces the bits.
+// Cayley rotations (S40 step 4).  This header holds what is two-view: the Sampson residual with its gradient in the 9
+// model entries and the chain rule of a left rotation; the LM sums, S24's damped Cholesky at N parameters and the Cayley
+// step are in lm_core.hpp.  Built with -ffp-contract=off like every unit: the only fused multiply-adds are the explicit
+// fma() calls, so tests/twoview_refine_ref.c (the CPU restatement) reproduces the bits.
 #pragma once
-#include "homography_refine_core.hpp"
+#include "lm_core.hpp"
 
 namespace pm_hrefine {
-
-constexpr double TV_LAMBDA0 = 1e-3;       // S24's damping start
-constexpr double TV_STEP_TOL = 1e-15;     // stop when max|d| <= this (every parameter is of unit scale)
 
 __device__ __forceinline__ double dot3f(const double* a, const double* b) { return fma(a[0], b[0], fma(a[1], b[1], a[2] * b[2])); }
 
@@ -71,87 +68,6 @@ __device__ __forceinline__ void left_rot_grad(const double (&G)[9], const double
     n[0] = N(2, 1) - N(1, 2);
     n[1] = N(0, 2) - N(2, 0);
     n[2] = N(1, 0) - N(0, 1);
-}
-
-// The LM sums of one inlier: N (N + 1) / 2 of J^T J (j <= k, row-major), N of J^T r, the cost
-template <int N>
-__device__ __forceinline__ void lm_sums(double (&acc)[N * (N + 1) / 2 + N + 1], const double (&J)[N], double r)
-{
-    int e = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-#pragma unroll
-        for (int k = j; k < N; ++k, ++e) acc[e] = acc[e] + J[j] * J[k];
-#pragma unroll
-    for (int j = 0; j < N; ++j, ++e) acc[e] = acc[e] + J[j] * r;
-    acc[e] = acc[e] + r * r;
-}
-
-// S24 step 4 at N parameters: (J^T J + lam * diag(J^T J)) d = -g by Cholesky in a fixed order.  jtjg: the packed upper
-// triangle, then g (LDS); d: N doubles.  false = not positive definite.  Runs in one thread between two passes.
-template <int N>
-__device__ __attribute__((noinline)) bool lm_solve_n(const double* jtjg, double lam, double* d)
-{
-    double L[N][N], y[N];
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        const double ajj = jtjg[j * N - j * (j - 1) / 2];
-        double dd = ajj + lam * ajj;
-#pragma unroll
-        for (int k = 0; k < j; ++k) dd = fma(-L[j][k], L[j][k], dd);
-        if (!(dd > 0.0) || !(dd < __builtin_inf())) return false;
-        L[j][j] = sqrt(dd);
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = jtjg[j * N - j * (j - 1) / 2 + (i - j)];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
-            L[i][j] = v / L[j][j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = -jtjg[N * (N + 1) / 2 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v = fma(-L[i][k], y[k], v);
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k) v = fma(-L[k][i], d[k], v);
-        d[i] = v / L[i][i];
-    }
-    return true;
-}
-
-// max |d_i|; a NaN propagates
-template <int N>
-__device__ __forceinline__ double step_max(const double* d)
-{
-    double dmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-        if (!(fabs(d[i]) <= dmax)) dmax = fabs(d[i]);
-    return dmax;
-}
-
-// S40 step 4: C = Cayley(d / 2)
-__device__ __forceinline__ void cayley(const double* d, double (&C)[9])
-{
-    const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-    const double cc = (h0 * h0 + h1 * h1) + h2 * h2;
-    const double s = 1.0 / (1.0 + cc), m = 1.0 - cc;
-    C[0] = (m + 2.0 * (h0 * h0)) * s; C[1] = (2.0 * (h0 * h1 - h2)) * s; C[2] = (2.0 * (h0 * h2 + h1)) * s;
-    C[3] = (2.0 * (h0 * h1 + h2)) * s; C[4] = (m + 2.0 * (h1 * h1)) * s; C[5] = (2.0 * (h1 * h2 - h0)) * s;
-    C[6] = (2.0 * (h0 * h2 - h1)) * s; C[7] = (2.0 * (h1 * h2 + h0)) * s; C[8] = (m + 2.0 * (h2 * h2)) * s;
-}
-
-__device__ __forceinline__ void rot3(const double (&C)[9], const double* v, double* o)
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) o[r] = (C[3 * r] * v[0] + C[3 * r + 1] * v[1]) + C[3 * r + 2] * v[2];
 }
 
 }  // namespace pm_hrefine
