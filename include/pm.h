@@ -83,7 +83,7 @@ int  pm_device_download(pm_ctx* ctx, void* dst, const void* d_src, size_t bytes)
  * "ransac_fused", "ransac_finish", "ransac_solve", "ransac_score", "ransac_select", "ransac_final", "lmeds_solve", "lmeds_median",
  * "lmeds_final", "fm_count", "flann_search", "ransac_h_fused", "homography_refine", "ransac_a_fused", "affine_refine",
  * "essential_solve", "ransac_e_fused", "recover_pose", "fundamental_refine", "pose_refine", "feat_blur", "feat_decimate",
- * "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather".
+ * "feat_extrema", "feat_rank", "feat_describe", "feat_compact", "feat_gather", "pose_graph", "pgo_move_points".
  * On a capturing stream no event is recorded, whatever enable says: a call that is captured, and every replay of the
  * graph, adds nothing to pm_ctx_timing_get (time a replay with events of your own around the graph launch). */
 int  pm_ctx_timing_enable(pm_ctx* ctx, int enable);
@@ -93,7 +93,8 @@ int  pm_ctx_timing_get(pm_ctx* ctx, const char* kernel, double* mean_ms, int* la
  * HIP graph on a capturing stream, and the graph replayed after the rows and the device-side counts in the recorded
  * buffers have changed: pm_ransac_run_dev, pm_ransac_{homography,affine,essential,pnp,align3d}_run_dev, the six
  * *_refine_dev calls, pm_recover_pose_dev, pm_triangulate_dev, pm_bundle_adjust_dev, pm_gather_pnp_dev,
- * pm_gather_align3d_dev and pm_transform_points3_dev (pm_transform_points_dev belongs to the image family and refuses capture like the rest of it).
+ * pm_gather_align3d_dev, pm_transform_points3_dev, pm_pose_graph_optimize_dev and pm_pgo_move_points_dev
+ * (pm_transform_points_dev belongs to the image family and refuses capture like the rest of it).
  *   Before recording: the *_run_dev calls take workgroup slots, candidate buffers and (E) a normalised copy from the
  *     context's scratch arena, and a context's first such call allocates the arrival words.  Neither can happen on a
  *     capturing stream, so make ONE EAGER CALL of the same or a larger shape (capacity, id range, PM_OPT_RANSAC_WG_IDS)
@@ -1038,6 +1039,81 @@ int pm_bundle_adjust_dev(pm_ctx* ctx, const pm_tri_views* views, const pm_camera
  * used may be NULL.  One staged block (the workspace inside it), the device form, one synchronisation. */
 int pm_bundle_adjust(pm_ctx* ctx, const float* const* uv, const double* const* Rt, int n_views, int n, const pm_camera* K,
                      const pm_ba_params* p, double* Rt_out, float* xyz, uint8_t* used, pm_ba_info* info);
+
+/* ---- pose-graph optimisation: the last step of a loop closer (ORB-SLAM's OptimizeEssentialGraph, a g2o graph of EdgeSim3 /
+ * EdgeSE3, GTSAM's BetweenFactor) — docs/SPEC.md S118-S123.  pm_bowdb_query* proposes a loop, pm_bf_match_guided_* verifies it,
+ * pm_ransac_align3d* + pm_align3d_refine* measure the transform between the two maps; this call spreads that loop error over
+ * the keyframes, and pm_pgo_move_points* moves the map rows with the keyframes they hang on.  Node i of n_nodes is a pose of 13
+ * doubles in pm_ransac_align3d's layout (R row-major, t, s) that takes world points to frame i, x_i = s_i R_i X + t_i;
+ * fixed[i] != 0 holds it.  Edge e joins the nodes ab[2e] = a and ab[2e+1] = b (int32) with a measurement Z_e of 13 doubles
+ * that takes frame-a coordinates to frame-b coordinates, x_b = s_z R_z x_a + t_z — exactly what pm_align3d_refine_dev leaves
+ * in d_T_out when xyz1 are points in frame a and xyz2 the same points in frame b, so that call can write row e of the E x 13
+ * array directly — and three square-root weights w[3e .. 3e+2] = (w_r, w_t, w_s) >= 0 of its rotation, translation and scale
+ * residuals.  With D = P_b P_a^-1 the residual is (w_r rho, w_t (t_D - t_z), w_s (sigma - 1/sigma)/2): rho the Cayley vector
+ * of R_z^T R_D (2 tan(angle/2) about the axis), sigma = s_D / s_z; the cost is the sum of its squares over the used edges.
+ * PM_PGO_SIM3 moves 7 parameters per free node; PM_PGO_RIGID moves 6, every s keeps its input bits and the scale residual
+ * does not exist.  Levenberg-Marquardt with S24's damping and acceptance (the accepted cost only falls); each step's normal
+ * equations are solved by conjugate gradients preconditioned with the nodes' damped diagonal blocks, at most cg_iters
+ * iterations or until the preconditioned residual has fallen to cg_tol^2 of its start.  The used set is decided once, at the
+ * start: edge e is used iff 0 <= a, b < n_nodes, a != b, every value of Z_e, its weights and both poses is finite, the three
+ * scales are > 0, at least one of the two nodes is not fixed, and the rotation residual is away from its singularity at a half
+ * turn (1 + tr(R_z^T R_D) > 2^-10).  A free node touched by no used edge is held for the run.  One launch of one workgroup: a
+ * latency design (loop closing is rare and runs in the background). */
+#define PM_PGO_MAX_NODES 16384
+#define PM_PGO_MAX_EDGES 131072
+enum { PM_PGO_RIGID = 0, PM_PGO_SIM3 = 1 };
+
+typedef struct pm_pgo_params {
+    int32_t model;      /* PM_PGO_RIGID or PM_PGO_SIM3 */
+    int32_t max_iters;  /* [0, 100]; 0 = evaluate only (cost_in, the used set), nothing moves */
+    int32_t cg_iters;   /* [1, 1000]: conjugate-gradient iterations per step at most */
+    int32_t flags;      /* 0 */
+    double  cg_tol;     /* finite, in [0, 1): stop a solve when r.z <= cg_tol^2 * (r.z at its start); 0 = run cg_iters */
+    int32_t reserved, reserved2;   /* 0 */
+} pm_pgo_params;
+
+typedef struct pm_pgo_info {
+    double  cost_in, cost_out;   /* sum of squared weighted residuals over the used edges */
+    int32_t n_edges_used, n_nodes_free, iters, accepted, cg_total, status;
+} pm_pgo_info;
+
+/* Bytes of device workspace pm_pose_graph_optimize_dev needs: pure host arithmetic (no context, no device), a multiple of
+ * 16, never decreasing in n_nodes or n_edges; 0 for n_nodes outside [2, PM_PGO_MAX_NODES], n_edges outside
+ * [0, PM_PGO_MAX_EDGES] or a model that is not PM_PGO_*.  1 745 bytes per edge and 1 281 per node (SIM3). */
+size_t pm_pose_graph_workspace(int n_nodes, int n_edges, int model);
+/* Device form.  d_pose_in / d_pose_out: n_nodes x 13 doubles, d_pose_out may be d_pose_in (every pose is read before any is
+ * written); d_fixed: n_nodes bytes; d_edge_ab: cap_edges x 2 int32; d_edge_Z: cap_edges x 13 doubles; d_edge_w: cap_edges x 3
+ * doubles; the edge count is *d_n_edges clamped to [0, cap_edges] (NULL: cap_edges), rows at or beyond it are neither read nor
+ * written.  d_edge_used (may be NULL): one byte per edge below the count, 1 = used.  d_work: work_bytes >=
+ * pm_pose_graph_workspace(n_nodes, cap_edges, model) of device memory the call may scribble on (no alignment asked for).
+ * *d_info: the costs, the used edges, the free nodes that a used edge touches, iters = trial evaluations, accepted =
+ * accepted ones, cg_total = conjugate-gradient iterations over all steps, status 0 = at least one step accepted; 1 = nothing
+ * improved (every pose equals its input bit for bit; max_iters = 0 ends here); 2 = not enough data (no used edge, or no fixed
+ * node: poses equal inputs, cost_out = cost_in).  Held nodes keep their input bits in every case.  Data outcomes are reported
+ * there only and the return value stays PM_OK.  PM_E_INVALID: a null context, params, d_info or array other than d_n_edges
+ * and d_edge_used, n_nodes < 2, cap_edges < 0, a model that is not PM_PGO_*, max_iters outside [0, 100], cg_iters outside
+ * [1, 1000], cg_tol not finite or outside [0, 1), non-zero flags or reserved, work_bytes too small.  PM_E_UNSUPPORTED: n_nodes >
+ * PM_PGO_MAX_NODES or cap_edges > PM_PGO_MAX_EDGES.  In every refusal nothing is written.  No per-call state and no
+ * allocation: the call may be captured. */
+int pm_pose_graph_optimize_dev(pm_ctx* ctx, const double* d_pose_in, int n_nodes, const uint8_t* d_fixed, const int32_t* d_edge_ab,
+                               const double* d_edge_Z, const double* d_edge_w, const int32_t* d_n_edges, int cap_edges,
+                               const pm_pgo_params* p, double* d_pose_out, uint8_t* d_edge_used, void* d_work, size_t work_bytes,
+                               pm_pgo_info* d_info);
+/* Host in, host out over n_edges edges; edge_used may be NULL.  One staged block (the workspace inside it), the device
+ * form, one synchronisation. */
+int pm_pose_graph_optimize(pm_ctx* ctx, const double* pose_in, int n_nodes, const uint8_t* fixed, const int32_t* edge_ab,
+                           const double* edge_Z, const double* edge_w, int n_edges, const pm_pgo_params* p, double* pose_out,
+                           uint8_t* edge_used, pm_pgo_info* info);
+/* The step a loop closer runs after the graph (S123): map row i, anchored to keyframe k = d_anchor[i], moves with it,
+ * X' = P_new,k^-1 (P_old,k X): fp64 with one rounding to f32.  A row with a non-finite input or result, a non-finite pose of
+ * its anchor or an anchor outside [0, n_nodes) becomes three quiet NaNs (S101's and pm_gather_pnp_dev's convention).  Rows
+ * [0, n), n = *d_n clamped to [0, cap] (d_n NULL: cap); rows beyond are not written; d_out may be d_xyz; one launch, no
+ * per-call state.  Statuses: PM_E_INVALID (null pointer, null ctx, negative size), size 0 -> PM_E_UNSUPPORTED.
+ * pm_pgo_move_points: the blocking host form. */
+int pm_pgo_move_points_dev(pm_ctx* ctx, const double* d_pose_old, const double* d_pose_new, int n_nodes, const int32_t* d_anchor,
+                           const float* d_xyz, const int32_t* d_n, int cap, float* d_out);
+int pm_pgo_move_points(pm_ctx* ctx, const double* pose_old, const double* pose_new, int n_nodes, const int32_t* anchor,
+                       const float* xyz, int n, float* out);
 
 /* ---- 7-point + LMedS: what the reference's call literally selects -----------------
  * cv::findFundamentalMat(..., CV_FM_7POINT) with more than 7 points runs OpenCV 2.4's least-median

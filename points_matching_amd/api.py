@@ -66,6 +66,8 @@ EXPORTS = [
     "pm_ransac_pnp", "pm_ransac_pnp_from_hyp", "pm_ransac_pnp_run_dev", "pm_pnp_refine", "pm_pnp_refine_dev",
     "pm_solve_pnp_ransac", "pm_gather_pnp_dev", "pm_triangulate_dev", "pm_triangulate",
     "pm_bundle_adjust_workspace", "pm_bundle_adjust_dev", "pm_bundle_adjust",
+    "pm_pose_graph_workspace", "pm_pose_graph_optimize_dev", "pm_pose_graph_optimize", "pm_pgo_move_points_dev",
+    "pm_pgo_move_points",
     "pm_ransac_align3d", "pm_ransac_align3d_from_hyp", "pm_ransac_align3d_run_dev", "pm_align3d_refine",
     "pm_align3d_refine_dev", "pm_estimate_align3d", "pm_transform_points3_dev", "pm_transform_points3",
     "pm_gather_align3d_dev",
@@ -337,6 +339,37 @@ def bundle_adjust_workspace(n_views, cap):
     return int(lib().pm_bundle_adjust_workspace(n_views, cap))
 
 
+PM_PGO_RIGID, PM_PGO_SIM3 = 0, 1
+PM_PGO_MAX_NODES, PM_PGO_MAX_EDGES = 16384, 131072
+
+
+class PgoParams(C.Structure):
+    """pm_pgo_params (include/pm.h, SPEC S118-S123); pgo_params() fills it."""
+    _fields_ = [("model", C.c_int32), ("max_iters", C.c_int32), ("cg_iters", C.c_int32), ("flags", C.c_int32),
+                ("cg_tol", C.c_double), ("reserved", C.c_int32), ("reserved2", C.c_int32)]
+
+
+class PgoInfo(C.Structure):
+    """pm_pgo_info (include/pm.h): costs over the used edges, counts, status 0/1/2."""
+    _fields_ = [("cost_in", C.c_double), ("cost_out", C.c_double), ("n_edges_used", C.c_int32), ("n_nodes_free", C.c_int32),
+                ("iters", C.c_int32), ("accepted", C.c_int32), ("cg_total", C.c_int32), ("status", C.c_int32)]
+
+
+PGO_INFO_DTYPE = np.dtype([("cost_in", "<f8"), ("cost_out", "<f8"), ("n_edges_used", "<i4"), ("n_nodes_free", "<i4"),
+                           ("iters", "<i4"), ("accepted", "<i4"), ("cg_total", "<i4"), ("status", "<i4")])   # the same record, 40 bytes
+
+
+def pgo_params(model=PM_PGO_SIM3, max_iters=10, cg_iters=50, cg_tol=1e-6, flags=0):
+    """model: PM_PGO_SIM3 (7 parameters per node) or PM_PGO_RIGID (6, scales untouched); max_iters 0 only evaluates; cg_iters
+    bounds the conjugate-gradient iterations of one step, cg_tol its relative stop (0: run them all)."""
+    return PgoParams(model, max_iters, cg_iters, flags, cg_tol, 0, 0)
+
+
+def pose_graph_workspace(n_nodes, n_edges, model=PM_PGO_SIM3):
+    """Bytes of device workspace for pose_graph_optimize_dev; 0 for bad arguments.  Needs no GPU."""
+    return int(lib().pm_pose_graph_workspace(n_nodes, n_edges, model))
+
+
 class HRefineInfo(C.Structure):
     """pm_h_refine_info (include/pm.h): costs in px^2, inliers used, LM iterations, status 0/1/2."""
     _fields_ = [("cost_in", C.c_double), ("cost_out", C.c_double), ("n_used", C.c_int32), ("iters", C.c_int32),
@@ -390,6 +423,7 @@ def lib():
         _lib.pm_status_string.restype = C.c_char_p
         _lib.pm_format_match_list.restype = C.c_long
         _lib.pm_bundle_adjust_workspace.restype = C.c_size_t
+        _lib.pm_pose_graph_workspace.restype = C.c_size_t
     return _lib
 
 
@@ -1741,6 +1775,59 @@ class Context:
         _check(lib().pm_bundle_adjust(self._h, up, rp, len(uv), n, C.byref(_camera(K)), C.byref(params), _p(out), _p(rows),
                                       _p(used), _p(info)))
         return out[:len(uv)], rows[:n], used[:n], info[0]
+
+    # -- pose-graph optimisation (SE(3) / Sim(3) loop correction in one launch, SPEC S118-S123) ----------------------------
+    def pose_graph_optimize_dev(self, dpose_in_ptr, n_nodes, dfixed_ptr, dab_ptr, dZ_ptr, dw_ptr, dcount_ptr, cap_edges, params,
+                                dpose_out_ptr, dused_ptr, dwork_ptr, work_bytes, dinfo_ptr):
+        """Device pointers: poses n_nodes x 13 f64 (out may be in), fixed n_nodes bytes, edges as ab (cap_edges x 2 i32), Z
+        (cap_edges x 13 f64, row e as pm_align3d_refine_dev writes it) and w (cap_edges x 3 f64), an optional device-side edge
+        count, optional d_edge_used (cap_edges bytes), a workspace of pose_graph_workspace(n_nodes, cap_edges, model) bytes
+        and *d_info (PGO_INFO_DTYPE).  Asynchronous on the stream."""
+        _check(lib().pm_pose_graph_optimize_dev(self._h, C.c_void_p(dpose_in_ptr), n_nodes, C.c_void_p(dfixed_ptr),
+                                                C.c_void_p(dab_ptr), C.c_void_p(dZ_ptr), C.c_void_p(dw_ptr),
+                                                C.c_void_p(dcount_ptr or 0), cap_edges, C.byref(params), C.c_void_p(dpose_out_ptr),
+                                                C.c_void_p(dused_ptr or 0), C.c_void_p(dwork_ptr), C.c_size_t(work_bytes),
+                                                C.c_void_p(dinfo_ptr)))
+
+    def pose_graph_optimize(self, pose, fixed, ab, Z, w, params=None):
+        """pose (N, 13), fixed (N) bytes, ab (E, 2), Z (E, 13), w (E, 3).  Returns (pose_out (N, 13), used (E) u8, info (a
+        PGO_INFO_DTYPE record))."""
+        params = params if params is not None else pgo_params()
+        pose = np.ascontiguousarray(pose, np.float64).reshape(-1, 13)
+        fixed = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+        ab = np.ascontiguousarray(ab, np.int32).reshape(-1, 2)
+        Z = np.ascontiguousarray(Z, np.float64).reshape(-1, 13)
+        w = np.ascontiguousarray(w, np.float64).reshape(-1, 3)
+        N, E = pose.shape[0], ab.shape[0]
+        if fixed.shape[0] != N or Z.shape[0] != E or w.shape[0] != E:
+            raise ValueError("one fixed byte per node; one measurement and one weight row per edge")
+        ab, Z, w = (v if E else np.zeros((1, v.shape[1]), v.dtype) for v in (ab, Z, w))
+        out = np.zeros((max(N, 1), 13), np.float64)
+        used = np.zeros(max(E, 1), np.uint8)
+        info = np.zeros(1, PGO_INFO_DTYPE)
+        _check(lib().pm_pose_graph_optimize(self._h, _p(pose), N, _p(fixed), _p(ab), _p(Z), _p(w), E, C.byref(params), _p(out),
+                                            _p(used), _p(info)))
+        return out[:N], used[:E], info[0]
+
+    def pgo_move_points_dev(self, dpose_old_ptr, dpose_new_ptr, n_nodes, danchor_ptr, dxyz_ptr, dn_ptr, cap, dout_ptr):
+        """Device pointers; poses n_nodes x 13 f64 before and after the graph, anchor cap i32, rows cap x 3 f32; dn_ptr (device
+        int32 count) may be None = cap; dout may equal dxyz."""
+        _check(lib().pm_pgo_move_points_dev(self._h, C.c_void_p(dpose_old_ptr), C.c_void_p(dpose_new_ptr), n_nodes,
+                                            C.c_void_p(danchor_ptr), C.c_void_p(dxyz_ptr), C.c_void_p(dn_ptr or 0), cap,
+                                            C.c_void_p(dout_ptr)))
+
+    def pgo_move_points(self, pose_old, pose_new, anchor, xyz):
+        """Host form: rows (n, 3) moved with their anchor keyframes -> (n, 3) f32; NaN rows stay NaN."""
+        po = np.ascontiguousarray(pose_old, np.float64).reshape(-1, 13)
+        pn = np.ascontiguousarray(pose_new, np.float64).reshape(-1, 13)
+        anchor = np.ascontiguousarray(anchor, np.int32).reshape(-1)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        if po.shape != pn.shape or anchor.shape[0] != n:
+            raise ValueError("old and new poses of the same nodes; one anchor per row")
+        out = np.zeros((max(n, 1), 3), np.float32)
+        _check(lib().pm_pgo_move_points(self._h, _p(po), _p(pn), po.shape[0], _p(anchor), _p(xyz), n, _p(out)))
+        return out[:n]
 
 
 class Pyramid:

@@ -22,7 +22,7 @@ SOURCES = ["pm_capi.cpp", "knn_l2.hip", "knn_coarse.hip", "knn_hamming.hip", "ra
            "pnp_refine.hip", "fundamental_refine.hip", "pose_refine.hip", "estimators.cpp", "match_cross.cpp",
            "pair_batch.cpp", "lmeds.hip", "mgpu.cpp", "flann.hip", "knn_guided.hip", "match_guided.cpp", "features.hip", "track_lk.hip",
            "corners.hip", "describe_points.hip", "warp.hip", "undistort.hip", "stereo.hip", "stereo_sgm.hip", "triangulate.hip",
-           "align3d_solve.hip", "ransac_align3d_fused.hip", "align3d_refine.hip", "vocab.hip", "bowdb.hip", "bundle_adjust.hip"]
+           "align3d_solve.hip", "ransac_align3d_fused.hip", "align3d_refine.hip", "vocab.hip", "bowdb.hip", "bundle_adjust.hip", "pose_graph.hip"]
 # per-file extra flags: the coarse kernels only nominate candidates (no result bit depends on them)
 EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          # one 512-thread workgroup holding 45 fp64 partial sums per thread: report its registers and spills
@@ -79,7 +79,10 @@ EXTRA = {"knn_coarse.hip": ["-ffinite-math-only"], "mgpu.cpp": ["-pthread"],
          "bowdb.hip": ["-Rpass-analysis=kernel-resource-usage"],
          # local bundle adjustment (S113-S117): one 512-thread workgroup, at most 42 fp64 partial sums per thread and the
          # 42 x 42 reduced system in LDS; it must not use scratch or spill
-         "bundle_adjust.hip": ["-Rpass-analysis=kernel-resource-usage"]}
+         "bundle_adjust.hip": ["-Rpass-analysis=kernel-resource-usage"],
+         # pose-graph optimisation (S118-S123): one 512-thread workgroup, a node's 28 + 7 fp64 sums per thread and the Jacobian
+         # rows streamed from the workspace; it must not use scratch or spill
+         "pose_graph.hip": ["-Rpass-analysis=kernel-resource-usage"]}
 RESOURCE_LINES = ("Function Name", "VGPRs:", "ScratchSize", "Spill")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
