@@ -25,6 +25,7 @@
 #include <new>
 
 #include "pm_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -44,20 +45,6 @@ struct BwScalars {
     unsigned n_images, n_entries;
     unsigned Nq, pad;                              // Nq of the last query: 0 when it was refused
 };
-
-__device__ __forceinline__ unsigned long long bw_wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned bw_wave_sum32(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o, 64));
-    return v;
-}
 
 // the stretch of words of wave `wv` of 16: whole groups of 64, so that every ballot below sees 64 lanes
 __device__ __forceinline__ void bw_stretch(int K, int wv, int& lo, int& hi)
@@ -89,9 +76,9 @@ __global__ __launch_bounds__(BW_WG) void bow_add(const uint32_t* __restrict__ hi
             nnz += h != 0;
         }
     }
-    T = bw_wave_sum64(T);
-    norm = bw_wave_sum64(norm);
-    nnz = bw_wave_sum32(nnz);
+    T = pm::wave_sum_u64(T);
+    norm = pm::wave_sum_u64(norm);
+    nnz = pm::wave_sum_u32(nnz);
     if (lane == 0) { s_T[wv] = T; s_norm[wv] = norm; s_nnz[wv] = nnz; }
     __syncthreads();
     unsigned long long T_all = 0, norm_all = 0;
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(BW_WG) void bow_add(const uint32_t* __restrict__ hi
             const unsigned h = w < hi ? hist[w] : 0u;
             const unsigned long long mask = __ballot(h != 0);
             if (h != 0) {
-                const unsigned pos = cursor + static_cast<unsigned>(__popcll(mask & ((1ull << lane) - 1ull)));
+                const unsigned pos = cursor + static_cast<unsigned>(pm::lane_rank(mask, lane));
                 words[pos] = static_cast<uint32_t>(w);
                 tfs[pos] = static_cast<uint16_t>(h);
                 df[w] += 1;
@@ -169,7 +156,7 @@ __global__ __launch_bounds__(256) void bow_norms(const BwScalars* __restrict__ s
         const unsigned off = offsets[i], end = offsets[i + 1];
         unsigned s = 0;
         for (unsigned e = off + lane; e < end; e += 64) s += static_cast<unsigned>(tfs[e]) * weight[words[e]];
-        s = bw_wave_sum32(s);
+        s = pm::wave_sum_u32(s);
         if (lane == 0) norms[i] = s;
     }
 }
@@ -192,8 +179,8 @@ __global__ __launch_bounds__(BW_WG) void bow_query_vec(const uint32_t* __restric
             qw[w] = make_uint2(static_cast<unsigned>(q), wt);        // (exact whenever the query is accepted)
         }
     }
-    T = bw_wave_sum64(T);
-    Nq = bw_wave_sum64(Nq);
+    T = pm::wave_sum_u64(T);
+    Nq = pm::wave_sum_u64(Nq);
     if (lane == 0) { s_T[wv] = T; s_Nq[wv] = Nq; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -235,7 +222,7 @@ __global__ __launch_bounds__(256) void bow_score(const BwScalars* __restrict__ s
                     S += a < d ? a : d;
                 }
             }
-            S = bw_wave_sum64(S);
+            S = pm::wave_sum_u64(S);
         }
         if (lane == 0) {
             const double s = live ? static_cast<double>(S) / static_cast<double>(Nq * Nd) : 0.0;
@@ -325,7 +312,7 @@ __global__ __launch_bounds__(BW_WG) void bow_top(const BwScalars* __restrict__ s
             const unsigned total = static_cast<unsigned>(__syncthreads_count(pass));
             if (total == 0) continue;                                 // uniform; nobody read wcnt
             if (pass) {
-                unsigned pos = cnt + static_cast<unsigned>(__popcll(mask & ((1ull << lane) - 1ull)));
+                unsigned pos = cnt + static_cast<unsigned>(pm::lane_rank(mask, lane));
                 for (unsigned i = 0; i < wv; ++i) pos += wcnt[i];
                 kh[pos] = eh[u];
                 kl[pos] = el[u];

@@ -33,6 +33,7 @@ using pm_hrefine::HR_CH;
 using pm_hrefine::HR_P;
 using pm_hrefine::LM_LAMBDA0;
 using pm_hrefine::LM_STEP_TOL;
+using pm_hrefine::group_max3;
 using pm_hrefine::lm_factor;
 using pm_hrefine::lm_subst;
 using pm_hrefine::pose_update;
@@ -117,16 +118,6 @@ __device__ __forceinline__ void observe(const Cam& k, const double (&P)[12], con
 // The poses in LDS change only between passes, so the compiler would hoist their loads out of the point loops and hold 12
 // doubles in registers through every pass (triangulate.hip's pose_fence).  This keeps each load next to its use.
 __device__ __forceinline__ void lds_fence() { asm volatile("" ::: "memory"); }
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double o = __shfl_xor(v, s, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
 {
@@ -446,16 +437,8 @@ __global__ __launch_bounds__(HR_P) void bundle_adjust(Args a)
                     Xt[3 * static_cast<size_t>(i) + c] = xc + dp[c];
                 }
             }
-            dmax = wave_max(dmax); hmax = wave_max(hmax); nonfin = wave_max(nonfin);
-            if ((tid & 63) == 0) { s_max[0][tid >> 6] = dmax; s_max[1][tid >> 6] = hmax; s_max[2][tid >> 6] = nonfin; }
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < HR_P / 64; ++w) {
-                dmax = s_max[0][w] > dmax ? s_max[0][w] : dmax;
-                hmax = s_max[1][w] > hmax ? s_max[1][w] : hmax;
-                nonfin = s_max[2][w] > nonfin ? s_max[2][w] : nonfin;
-            }
-            if (nonfin > 0.0 || !(dmax > LM_STEP_TOL * hmax)) break;
+            const auto mx = group_max3(s_max, tid, dmax, hmax, nonfin);         // of dmax, hmax, nonfin over the workgroup
+            if (mx.c > 0.0 || !(mx.a > LM_STEP_TOL * mx.b)) break;
             // ---- steps 7-9: the trial poses, their linearisation, accept or reject
             if (tid < F) pose_update(s_cur[s_fview[tid]], s_d + 6 * tid, s_tr[s_fview[tid]]);
             __syncthreads();

@@ -17,6 +17,7 @@
 
 #include "pm_common.hpp"
 #include "pyramid.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -124,14 +125,7 @@ __global__ __launch_bounds__(256) void corner_rank(const unsigned* counter, unsi
     if (blockIdx.x * 256u >= n) return;
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     const unsigned long long mine = t < n ? keys[t] : 0ull;
-    unsigned rank = 0;
-    for (unsigned base = 0; base < n; base += 256) {
-        __syncthreads();
-        if (base + threadIdx.x < n) s_key[threadIdx.x] = keys[base + threadIdx.x];
-        __syncthreads();
-        const unsigned m = min(256u, n - base);
-        for (unsigned j = 0; j < m; ++j) rank += s_key[j] < mine ? 1u : 0u;
-    }
+    const unsigned rank = pm::rank_below(keys, n, mine, s_key);
     if (t < n) sorted[rank] = mine;
 }
 
@@ -254,7 +248,7 @@ __global__ __launch_bounds__(ST) void corner_select(const SelArgs a)
             if (wd < wv) before += c;
             total += c;
         }
-        before += __popcll(s_acc[wv] & ((1ull << lane) - 1ull));
+        before += pm::lane_rank(s_acc[wv], lane);
         const int row = n_acc + before;
         if (state == 1 && row < limit) {
             out[2 * static_cast<size_t>(row)] = fx;

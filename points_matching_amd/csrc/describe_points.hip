@@ -14,6 +14,7 @@
 
 #include "pm_common.hpp"
 #include "pyramid.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -82,21 +83,8 @@ struct DescArgs {
     uint8_t* bin;
 };
 
-// The lanes of ONE wave exchange data through their slice of LDS (as in track_lk.hip): LDS operations of a wave complete in
-// issue order, so all that is needed is that the compiler keeps the order too.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
+using pm::wave_lds_sync;
+using pm::wave_sum_i32;
 
 // No workgroup barrier anywhere: a wave owns its point and its LDS slice, so a wave behind the count may leave at once and the
 // waves of a workgroup may take the valid and the invalid path side by side.  Every branch below is wave-uniform.
@@ -204,51 +192,33 @@ __global__ __launch_bounds__(64 * WPB) void desc_points(const DescArgs a)
     }
 }
 
-// ---- the gather form.  One workgroup: flags of a chunk of 1024 rows, exclusive scan (ballot prefix inside a wave, wave totals
-// through LDS), then the chunk's bytes are moved one per thread and step, so that a row's 32 bytes go out as one segment.  The
-// running base carries the order across chunks: the selection is stable.
+// ---- the gather form.  One workgroup selects the valid rows in order (pm::select_stable_1024); a chunk's descriptor bytes are
+// then moved one per thread and step, so that a row's 32 bytes go out as one segment.
 __global__ __launch_bounds__(1024) void desc_compact(const float* pts, const int32_t* d_n, int cap, const uint8_t* rows, const uint8_t* valid,
                                                      float* xy, uint8_t* desc, int32_t* src_idx, int32_t* count)
 {
-    __shared__ int s_wave[16];
     __shared__ int s_dst[1024];
-    __shared__ int s_base;
     const int n = pm::clamped_count(d_n, cap);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int r0 = 0; r0 < n; r0 += 1024) {                         // (n is the same on every thread: a uniform trip count)
-        const int r = r0 + tid;
-        const int f = r < n ? (valid[r] != 0) : 0;
-        const unsigned long long bal = __ballot(f);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int off = s_base, total = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wv) off += s_wave[k];
-            total += s_wave[k];
-        }
-        const int d = f ? off + before : -1;
-        s_dst[tid] = d;
-        if (f) {
+    const int tid = threadIdx.x;
+    pm::select_stable_1024(
+        n, count, [&](int r) { return valid[r] != 0; },
+        [&](int r, int d) {
+            s_dst[tid] = d;
+            if (d < 0) return;
             const unsigned* p = reinterpret_cast<const unsigned*>(pts) + 2 * static_cast<size_t>(r);     // bit copies
             unsigned* o = reinterpret_cast<unsigned*>(xy) + 2 * static_cast<size_t>(d);
             o[0] = p[0];
             o[1] = p[1];
             if (src_idx) src_idx[d] = r;
-        }
-        __syncthreads();
-        const int m = min(1024, n - r0);
-        for (int e = tid; e < m * 32; e += 1024) {
-            const int k = e >> 5, byte = e & 31;
-            const int dst = s_dst[k];
-            if (dst >= 0) desc[static_cast<size_t>(dst) * 32 + byte] = rows[static_cast<size_t>(r0 + k) * 32 + byte];
-        }
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) *count = s_base;
+        },
+        [&](int r0) {
+            const int m = min(1024, n - r0);
+            for (int e = tid; e < m * 32; e += 1024) {
+                const int k = e >> 5, byte = e & 31;
+                const int dst = s_dst[k];
+                if (dst >= 0) desc[static_cast<size_t>(dst) * 32 + byte] = rows[static_cast<size_t>(r0 + k) * 32 + byte];
+            }
+        });
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "pm_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -256,14 +257,7 @@ __global__ __launch_bounds__(256) void feat_rank(const unsigned* counter, unsign
     if (blockIdx.x * 256u >= n) return;
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     const unsigned long long mine = t < n ? keys[t] : 0ull;
-    unsigned rank = 0;
-    for (unsigned base = 0; base < n; base += 256) {
-        __syncthreads();
-        if (base + threadIdx.x < n) s_key[threadIdx.x] = keys[base + threadIdx.x];
-        __syncthreads();
-        const unsigned m = min(256u, n - base);
-        for (unsigned j = 0; j < m; ++j) rank += s_key[j] < mine ? 1u : 0u;
-    }
+    const unsigned rank = pm::rank_below(keys, n, mine, s_key);
     if (t < n && rank < static_cast<unsigned>(max_kp)) sel[rank] = static_cast<int>(t);
 }
 
@@ -420,7 +414,7 @@ __global__ __launch_bounds__(DTHREADS) void feat_describe(const float* pyr, cons
 #pragma unroll 1
         for (int t = 0; t < 8; ++t) {
             const unsigned long long bal = __ballot((waves >> t) & 1);
-            before |= static_cast<unsigned long long>(__popcll(bal & ((1ull << lane) - 1ull))) << (8 * t);
+            before |= static_cast<unsigned long long>(pm::lane_rank(bal, lane)) << (8 * t);
             if (lane == 0) s_cnt[t][wave] = __popcll(bal);
         }
         __syncthreads();
@@ -562,35 +556,18 @@ __global__ __launch_bounds__(BTHREADS) void feat_describe_bits(const float* pyr,
 // order and publishes the count; on overflow of the candidate buffer the count is -1 and no row is written.
 __global__ __launch_bounds__(1024) void feat_compact(const unsigned* counter, unsigned cap, int max_kp, const int* valid, int* pos, int* d_n)
 {
-    __shared__ int s_wave[16];
-    __shared__ int s_base;
     const unsigned cnt = *counter;
     if (cnt > cap) {
         if (threadIdx.x == 0) *d_n = -1;
         return;
     }
     const int n_sel = min(static_cast<int>(cnt), max_kp);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int r0 = 0; r0 < n_sel; r0 += 1024) {
-        const int r = r0 + tid;
-        const int f = r < n_sel ? (valid[r] != 0) : 0;
-        const unsigned long long bal = __ballot(f);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int off = s_base, total = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wv) off += s_wave[k];
-            total += s_wave[k];
-        }
-        if (r < n_sel) pos[r] = f ? off + before : -1;
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) *d_n = s_base;
+    pm::select_stable_1024(
+        n_sel, d_n, [&](int r) { return valid[r] != 0; },
+        [&](int r, int dst) {
+            if (r < n_sel) pos[r] = dst;
+        },
+        [](int) {});
 }
 
 __global__ __launch_bounds__(128) void feat_gather(const unsigned* counter, unsigned cap, int max_kp, const int* pos, const float* kp_tmp,

@@ -6,6 +6,7 @@
 // second neighbour present and d1 < ratio * d2 (float multiply, strict).  The cross-check rule of SPEC S41 (mutual
 // nearest neighbours, pm_filter_cross) is a third predicate of the same compaction.
 #include "pm_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -167,7 +168,7 @@ __device__ __forceinline__ void fg_compact(const pm_match* __restrict__ knn, int
     for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
     if (lane == 0) wave_pre[wave] = before;
     __syncthreads();
-    int off = __popcll(bal & ((1ull << lane) - 1ull));
+    int off = pm::lane_rank(bal, lane);
 #pragma unroll
     for (int w = 0; w < FG_ROWS / 64; ++w) {
         off += wave_pre[w];

@@ -16,6 +16,7 @@
 // all nq x nt pairs.  Nothing in the result depends on GK_BATCH, the ring size or the grid: a row's distance is a function
 // of the two rows alone and the order is decided by the keys.
 #include "pm_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -136,9 +137,7 @@ __device__ __forceinline__ float gk_l2sqr_coop8(const E* __restrict__ a, const E
         const float p = t * t;
         acc = acc + p;
     }
-    const float s = acc + __shfl_down(acc, 4, 8);            // lanes 0..3: acc[l] + acc[l+4]
-    const float s1 = __shfl_down(s, 1, 8), s2 = __shfl_down(s, 2, 8), s3 = __shfl_down(s, 3, 8);
-    float d = ((s + s1) + s2) + s3;                          // meaningful in lane 0
+    float d = pm::coop8_combine(acc);                        // meaningful in lane 0
     for (int j = full8; j < dim; ++j) {
         const float t = static_cast<float>(a[j]) - static_cast<float>(b[j]);
         const float p = t * t;
@@ -321,7 +320,7 @@ __global__ __launch_bounds__(64) void knn_guided(const typename POL::elem* __res
                 }
                 const unsigned long long mask = __ballot(in);
                 if (mask == 0ull) continue;                                     // wave-uniform
-                if (in) ring[(tail + static_cast<unsigned>(__popcll(mask & ((1ull << lane) - 1ull)))) & (GK_RING - 1)] = j;
+                if (in) ring[(tail + static_cast<unsigned>(pm::lane_rank(mask, lane))) & (GK_RING - 1)] = j;
                 tail += static_cast<unsigned>(__popcll(mask));
                 __syncthreads();
                 if (tail - head >= static_cast<unsigned>(GK_BATCH)) {

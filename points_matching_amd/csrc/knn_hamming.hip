@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "knn_shared.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 using namespace pm_knn;
@@ -269,6 +270,7 @@ struct Key32T {
     static __device__ __forceinline__ int dist(type k) { return static_cast<int>(k >> SHIFT); }
     static __device__ __forceinline__ int row(type k) { return static_cast<int>(k & ((1u << SHIFT) - 1u)); }
     static __device__ __forceinline__ type wave_min(type k) { return wave_min_u32(k); }
+    static __device__ __forceinline__ type row16_min(type k) { return pm::row16_min_u32(k); }
 };
 typedef Key32T<23> Key32;
 typedef Key32T<22> Key32W;
@@ -279,6 +281,7 @@ struct Key64 {
     static __device__ __forceinline__ int dist(type k) { return static_cast<int>(k >> 32); }
     static __device__ __forceinline__ int row(type k) { return static_cast<int>(k & 0xFFFFFFFFull); }
     static __device__ __forceinline__ type wave_min(type k) { return wave_min_u64(k); }
+    static __device__ __forceinline__ type row16_min(type k) { return pm::row16_min_u64(k); }
 };
 
 template <typename KT>
@@ -500,23 +503,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine(const uint32_t* __rest
 // no v_readlane), the instruction stream of a wave serves four queries.  Same entry layout, same tau / full-sub-list /
 // candidate rules and therefore the same rows evaluated as knn_hamming_refine above; for slots <= 64 (NE = 1, 2 or 4
 // entries per lane: entry e = l + 16*i).
-__device__ __forceinline__ unsigned row16_min_u32(unsigned v)
-{
-    v = min(v, pm::dpp_u32<0x121>(v));      // row_ror:1
-    v = min(v, pm::dpp_u32<0x122>(v));
-    v = min(v, pm::dpp_u32<0x124>(v));
-    v = min(v, pm::dpp_u32<0x128>(v));
-    return v;
-}
-__device__ __forceinline__ unsigned long long row16_min_u64(unsigned long long v)
-{
-    const unsigned hi = static_cast<unsigned>(v >> 32), lo = static_cast<unsigned>(v);
-    const unsigned mh = row16_min_u32(hi);
-    const unsigned ml = row16_min_u32(hi == mh ? lo : 0xFFFFFFFFu);
-    return (static_cast<unsigned long long>(mh) << 32) | ml;
-}
-__device__ __forceinline__ unsigned row16_min(unsigned v) { return row16_min_u32(v); }
-__device__ __forceinline__ unsigned long long row16_min(unsigned long long v) { return row16_min_u64(v); }
+using pm::row16_min_u32;
 
 template <int NE, int NW, typename K>
 __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __restrict__ Q, const uint32_t* __restrict__ T,
@@ -597,7 +584,7 @@ __global__ __launch_bounds__(256) void knn_hamming_refine4(const uint32_t* __res
     }
     wg_scan_phase<16, 4 * NE, 16, NW, K>(hs, best, own, l, T, nt, tiles_per_split);
     for (int c = 0; c < k; ++c) {
-        const typename K::type m = row16_min(best.a);
+        const typename K::type m = K::row16_min(best.a);
         if (best.a == m && m != K::NONE) { best.a = best.b; best.b = K::NONE; }      // keys are unique rows
         if (l == 0 && live) {
             pm_match mm;

@@ -24,6 +24,7 @@
 
 #include "knn_l2_plan.hpp"
 #include "knn_shared.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -828,9 +829,7 @@ __device__ __forceinline__ float l2sqr_canonical_coop8(const float* __restrict__
         const float p = t * t;
         acc = acc + p;
     }
-    const float s = acc + __shfl_down(acc, 4, 8);            // lanes 0..3: acc[l] + acc[l+4]
-    const float s1 = __shfl_down(s, 1, 8), s2 = __shfl_down(s, 2, 8), s3 = __shfl_down(s, 3, 8);
-    float d = ((s + s1) + s2) + s3;                          // meaningful in lane 0
+    float d = pm::coop8_combine(acc);                        // meaningful in lane 0
     for (int j = full8; j < dim; ++j) {
         const float t = a[j] - b[j];
         const float p = t * t;
@@ -984,7 +983,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(80))) void knn_
             const bool mine_spilled = (spilled >> (lane | (KNN_C - 1))) & 1ull;
             const bool is_cand = in && v <= thr && j < nt && !mine_spilled;
             const unsigned long long cand = __ballot(is_cand);
-            if (is_cand) clist[wave][total + __popcll(cand & ((1ull << lane) - 1ull))] = j;
+            if (is_cand) clist[wave][total + pm::lane_rank(cand, lane)] = j;
             total += __popcll(cand);
             if (diag && lane == 0 && spilled && !ghost) atomicAdd(&diag[0], static_cast<unsigned>(__popcll(spilled)));
             while (spilled) {                               // wave-uniform, rare: every row of that split
@@ -1159,21 +1158,6 @@ __device__ __forceinline__ int u8_unit_dot8(const uint4& qu, const uint4& tu)
 // covers 4 queries x 2 rows x 128 B, and lane (hh, sub) ends the pass owning candidate r0 + 2 sub + hh.  A lane holds
 // one 16-byte unit of its query, not the whole row.  A query with an overflowing list, fewer than k ranked groups or a
 // wrong hint scans all train rows (rare).
-__device__ __forceinline__ unsigned row_min_u32(unsigned v)          // minimum over the lane's 16-lane row, in every lane of it
-{
-    v = min(v, pm::dpp_u32<0x121>(v));
-    v = min(v, pm::dpp_u32<0x122>(v));
-    v = min(v, pm::dpp_u32<0x124>(v));
-    v = min(v, pm::dpp_u32<0x128>(v));
-    return v;
-}
-__device__ __forceinline__ unsigned long long row_min_u64(unsigned long long v)
-{
-    const unsigned hi = static_cast<unsigned>(v >> 32), lo = static_cast<unsigned>(v);
-    const unsigned mh = row_min_u32(hi);
-    const unsigned ml = row_min_u32(hi == mh ? lo : 0xFFFFFFFFu);
-    return (static_cast<unsigned long long>(mh) << 32) | ml;
-}
 
 // Exact re-scans of knn_l2_refine8 (round 3).  A list whose 4th entry is inside the window may have dropped candidates
 // (SPEC S1b), so the rows of that split are evaluated exactly; runs of identical train rows — repeated texture — make that
@@ -1267,7 +1251,7 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
     static_assert(KNN_C == 4, "slot decoding assumes 4 entries per list");
     int tau = IMAX;
     for (int round = 0; round < k; ++round) {                // k <= KM
-        tau = static_cast<int>(row_min_u32(static_cast<unsigned>(mn.m[0]) ^ 0x80000000u) ^ 0x80000000u);
+        tau = static_cast<int>(pm::row16_min_u32(static_cast<unsigned>(mn.m[0]) ^ 0x80000000u) ^ 0x80000000u);
         const unsigned owners = static_cast<unsigned>(__ballot(mn.m[0] == tau) >> (16 * qi)) & 0xFFFFu;
         if (l == __ffs(static_cast<int>(owners)) - 1) mn.pop(IMAX);
     }
@@ -1390,7 +1374,7 @@ __global__ __launch_bounds__(256) void knn_l2_refine8(
     int nn_idx[2] = {-1, -1};                                // the first two neighbours of the row's query (FUSE)
     float nn_d[2] = {KNN_INF, KNN_INF};
     for (int c = 0; c < k; ++c) {
-        const uint64_t best = row_min_u64(b.k[0]);
+        const uint64_t best = pm::row16_min_u64(b.k[0]);
         const unsigned owners = static_cast<unsigned>(__ballot(b.k[0] == best) >> (16 * qi)) & 0xFFFFu;
         const int first = __ffs(static_cast<int>(owners)) - 1;
         const float dist = __shfl(b.d[0], 16 * qi + first, 64);

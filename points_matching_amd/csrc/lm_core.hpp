@@ -8,6 +8,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_ops.hpp"
+
 namespace pm_hrefine {
 
 constexpr double LM_LAMBDA0 = 1e-3;       // S24 initial damping (S40, S45, S47, S95, S115 start from it too)
@@ -125,6 +127,28 @@ __device__ __forceinline__ double step_max(const double* d)
     for (int i = 0; i < N; ++i)
         if (!(fabs(d[i]) <= dmax)) dmax = fabs(d[i]);
     return dmax;
+}
+
+// The workgroup maximum of three values at once (the step test of bundle adjustment and of the pose graph: largest step,
+// scale of the parameters, non-finite flag): a wave butterfly each, the NW wave maxima through s_max, one barrier.  Every
+// thread of the NW waves calls it with its own three values and gets the three maxima; a NaN never wins.  (By value and a
+// returned struct: with reference parameters the callers' `if (x > dmax) dmax = x` compile to branches.)
+struct Max3 {
+    double a, b, c;
+};
+template <int NW>
+__device__ __forceinline__ Max3 group_max3(double (&s_max)[3][NW], int tid, double a, double b, double c)
+{
+    a = pm::wave_max_f64(a); b = pm::wave_max_f64(b); c = pm::wave_max_f64(c);
+    if ((tid & 63) == 0) { s_max[0][tid >> 6] = a; s_max[1][tid >> 6] = b; s_max[2][tid >> 6] = c; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        a = s_max[0][w] > a ? s_max[0][w] : a;
+        b = s_max[1][w] > b ? s_max[1][w] : b;
+        c = s_max[2][w] > c ? s_max[2][w] : c;
+    }
+    return {a, b, c};
 }
 
 // S40 step 4: C = Cayley(d / 2)

@@ -32,6 +32,7 @@ using pm_hrefine::HR_CH;
 using pm_hrefine::HR_P;
 using pm_hrefine::LM_LAMBDA0;
 using pm_hrefine::LM_STEP_TOL;
+using pm_hrefine::group_max3;
 using pm_hrefine::lm_factor;
 using pm_hrefine::lm_subst;
 using pm_hrefine::pose_update;
@@ -172,16 +173,6 @@ __device__ __forceinline__ bool edge_eval(const double* Ap, const double* Bp, co
         Jb[P * 3 + 6] = -wm0; Jb[P * 4 + 6] = -wm1; Jb[P * 5 + 6] = -wm2;
     }
     return den > 0.0009765625;
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        const double o = __shfl_xor(v, s, 64);
-        v = o > v ? o : v;
-    }
-    return v;
 }
 
 // t = a_0 b_0, t = fma(a_j, b_j, t)
@@ -528,16 +519,8 @@ __global__ __launch_bounds__(HR_P) void pose_graph(Args a)
                     if (h > hmax) hmax = h;
                 }
             }
-            dmax = wave_max(dmax); hmax = wave_max(hmax); nonfin = wave_max(nonfin);
-            if ((tid & 63) == 0) { s_max[0][tid >> 6] = dmax; s_max[1][tid >> 6] = hmax; s_max[2][tid >> 6] = nonfin; }
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < HR_P / 64; ++w) {
-                dmax = s_max[0][w] > dmax ? s_max[0][w] : dmax;
-                hmax = s_max[1][w] > hmax ? s_max[1][w] : hmax;
-                nonfin = s_max[2][w] > nonfin ? s_max[2][w] : nonfin;
-            }
-            if (__builtin_amdgcn_readfirstlane(static_cast<int>(nonfin > 0.0 || !(dmax > LM_STEP_TOL * hmax)))) break;
+            const auto mx = group_max3(s_max, tid, dmax, hmax, nonfin);         // of dmax, hmax, nonfin over the workgroup
+            if (__builtin_amdgcn_readfirstlane(static_cast<int>(mx.c > 0.0 || !(mx.a > LM_STEP_TOL * mx.b)))) break;
             // ---- step 6: the trial poses, their linearisation, accept or reject
             double bad = 0.0;
             for (int i = tid; i < N; i += HR_P) {

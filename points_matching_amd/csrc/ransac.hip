@@ -21,6 +21,7 @@
 // elsewhere; the TU is built with -ffp-contract=off) so that the CPU restatement reproduces the
 // same bits.
 #include "ransac_internal.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -87,16 +88,6 @@ __device__ __forceinline__ unsigned long long hyp_key(const float* __restrict__ 
     const unsigned long long key = (static_cast<unsigned long long>(cnt) << 32) |
                                    static_cast<unsigned long long>(0xFFFFFFFFu - h);
     return valid != 0.f ? key : 0ull;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long key)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(key, o, 64);
-        key = w > key ? w : key;
-    }
-    return key;
 }
 
 constexpr int SCORE_CHUNK = 256;      // correspondences staged per pass (4 KB of LDS)
@@ -263,7 +254,7 @@ __global__ __launch_bounds__(256) void ransac_score(const float* __restrict__ xy
         key = (static_cast<unsigned long long>(c) << 32) |
               static_cast<unsigned long long>(0xFFFFFFFFu - static_cast<uint32_t>(ft.hyp_begin + t));
     }
-    key = wave_max_u64(key);
+    key = pm::wave_max_u64_xor(key);
     if ((threadIdx.x & 63) == 0) wkey[threadIdx.x >> 6] = key;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -321,7 +312,7 @@ __global__ __launch_bounds__(256) void ransac_select(const float* __restrict__ m
     __shared__ unsigned long long wbest[4];
     const int t = blockIdx.x * 256 + threadIdx.x;
     unsigned long long key = t < nh ? hyp_key(models, counts, t, hyp_begin) : 0ull;
-    key = wave_max_u64(key);
+    key = pm::wave_max_u64_xor(key);
     if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = key;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -33,6 +33,7 @@
 
 #include "ransac_core.hpp"
 #include "ransac_internal.hpp"
+#include "wave_ops.hpp"
 
 namespace pm_ransac {
 namespace {

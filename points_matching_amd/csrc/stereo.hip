@@ -21,6 +21,7 @@
 #include "pm_common.hpp"
 #include "stereo_core.hpp"
 #include "stereo_rectify_core.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 

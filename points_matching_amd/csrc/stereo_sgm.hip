@@ -22,6 +22,7 @@
 #include "pm_common.hpp"
 #include "stereo_core.hpp"
 #include "stereo_sgm_plan.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -83,24 +84,6 @@ struct PathArgs {
     int dstride;
     pm_stereo_info* info;
 };
-
-// pm::wave_min_u32 with the value that no lane reads (every row_ror lane has a source) set to the minimum's identity, so that
-// the compiler folds each move into its v_min_u32: one instruction per stage instead of three.  All 64 lanes active.
-template <int CTRL>
-__device__ __forceinline__ unsigned min_dpp(unsigned v)
-{
-    return min(v, static_cast<unsigned>(__builtin_amdgcn_update_dpp(-1, static_cast<int>(v), CTRL, 0xF, 0xF, false)));
-}
-__device__ __forceinline__ unsigned wave_min(unsigned v)
-{
-    v = min_dpp<0x121>(v);                                // row_ror:1, 2, 4, 8
-    v = min_dpp<0x122>(v);
-    v = min_dpp<0x124>(v);
-    v = min_dpp<0x128>(v);
-    const unsigned a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const unsigned c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    return min(min(a, b), min(c, d));
-}
 
 enum { WRITE = 0, ADD = 1, WINNER = 2 };
 
@@ -211,7 +194,7 @@ __global__ __launch_bounds__(64) void sgm_path(PathArgs a)
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) lo = min(lo, L[c]);
-        m = wave_min(lo);
+        m = pm::wave_min_u32_id(lo);
 
         unsigned Sv[NC];
 #pragma unroll
@@ -221,7 +204,7 @@ __global__ __launch_bounds__(64) void sgm_path(PathArgs a)
             for (int c = 0; c < NC; ++c)
                 if (live[c]) cs[lane + 64 * c] = static_cast<uint16_t>(Sv[c]);
         } else {
-            const stereo_core::Won won = stereo_core::winner<wave_min>(Sv, live, lane, D, a.dmin, a.uniq);
+            const stereo_core::Won won = stereo_core::winner<pm::wave_min_u32_id>(Sv, live, lane, D, a.dmin, a.uniq);
             if (won.kept) ++n_valid;
             if (lane == 0) *cd = static_cast<int16_t>(won.value);
         }

@@ -15,6 +15,7 @@
 
 #include "pm_common.hpp"
 #include "pyramid.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -102,23 +103,8 @@ __device__ __forceinline__ int sample(const uint8_t* p, int w, const Win& o)
     return (p[0] * o.w00 + p[1] * o.w01 + p[w] * o.w10 + p[w + 1] * o.w11 + 256) >> 9;
 }
 
-// Exact 64-lane sum: an xor butterfly of six __shfl_xor steps (two ds_bpermute each for the 64-bit value); every lane ends
-// with the total.  The addends are integers, so the order of the butterfly is of no consequence.
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// The lanes of ONE wave exchange data through their slice of LDS.  LDS operations of a wave complete in issue order, so all
-// that is needed is that the compiler keeps the order too.
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using pm::wave_lds_sync;
+using pm::wave_sum_i64;         // the sums below are long long throughout: exact
 
 __device__ __forceinline__ float canon(float v) { return v != v ? __uint_as_float(0x7FC00000u) : v; }
 
@@ -173,9 +159,9 @@ __device__ __forceinline__ int track_point(const LkArgs& a, int dir, float ptx, 
                 syy += dy * dy;
             }
             wave_lds_sync();
-            Gxx = static_cast<double>(wave_sum(sxx));
-            Gxy = static_cast<double>(wave_sum(sxy));
-            Gyy = static_cast<double>(wave_sum(syy));
+            Gxx = static_cast<double>(wave_sum_i64(sxx));
+            Gxy = static_cast<double>(wave_sum_i64(sxy));
+            Gyy = static_cast<double>(wave_sum_i64(syy));
             D = Gxx * Gyy - Gxy * Gxy;
             const double ev = ((Gxx + Gyy) - sqrt((Gxx - Gyy) * (Gxx - Gyy) + 4.0 * (Gxy * Gxy))) / (2.0 * N * 4096.0);
             if (!(ev >= static_cast<double>(a.prm.min_eig)) || !(D > 0)) code = 2;
@@ -198,8 +184,8 @@ __device__ __forceinline__ int track_point(const LkArgs& a, int dir, float ptx, 
                 by += d * sgy[e];
                 sa += d < 0 ? -d : d;
             }
-            const double dbx = static_cast<double>(wave_sum(bx)), dby = static_cast<double>(wave_sum(by));
-            const long long tsa = wave_sum(sa);
+            const double dbx = static_cast<double>(wave_sum_i64(bx)), dby = static_cast<double>(wave_sum_i64(by));
+            const long long tsa = wave_sum_i64(sa);
             if (l == 0) err = static_cast<float>(static_cast<double>(tsa) / (32.0 * N));
             const double dx = 2.0 * (Gxy * dby - Gyy * dbx) / D;
             const double dy = 2.0 * (Gxy * dbx - Gxx * dby) / D;
@@ -246,42 +232,22 @@ __global__ __launch_bounds__(64 * WPB) void lk_track(const LkArgs a)
     }
 }
 
-// ---- S66: the gather form.  One workgroup: flags of a chunk of 1024 rows, exclusive scan (ballot prefix inside a wave, wave
-// totals through LDS), the move; the running base carries the order across chunks, so the selection is stable.
+// ---- S66: the gather form.  One workgroup selects the tracked rows in order (pm::select_stable_1024) and moves them.
 __global__ __launch_bounds__(1024) void lk_compact(const float* pts, const int32_t* d_n, int cap, const float* out, const uint8_t* status,
                                                    float* xy1, float* xy2, int32_t* src_idx, int32_t* count)
 {
-    __shared__ int s_wave[16];
-    __shared__ int s_base;
-    const int n = pm::clamped_count(d_n, cap);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int r0 = 0; r0 < n; r0 += 1024) {
-        const int r = r0 + tid;
-        const int f = r < n ? (status[r] == 1) : 0;
-        const unsigned long long bal = __ballot(f);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[wv] = __popcll(bal);
-        __syncthreads();
-        int off = s_base, total = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < wv) off += s_wave[k];
-            total += s_wave[k];
-        }
-        if (f) {
-            const size_t d = static_cast<size_t>(off + before), s = static_cast<size_t>(r);
+    pm::select_stable_1024(
+        pm::clamped_count(d_n, cap), count, [&](int r) { return status[r] == 1; },
+        [&](int r, int dst) {
+            if (dst < 0) return;
+            const size_t d = static_cast<size_t>(dst), s = static_cast<size_t>(r);
             xy1[2 * d] = pts[2 * s];
             xy1[2 * d + 1] = pts[2 * s + 1];
             xy2[2 * d] = out[2 * s];
             xy2[2 * d + 1] = out[2 * s + 1];
             if (src_idx) src_idx[d] = r;
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) *count = s_base;
+        },
+        [](int) {});
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------

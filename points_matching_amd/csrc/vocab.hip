@@ -25,6 +25,7 @@
 #include <new>
 
 #include "pm_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -63,13 +64,6 @@ __device__ __forceinline__ unsigned vc_sort64(unsigned key, int lane)
         }
     }
     return key;
-}
-
-__device__ __forceinline__ unsigned vc_wave_sum(unsigned v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += static_cast<unsigned>(__shfl_xor(static_cast<int>(v), o, 64));
-    return v;
 }
 
 // KIND 0: u8 rows, squared L2.  KIND 1: bit rows, Hamming.  W = dwords per row (1 .. 64; bit rows 1 .. 16).
@@ -188,7 +182,7 @@ __global__ __launch_bounds__(256) void vocab_update(const pm_match* __restrict__
         }
         flush();
     }
-    cost = vc_wave_sum(cost);
+    cost = pm::wave_sum_u32(cost);
     if (lane == 0) {
         if (n_changed) atomicAdd(&sc->n_changed, n_changed);
         if (cost) atomicAdd(&sc->cost, static_cast<unsigned long long>(cost));

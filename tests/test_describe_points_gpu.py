@@ -242,6 +242,44 @@ def test_gather_more_than_one_chunk(ctx, fr):
     assert_gathered("2500 points", dev_gather(ctx, fr.dev("1"), d_pts.data_ptr(), None, 2500), pts, want)
 
 
+CHUNK_CAP = 2049                                                     # two chunks of the compaction's 1024 rows and one row
+CHUNK_KEPT = {"all": lambda n: n, "none": lambda n: 0, "alternating": lambda n: (n + 1) // 2}
+
+
+@pytest.fixture(scope="module")
+def chunk_rows(ctx, fr):
+    """pattern -> (points, the same on the device, their aligned rows from pm_describe_points_dev), each made once.  2049
+    points of frame "1": every one at least 20 pixels inside the image, every one outside it, or the two in turn."""
+    import torch
+    h, w = fr.img["1"].shape
+    rng = np.random.default_rng(21)
+    inside = np.stack([rng.uniform(20, w - 21, CHUNK_CAP), rng.uniform(20, h - 21, CHUNK_CAP)], 1).astype(np.float32)
+    outside = np.stack([rng.uniform(w + 5, w + 50, CHUNK_CAP), rng.uniform(-50, -5, CHUNK_CAP)], 1).astype(np.float32)
+    mixed = np.where((np.arange(CHUNK_CAP) % 2 == 0)[:, None], inside, outside)
+    out = {}
+    for pattern, pts in (("all", inside), ("none", outside), ("alternating", mixed)):
+        aligned = dev_describe(ctx, fr.dev("1"), pts)
+        assert int(aligned[1].sum()) == CHUNK_KEPT[pattern](CHUNK_CAP)
+        out[pattern] = (pts, torch.from_numpy(pts).to("cuda:0"), aligned)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("pattern", ["all", "none", "alternating"])
+@pytest.mark.parametrize("count", [0, 1, 1023, 1024, 1025, 2049])
+def test_gather_at_the_chunk_boundary(ctx, fr, chunk_rows, pattern, count):
+    """The device count at 0, 1, one below, at and one above the compaction's chunk of 1024 rows, and at two chunks and a row,
+    with every row kept, none, and every other one: rows, src_idx and count are the aligned form of the same points compacted on
+    the host, and everything behind the count keeps its pattern."""
+    import torch
+    pts, d_pts, aligned = chunk_rows[pattern]
+    d_n = torch.tensor([count], dtype=torch.int32, device="cuda:0")
+    got = dev_gather(ctx, fr.dev("1"), d_pts.data_ptr(), d_n.data_ptr(), CHUNK_CAP)
+    want = tuple(a[:count] for a in aligned)
+    assert int(want[1].sum()) == CHUNK_KEPT[pattern](count)
+    assert_gathered("%s, count %d" % (pattern, count), got, pts[:count], want)
+
+
 def test_gather_chained_after_corners(ctx, fr):
     """pm_corners_dev -> pm_describe_points_gather_dev through the device count, no host round trip between them."""
     import torch
