@@ -10,11 +10,11 @@
 namespace pm_affine {
 
 using pm_ransac::f32x2;
-using pm_ransac::mix64;
 
 enum { FULL = PM_AFFINE_FULL, PARTIAL = PM_AFFINE_PARTIAL };
 
-// S26: sample size and sampler stream key of a model (the two 16-bit rotations of S6's constant S6, S13, S19 leave)
+// S26: sample size and sampler stream key of a model (the two 16-bit rotations of S6's constant S6, S13, S19 leave);
+// the sample is S6's walk, sample_walk<MIN_PTS, STREAM> (sample_core.hpp)
 template <int MODEL> struct Traits;
 template <> struct Traits<FULL> {
     static constexpr int MIN_PTS = 3;
@@ -24,41 +24,6 @@ template <> struct Traits<PARTIAL> {
     static constexpr int MIN_PTS = 2;
     static constexpr uint64_t STREAM = 0x7C159E3779B97F4AULL;
 };
-
-// SPEC S26: K distinct indices in [0, n) as a pure function of (seed, h, n), n >= K.  S6's walk on its own stream.
-template <int MODEL>
-__device__ __forceinline__ void sample(uint64_t seed, uint64_t h, int n, int (&idx)[Traits<MODEL>::MIN_PTS])
-{
-    constexpr int K = Traits<MODEL>::MIN_PTS;
-    const uint64_t stream = mix64(seed ^ Traits<MODEL>::STREAM) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-#pragma unroll
-    for (int s = 0; s < K; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < K; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < K; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < K; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < K; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < K; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < K; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
 
 __device__ __forceinline__ bool finite6(const double (&A)[9])
 {

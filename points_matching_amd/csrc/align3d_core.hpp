@@ -10,8 +10,9 @@ namespace pm_align3d {
 
 using pm_pnp::dot3;
 using pm_pnp::triad;
-using pm_ransac::mix64;
 
+// S97: the 3-sample is S6's walk (sample_walk<3, STREAM, STREAM_H>) with both salts its own, n >= 3
+constexpr uint64_t STREAM = 0x3C6EF372FE94F82BULL, STREAM_H = 0xA54FF53A5F1D36F1ULL;
 constexpr int RIGID = PM_ALIGN3D_RIGID, SIMILARITY = PM_ALIGN3D_SIMILARITY;
 constexpr int WORDS = 13;             // R (9), t (3), s (1)
 constexpr int FLAG = 13;              // the valid flag (1.0 / 0.0) of a candidate slot
@@ -19,39 +20,6 @@ constexpr int M32 = 14;               // M32 = (float)(s R | t), 3 x 4 row-major
 // A candidate slot of the solve launch: 13 + 1 + 6 doubles = 160 B, a multiple of the 32-byte sector like pnp_core.hpp's
 // slot, so no slot straddles one more sector than it must; no pad is needed.
 constexpr int SLOT_DOUBLES = 20;
-
-// S97: 3 distinct indices in [0, n) as a pure function of (seed, h, n), n >= 3.  S37's walk on a stream of its own.
-__device__ __forceinline__ void sample3(uint64_t seed, uint64_t h, int n, int (&idx)[3])
-{
-    const uint64_t stream = mix64(seed ^ 0x3C6EF372FE94F82BULL) ^ mix64(h + 0xA54FF53A5F1D36F1ULL);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < 3; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 3; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
 
 // S99: M32 = (float)(s R | t), row r at P[4r .. 4r + 3]
 __device__ __forceinline__ void model32(const double* T, float* P)

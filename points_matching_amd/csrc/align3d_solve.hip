@@ -26,7 +26,7 @@ __global__ __launch_bounds__(AS_THREADS) void align3d_solve(pm_points_view v, in
         return;
     }
     int idx[3];
-    sample3(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
+    sample_walk<3, STREAM, STREAM_H>(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
     float a[3][3], b[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

@@ -11,8 +11,7 @@
 
 namespace pm_essential {
 
-using pm_ransac::mix64;
-
+constexpr uint64_t STREAM = 0xC2B2AE3D27D4EB4FULL;   // S32: the 5-sample is S6's walk (sample_walk<5, STREAM>), n >= 5
 constexpr int MAX_MODELS = 10;        // S33: candidates per sample (model ids 10h .. 10h + 9)
 constexpr int BISECT_STEPS = 64;      // S33 root bisection
 constexpr int SWEEPS_E = 6;           // S35 Jacobi sweeps on E
@@ -34,39 +33,6 @@ __device__ __forceinline__ float normalise1(float p, double c, double f)
 __device__ __forceinline__ float2 normalise(const Cam& k, float2 p)
 {
     return float2{normalise1(p.x, k.cx, k.fx), normalise1(p.y, k.cy, k.fy)};
-}
-
-// S32: 5 distinct indices in [0, n) as a pure function of (seed, h, n), n >= 5.  S6's walk on its own stream.
-__device__ __forceinline__ void sample5(uint64_t seed, uint64_t h, int n, int (&idx)[5])
-{
-    const uint64_t stream = mix64(seed ^ 0xC2B2AE3D27D4EB4FULL) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-#pragma unroll
-    for (int s = 0; s < 5; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < 5; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 5; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 5; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 5; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 5; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 5; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
 }
 
 // S33 polynomial products in (x, y, z): linear [x y z 1] x linear -> quadratic (10 monomials

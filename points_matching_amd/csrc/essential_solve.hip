@@ -47,7 +47,7 @@ __global__ __launch_bounds__(ES_THREADS) void essential_solve(pm_points_view v, 
         return;
     }
     int idx[5];
-    sample5(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
+    sample_walk<5, STREAM>(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
     double x1[5], y1[5], x2[5], y2[5];
 #pragma unroll
     for (int i = 0; i < 5; ++i) {

@@ -13,45 +13,14 @@ using pm_ransac::f32x2;
 using pm_ransac::hartley;
 using pm_ransac::householder_null9x8;
 using pm_ransac::householder_qr9x8;
-using pm_ransac::mix64;
 using pm_ransac::scale_sign;
+
+// SPEC S19: the 4-sample is S6's walk (sample_core.hpp, sample_walk<4, STREAM>) on a stream of its own, n >= 4
+constexpr uint64_t STREAM = 0x4A7C159E3779B97FULL;
 
 // S20: |cross| of a normalised triple at or below this is collinear (normalised points sit at mean distance sqrt(2)
 // from their centroid, so the bound is ~3.5e-5 of a typical triangle's doubled area)
 constexpr double COLLINEAR_EPS = 1e-4;
-
-// SPEC S19: 4 distinct indices in [0, n) as a pure function of (seed, h, n), n >= 4.  S6's walk on its own stream.
-__device__ __forceinline__ void sample4(uint64_t seed, uint64_t h, int n, int (&idx)[4])
-{
-    const uint64_t stream = mix64(seed ^ 0x4A7C159E3779B97FULL) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < 4; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 4; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
 
 // SPEC S20 step 2: doubled signed area of the normalised triple (a, b, c), unfused.
 __device__ __forceinline__ double cross3(const double (&x)[4], const double (&y)[4], int a, int b, int c)

@@ -24,40 +24,9 @@ constexpr int LM_MAX_N = 32768;          // residual keys of one model live in L
 constexpr double LM_INF = __builtin_inf();
 
 using pm_ransac::hartley;
-using pm_ransac::mix64;
+using pm_ransac::sample_walk;
 
-// SPEC S13: 7 distinct indices in [0, n) as a pure function of (seed, h, n).
-__device__ __forceinline__ void sample7(uint64_t seed, uint64_t h, int n, int (&idx)[7])
-{
-    const uint64_t stream = mix64(seed ^ 0x7F4A7C159E3779B9ULL) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-#pragma unroll
-    for (int s = 0; s < 7; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < 7; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool dup = false;
-#pragma unroll
-        for (int s = 0; s < 7; ++s) dup |= (s < cnt) && (idx[s] == c);
-        if (!dup) {
-#pragma unroll
-            for (int s = 0; s < 7; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 7; ++c) {
-        bool dup = false;
-#pragma unroll
-        for (int s = 0; s < 7; ++s) dup |= (s < cnt) && (idx[s] == c);
-        if (!dup) {
-#pragma unroll
-            for (int s = 0; s < 7; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
+constexpr uint64_t LM_STREAM = 0x7F4A7C159E3779B9ULL;     // SPEC S13: the 7-sample is S6's walk on a stream of its own
 
 __device__ __forceinline__ double det3(double r00, double r01, double r02, double r10, double r11, double r12,
                                        double r20, double r21, double r22)
@@ -215,7 +184,7 @@ __global__ __launch_bounds__(64) void lmeds_solve(const float* __restrict__ xy1,
     const int t = blockIdx.x * 64 + threadIdx.x;
     if (t >= nh) return;
     int idx[7];
-    sample7(seed, static_cast<uint64_t>(hyp_begin + t), n, idx);
+    sample_walk<7, LM_STREAM>(seed, static_cast<uint64_t>(hyp_begin + t), n, idx);
     double x1[7], y1[7], x2[7], y2[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) {

@@ -75,8 +75,8 @@ int sync_words_reserve(pm_ctx* ctx)
         return PM_E_UNSUPPORTED;
     }
     int* w = nullptr;
-    PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w), 256));
-    const hipError_t e = hipMemsetAsync(w, 0, 256, ctx->stream);
+    PM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w), SYNC_WORDS_BYTES));
+    const hipError_t e = hipMemsetAsync(w, 0, SYNC_WORDS_BYTES, ctx->stream);
     if (e != hipSuccess) {
         (void)hipFree(w);
         PM_HIP_CHECK(e);

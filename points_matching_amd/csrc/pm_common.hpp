@@ -127,7 +127,9 @@ int arena_reserve(pm_ctx* ctx, size_t bytes);
 void arena_reset(pm_ctx* ctx);                          // also notes whether the stream is capturing, for arena_take
 void* arena_take(pm_ctx* ctx, size_t bytes);            // 256-B aligned carve; nullptr if over cap
 // The arrival words of the one-launch RANSAC kernels (ctx->sync_words), allocated and zeroed on a context's first such call;
-// on a capturing stream that first call is refused (PM_E_UNSUPPORTED) before anything is allocated or enqueued.
+// on a capturing stream that first call is refused (PM_E_UNSUPPORTED) before anything is allocated or enqueued.  Who owns
+// which word: ransac_internal.hpp (SyncWord), checked there against the size here.
+constexpr size_t SYNC_WORDS_BYTES = 256;
 int sync_words_reserve(pm_ctx* ctx);
 int pinned_reserve(pm_ctx* ctx, size_t bytes);
 // The private device block of a host-pointer entry point around its _dev form (the _dev form resets the arena, so the

@@ -10,46 +10,13 @@ namespace pm_pnp {
 
 using pm_essential::Cam;
 using pm_essential::cross3;
-using pm_ransac::mix64;
 
+constexpr uint64_t STREAM = 0x165667B19E3779F9ULL;   // S37: the 3-sample is S6's walk (sample_walk<3, STREAM>), n >= 3
 constexpr int MAX_CAND = 4;           // S38: candidates per sample (model ids 4h .. 4h + 3)
 constexpr int WORDS = 12;             // R (9), t (3)
-// A candidate slot of the solve launch: R, t (12 doubles), the valid flag (1.0 / 0.0), P32 = (float)(K [R|t]) as 12
-// floats in doubles 13..18, one pad double.
-constexpr int SLOT_DOUBLES = 20;
-
-// S37: 3 distinct indices in [0, n) as a pure function of (seed, h, n), n >= 3.  S6's walk on its own stream.
-__device__ __forceinline__ void sample3(uint64_t seed, uint64_t h, int n, int (&idx)[3])
-{
-    const uint64_t stream = mix64(seed ^ 0x165667B19E3779F9ULL) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-#pragma unroll
-    for (int s = 0; s < 3; ++s) idx[s] = -1;
-    int cnt = 0;
-    for (uint64_t d = 0; d < 64 && cnt < 3; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 3; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 3; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
+constexpr int FLAG = 12;              // the valid flag (1.0 / 0.0) of a candidate slot
+constexpr int M32 = 13;               // P32 = (float)(K [R|t]), 3 x 4 row-major, as 12 floats in doubles 13..18
+constexpr int SLOT_DOUBLES = 20;      // a candidate slot of the solve launch: the above and one pad double
 
 __device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3])
 {
@@ -156,10 +123,10 @@ __device__ __forceinline__ int p3p(const Cam& k, const float (&X)[3][3], const f
         double* o = out + SLOT_DOUBLES * j;
 #pragma unroll
         for (int i = 0; i < WORDS; ++i) o[i] = Rt[i];
-        o[WORDS] = 1.0;
+        o[FLAG] = 1.0;
         float P[WORDS];
         proj32(k, Rt, P);
-        __builtin_memcpy(o + WORDS + 1, P, sizeof P);         // 12 floats in doubles 13..18, no type punning
+        __builtin_memcpy(o + M32, P, sizeof P);               // 12 floats in doubles 13..18, no type punning
         ++nv;
     }
     return nv;

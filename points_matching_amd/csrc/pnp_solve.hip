@@ -27,7 +27,7 @@ __global__ __launch_bounds__(PS_THREADS) void pnp_solve(pm_points_view v, Cam k,
         return;
     }
     int idx[3];
-    sample3(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
+    sample_walk<3, STREAM>(seed, static_cast<uint64_t>(hyp_begin + g), n, idx);
     float X[3][3], u[3], w[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

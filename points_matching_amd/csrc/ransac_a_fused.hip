@@ -17,8 +17,6 @@ namespace {
 
 using namespace pm_affine;
 
-constexpr int RA_SYNC_WORD = 12;      // arrival ticket in ctx->sync_words (RANSAC-F uses words 0 and 2, RANSAC-H word 8)
-
 // The affine policies of the LDS one-launch kernel (ransac_fused_kernels.hpp, ransac_fused_lds).  Models are carried
 // as 9 doubles [a0 .. a5, 0, 0, 1]; the kernel publishes the first OUT_WORDS = 6.
 template <int MODEL>
@@ -27,6 +25,8 @@ struct AModel {
     static constexpr bool SHARD_OUT = false;               // key, A, mask and count only
     static constexpr int OUT_WORDS = 6;
     static constexpr bool CANDIDATES = false;
+    static constexpr int SYNC_WORD = SYNC_A;
+    static constexpr const char* TIMER = "ransac_a_fused";
 
     // SPEC S26, S27: sample and solve hypothesis h.
     template <typename DIAG>
@@ -34,7 +34,7 @@ struct AModel {
                                                  uint64_t h, double (&A)[9])
     {
         int idx[MIN_PTS];
-        sample<MODEL>(seed, h, n, idx);
+        sample_walk<MIN_PTS, Traits<MODEL>::STREAM>(seed, h, n, idx);
         double x1[MIN_PTS], y1[MIN_PTS], x2[MIN_PTS], y2[MIN_PTS];
 #pragma unroll
         for (int i = 0; i < MIN_PTS; ++i) {
@@ -74,8 +74,8 @@ int ransac_a_enqueue(pm_ctx* ctx, int model, const pm_points_view& v, const pm_r
                      double* d_A, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
     if (model == PM_AFFINE_FULL)
-        return fused_lds_enqueue<AModel<FULL>>(ctx, v, p, RA_SYNC_WORD, "ransac_a_fused", d_key, d_A, d_mask, mask_len, d_ninl);
-    return fused_lds_enqueue<AModel<PARTIAL>>(ctx, v, p, RA_SYNC_WORD, "ransac_a_fused", d_key, d_A, d_mask, mask_len, d_ninl);
+        return fused_lds_enqueue<AModel<FULL>>(ctx, v, p, d_key, d_A, d_mask, mask_len, d_ninl);
+    return fused_lds_enqueue<AModel<PARTIAL>>(ctx, v, p, d_key, d_A, d_mask, mask_len, d_ninl);
 }
 
 }  // namespace pm_ransac

@@ -18,10 +18,6 @@
 namespace pm_ransac {
 namespace {
 
-using pm_align3d::SLOT_DOUBLES;
-
-constexpr int RX_SYNC_WORD = 24;      // arrival ticket in ctx->sync_words (F: 0 and 2, H: 8, A: 12, E: 16, P: 20)
-
 struct XyzGeom {
     static constexpr bool OWN = true;
     static constexpr int PLANES = 6, MW = 16, FLAG = 12, WORDS = 13, MAX_SLOTS = 40;
@@ -42,46 +38,13 @@ __device__ __forceinline__ bool inlier1(const float (&P)[16], float x, float y, 
     return d2 <= thr2 && d2 < __builtin_inff();
 }
 
-struct XModel {
+// Regs, regs(), load() and mask_model() are Cand3x4's, on align3d_solve's slots: R, t, s for the winner, M32 for the test
+struct XModel : Cand3x4<pm_align3d::SLOT_DOUBLES, pm_align3d::WORDS, pm_align3d::FLAG, pm_align3d::M32> {
     using Geom = XyzGeom;
     static constexpr int MIN_PTS = 3;
-    static constexpr bool SHARD_OUT = false;               // key, model, mask and count only
     static constexpr int OUT_WORDS = 13;
-    static constexpr bool CANDIDATES = true;
-
-    // M32 in SGPR pairs: (P0, P1) (P2, P3) (P4, P5) (P6, P7) (P8, P9) (P10, P11)
-    struct Regs {
-        unsigned long long q01, q23, q45, q67, q89, qab;
-    };
-    static __device__ __forceinline__ Regs regs(const float* m)
-    {
-        return Regs{spair(m[0], m[1]), spair(m[2], m[3]), spair(m[4], m[5]), spair(m[6], m[7]), spair(m[8], m[9]),
-                    spair(m[10], m[11])};
-    }
-
-    // candidate k of the launch (id hyp_begin + k): R, t, s (13 doubles), M32 into the LDS model, the valid flag
-    static __device__ __forceinline__ bool load(const double* __restrict__ cand, int k, double (&F)[13], float* mdl)
-    {
-        const double* c = cand + SLOT_DOUBLES * static_cast<size_t>(k);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) F[i] = c[i];
-        float P[12];
-        __builtin_memcpy(P, c + pm_align3d::M32, sizeof P);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) mdl[i] = P[i];
-        return c[pm_align3d::FLAG] != 0.0;
-    }
-
-    // the winner's M32 for the mask phase (zero without a winner: `ok` then fails every test)
-    static __device__ __forceinline__ void mask_model(const double* __restrict__ cand, bool ok, unsigned long long kwin,
-                                                      int64_t hyp_begin, float (&fw)[16])
-    {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) fw[i] = 0.0f;
-        if (!ok) return;
-        const int64_t k = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(kwin)) - hyp_begin;
-        __builtin_memcpy(fw, cand + SLOT_DOUBLES * static_cast<size_t>(k) + pm_align3d::M32, 12 * sizeof(float));
-    }
+    static constexpr int SYNC_WORD = SYNC_X;
+    static constexpr const char* TIMER = "ransac_align3d_fused";
 
     // rows i0, i0 + 1 of the view (xy1, xy2: 3 floats each; NaN past n) as the 6 packed planes of one lane
     static __device__ __forceinline__ void load_pair(const pm_points_view& v, int n, int i0, f32x2* d)
@@ -127,7 +90,7 @@ struct XModel {
 int ransac_align3d_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* q, const double* d_cand,
                            unsigned long long* d_key, double* d_T, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
-    return fused_lds_enqueue<XModel>(ctx, v, q, RX_SYNC_WORD, "ransac_align3d_fused", d_key, d_T, d_mask, mask_len, d_ninl, d_cand);
+    return fused_lds_enqueue<XModel>(ctx, v, q, d_key, d_T, d_mask, mask_len, d_ninl, d_cand);
 }
 
 }  // namespace pm_ransac

@@ -1,12 +1,13 @@
 // ransac_core.hpp — device functions shared by the RANSAC-F translation units (ransac.hip: hypothesis-per-lane
 // kernels for large correspondence sets and the sharded legacy entry points; ransac_fused.hip: the one-launch
 // solve + score + pick + mask kernel); the fp64 normalisation, QR and scale/sign steps also serve RANSAC-H
-// (homography_core.hpp) and LMedS (lmeds.hip).  Every operation is written in the order docs/SPEC.md fixes (S6 sampler,
-// S7 normalised 8-point solve, S8 inlier test); both TUs are built with -ffp-contract=off, so the only fused
+// (homography_core.hpp) and LMedS (lmeds.hip).  Every operation is written in the order docs/SPEC.md fixes (S6 sampler, in
+// sample_core.hpp; S7 normalised 8-point solve, S8 inlier test); both TUs are built with -ffp-contract=off, so the only fused
 // multiply-adds are the explicit fma()/fmaf() calls and the CPU restatement reproduces the same bits.
 // Replaces the arithmetic behind cv::findFundamentalMat (main.cpp:95-98) with the estimator BASELINE.json names.
 #pragma once
 #include "pm_common.hpp"
+#include "sample_core.hpp"
 
 namespace pm_ransac {
 
@@ -19,74 +20,6 @@ struct NoDiag {
 };
 
 constexpr int MODEL_STRIDE = 12;   // 9 x fp32 F, valid flag, 2 pad
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// SPEC S6: 8 distinct indices in [0, n) as a pure function of (seed, h, n): draws d = 0, 1, ... give candidates
-// c_d = floor(n * hi32(mix64(stream + (d+1)*phi)) / 2^32); a candidate equal to an earlier one is skipped; after 64
-// draws the smallest unused integers complete the sample.  Same results as the sequential loop of the oracle, computed
-// so that the 64-bit multiplies of the first eight draws are independent (they dominated: 5.3k of the solver's 24k
-// cycles with the draw-by-draw loop) and the common case — eight distinct candidates — touches no select chains.
-__device__ __forceinline__ void sample8(uint64_t seed, uint64_t h, int n, int (&idx)[8])
-{
-    const uint64_t stream = mix64(seed ^ 0x9E3779B97F4A7C15ULL) ^ mix64(h + 0xD1B54A32D192ED03ULL);
-    int cand[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        const uint64_t r = mix64(stream + static_cast<uint64_t>(d + 1) * 0x9E3779B97F4A7C15ULL);
-        cand[d] = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-    }
-    unsigned dup = 0u;                         // bit d: candidate d repeats an earlier one (so it is skipped)
-#pragma unroll
-    for (int d = 1; d < 8; ++d)
-#pragma unroll
-        for (int e = 0; e < d; ++e) dup |= (cand[e] == cand[d] ? 1u : 0u) << d;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) idx[s] = cand[s];
-    if (dup == 0u) return;
-    // rare: keep the first occurrences in draw order, then go on drawing
-#pragma unroll
-    for (int s = 0; s < 8; ++s) idx[s] = -1;
-    int cnt = 0;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        if (!((dup >> d) & 1u)) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (s == cnt) idx[s] = cand[d];
-            ++cnt;
-        }
-    }
-    for (uint64_t d = 8; d < 64 && cnt < 8; ++d) {
-        const uint64_t r = mix64(stream + (d + 1) * 0x9E3779B97F4A7C15ULL);
-        const int c = static_cast<int>(((r >> 32) * static_cast<uint64_t>(static_cast<uint32_t>(n))) >> 32);
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-    for (int c = 0; cnt < 8; ++c) {
-        bool rep = false;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) rep |= (s < cnt) && (idx[s] == c);
-        if (!rep) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s)
-                if (s == cnt) idx[s] = c;
-            ++cnt;
-        }
-    }
-}
 
 // SPEC S7 step 1 (and S14 step 1, S20 step 1): Hartley normalisation of N points, centroid to the origin, mean distance
 // sqrt(2).  The means divide by N (for N = 4 and 8 the same bits as a multiply by 1/N).

@@ -13,13 +13,13 @@
 namespace pm_ransac {
 namespace {
 
-constexpr int RE_SYNC_WORD = 16;      // arrival ticket in ctx->sync_words (F: 0 and 2, H: 8, A: 12)
-
 struct EModel {
     static constexpr int MIN_PTS = 5;
     static constexpr bool SHARD_OUT = false;               // key, E, mask and count only
     static constexpr int OUT_WORDS = 9;
     static constexpr bool CANDIDATES = true;
+    static constexpr int SYNC_WORD = SYNC_E;
+    static constexpr const char* TIMER = "ransac_e_fused";
 
     // candidate k of the launch (id hyp_begin + k): 9 doubles and the valid flag
     static __device__ __forceinline__ bool load(const double* __restrict__ cand, int k, double (&E)[9])
@@ -46,7 +46,7 @@ struct EModel {
 int ransac_e_enqueue(pm_ctx* ctx, const pm_points_view& vn, const pm_ransac_params* q, const double* d_cand,
                      unsigned long long* d_key, double* d_E, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
-    return fused_lds_enqueue<EModel>(ctx, vn, q, RE_SYNC_WORD, "ransac_e_fused", d_key, d_E, d_mask, mask_len, d_ninl, d_cand);
+    return fused_lds_enqueue<EModel>(ctx, vn, q, d_key, d_E, d_mask, mask_len, d_ninl, d_cand);
 }
 
 }  // namespace pm_ransac

@@ -543,6 +543,49 @@ struct GeomOf<M, std::void_t<typename M::Geom>> {
     using type = typename M::Geom;
 };
 
+// What the candidate-loaded policies with a 3 x 4 fp32 scoring matrix share (PModel: P32, XModel: M32).  A slot of their
+// solve launch is SLOT doubles: the fp64 model in the first WORDS, the valid flag (1.0 / 0.0) at FLAG_AT, the matrix as
+// 12 floats from M32_AT.  The policy adds Geom, MIN_PTS, OUT_WORDS, load_pair and the inlier tests.
+template <int SLOT, int WORDS, int FLAG_AT, int M32_AT>
+struct Cand3x4 {
+    static constexpr bool SHARD_OUT = false;               // key, model, mask and count only
+    static constexpr bool CANDIDATES = true;
+
+    // the matrix in SGPR pairs: (P0, P1) (P2, P3) (P4, P5) (P6, P7) (P8, P9) (P10, P11)
+    struct Regs {
+        unsigned long long q01, q23, q45, q67, q89, qab;
+    };
+    static __device__ __forceinline__ Regs regs(const float* m)
+    {
+        return Regs{spair(m[0], m[1]), spair(m[2], m[3]), spair(m[4], m[5]), spair(m[6], m[7]), spair(m[8], m[9]),
+                    spair(m[10], m[11])};
+    }
+
+    // candidate k of the launch (id hyp_begin + k): the fp64 model, the matrix into the LDS model, the valid flag
+    static __device__ __forceinline__ bool load(const double* __restrict__ cand, int k, double (&F)[WORDS], float* mdl)
+    {
+        const double* c = cand + SLOT * static_cast<size_t>(k);
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) F[i] = c[i];
+        float P[12];
+        __builtin_memcpy(P, c + M32_AT, sizeof P);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) mdl[i] = P[i];
+        return c[FLAG_AT] != 0.0;
+    }
+
+    // the winner's matrix for the mask phase (zero without a winner: every test fails)
+    static __device__ __forceinline__ void mask_model(const double* __restrict__ cand, bool ok, unsigned long long kwin,
+                                                      int64_t hyp_begin, float (&fw)[16])
+    {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) fw[i] = 0.0f;
+        if (!ok) return;
+        const int64_t k = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(kwin)) - hyp_begin;
+        __builtin_memcpy(fw, cand + SLOT * static_cast<size_t>(k) + M32_AT, 12 * sizeof(float));
+    }
+};
+
 // NH hypotheses of one wave (ids s0, s0 + RL_WAVES, ...) over the slots of the LDS tile in ONE pass: each operand read serves NH
 // models (the LDS port, 4 x 512 B per wave and slot, would otherwise be ~3/4 as busy as the VALU and the two contend).
 template <typename MODEL, int NH>
@@ -921,13 +964,12 @@ int fused_lds_launch(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_param
     return PM_OK;
 }
 
-// Enqueue the LDS form for a model policy with a local result (key, model, mask[mask_len], count), timed as `timer`,
-// arrival ticket sync_words[sync_word]: the launch of RANSAC-H and RANSAC-A.  The arena must already be reserved for
-// fused_scratch_bytes(); the workgroup slots are carved here.
+// Enqueue the LDS form for a model policy with a local result (key, model, mask[mask_len], count), timed as
+// MODEL::TIMER, arrival ticket sync_words[MODEL::SYNC_WORD]: the launch of every family but F.  The arena must already be
+// reserved for fused_scratch_bytes(); the workgroup slots are carved here.
 template <typename MODEL>
-int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, int sync_word, const char* timer,
-                      unsigned long long* d_key, double* d_model, uint8_t* d_mask, int mask_len, int* d_ninl,
-                      const double* d_cand = nullptr)
+int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
+                      double* d_model, uint8_t* d_mask, int mask_len, int* d_ninl, const double* d_cand = nullptr)
 {
     const long long nh = p->hyp_end - p->hyp_begin;
     const int hb = fused_hb(ctx, nh);
@@ -940,8 +982,8 @@ int fused_lds_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_para
     RfOut out{};
     out.key = d_key; out.F = d_model; out.mask = d_mask; out.mask_len = mask_len; out.n_inliers = d_ninl;
     out.cand = d_cand;
-    pm::ScopedKernelTime t(ctx, timer);
-    return fused_lds_launch<MODEL, NoDiag>(ctx, v, p, nwg, hb, slots, sync + sync_word, out);
+    pm::ScopedKernelTime t(ctx, MODEL::TIMER);
+    return fused_lds_launch<MODEL, NoDiag>(ctx, v, p, nwg, hb, slots, sync + MODEL::SYNC_WORD, out);
 }
 
 // Enqueue the one-launch run.  The arena must already be reserved for fused_scratch_bytes(); it is carved here.
@@ -974,13 +1016,13 @@ int fused_launch_t(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params*
     // PM_OPT_RANSAC_FORM: 1 = correspondences in registers, two teams (round 2), 2 = correspondences in LDS, one wave per
     // hypothesis (round 3, the default)
     if (ctx->opts[PM_OPT_RANSAC_FORM] != 1) {
-        if (p->error_kind == PM_ERR_SAMPSON) return fused_lds_launch<FModel<PM_ERR_SAMPSON>, DIAG>(ctx, v, p, nwg, hb, slots, sync, out);
-        return fused_lds_launch<FModel<PM_ERR_SYM_EPIPOLAR>, DIAG>(ctx, v, p, nwg, hb, slots, sync, out);
+        if (p->error_kind == PM_ERR_SAMPSON) return fused_lds_launch<FModel<PM_ERR_SAMPSON>, DIAG>(ctx, v, p, nwg, hb, slots, sync + SYNC_F, out);
+        return fused_lds_launch<FModel<PM_ERR_SYM_EPIPOLAR>, DIAG>(ctx, v, p, nwg, hb, slots, sync + SYNC_F, out);
     }
     // 2*RF_PPT2 points per thread: a 2560-point tile (config C3 fits one); small capacities take the 2-slot build
 #define PM_RF(KIND_, PPT2_)                                                                                              \
     hipLaunchKernelGGL((ransac_fused<KIND_, PPT2_, DIAG>), dim3(nwg), dim3(RF_WG), 0, ctx->stream, v, p->seed, p->hyp_begin, \
-                       static_cast<int>(nh), hb, thr2, slots, sync, out)
+                       static_cast<int>(nh), hb, thr2, slots, sync + SYNC_F, out)
     const int depth = cap_total <= 2 * RF_PTS_PER_SLOT ? 2 : (cap_total <= RF_PPT2 * RF_PTS_PER_SLOT ? RF_PPT2 : RF_PPT2_BIG);
 #define PM_RF_K(KIND_)                                                                   \
     do {                                                                                 \

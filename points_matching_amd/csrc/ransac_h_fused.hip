@@ -18,8 +18,6 @@ namespace {
 
 using namespace pm_homog;
 
-constexpr int RH_SYNC_WORD = 8;       // arrival ticket in ctx->sync_words (RANSAC-F uses words 0 and 2)
-
 // The homography policy of the LDS one-launch kernel (ransac_fused_kernels.hpp, ransac_fused_lds; FModel is the
 // fundamental-matrix one).
 struct HModel {
@@ -27,6 +25,8 @@ struct HModel {
     static constexpr bool SHARD_OUT = false;               // key, H, mask and count only
     static constexpr int OUT_WORDS = 9;
     static constexpr bool CANDIDATES = false;
+    static constexpr int SYNC_WORD = SYNC_H;
+    static constexpr const char* TIMER = "ransac_h_fused";
 
     // SPEC S19, S20: sample and solve hypothesis h.
     template <typename DIAG>
@@ -34,7 +34,7 @@ struct HModel {
                                                  uint64_t h, double (&H)[9])
     {
         int idx[4];
-        sample4(seed, h, n, idx);
+        sample_walk<4, STREAM>(seed, h, n, idx);
         double x1[4], y1[4], x2[4], y2[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -74,7 +74,7 @@ struct HModel {
 int ransac_h_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* p, unsigned long long* d_key,
                      double* d_H, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
-    return fused_lds_enqueue<HModel>(ctx, v, p, RH_SYNC_WORD, "ransac_h_fused", d_key, d_H, d_mask, mask_len, d_ninl);
+    return fused_lds_enqueue<HModel>(ctx, v, p, d_key, d_H, d_mask, mask_len, d_ninl);
 }
 
 }  // namespace pm_ransac

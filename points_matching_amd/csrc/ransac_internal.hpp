@@ -1,13 +1,39 @@
 // ransac_internal.hpp — host functions shared across translation units: the entry points of ransac_fused.hip used by
 // the C-ABI functions in ransac.hip (host-pointer and device-resident single-shard runs) and by the multi-GPU driver
-// (mgpu.cpp), the view check of every device-resident entry point, and the one enqueue of each kernel file that
-// estimators.cpp drives for its four families: homography (ransac_h_fused.hip, homography_refine.hip), affine
+// (mgpu.cpp), the view check of every device-resident entry point, the table of arrival words, and the one enqueue of
+// each kernel file that estimators.cpp drives: homography (ransac_h_fused.hip, homography_refine.hip), affine
 // (ransac_a_fused.hip, affine_refine.hip), calibrated relative pose (essential_solve.hip, ransac_e_fused.hip,
-// recover_pose.hip) and absolute pose (pnp_solve.hip, ransac_p_fused.hip, pnp_refine.hip).
+// recover_pose.hip), the two-view refinements (fundamental_refine.hip, pose_refine.hip), absolute pose (pnp_solve.hip,
+// ransac_p_fused.hip, pnp_refine.hip) and 3-D alignment (align3d_solve.hip, ransac_align3d_fused.hip, align3d_refine.hip).
 #pragma once
 #include "ransac_core.hpp"
 
 namespace pm_ransac {
+
+// The arrival words in ctx->sync_words (pm_common.hpp), one entry per launch that draws tickets.  An entry owns the word
+// it names and the next one (the finish kernel counts inliers there); every launch returns its words to zero.  Families
+// may follow one another on one context and stream, so no two entries may meet.
+enum SyncWord : int {
+    SYNC_F = 0,                 // ransac_fused, ransac_fused_lds<FModel>
+    SYNC_F_FINISH = 2,          // ransac_finish (ransac_shard.hip)
+    SYNC_H = 8,
+    SYNC_A = 12,
+    SYNC_E = 16,
+    SYNC_P = 20,
+    SYNC_X = 24,                // 3-D alignment
+};
+constexpr bool sync_words_ok()
+{
+    constexpr int w[] = {SYNC_F, SYNC_F_FINISH, SYNC_H, SYNC_A, SYNC_E, SYNC_P, SYNC_X};
+    constexpr int n = sizeof w / sizeof w[0], words = static_cast<int>(pm::SYNC_WORDS_BYTES / sizeof(int));
+    for (int i = 0; i < n; ++i) {
+        if (w[i] < 0 || w[i] + 2 > words) return false;
+        for (int j = 0; j < i; ++j)
+            if (w[i] - w[j] < 2 && w[j] - w[i] < 2) return false;
+    }
+    return true;
+}
+static_assert(sync_words_ok(), "two arrival-word entries overlap, or one lies outside ctx->sync_words");
 
 constexpr int RF_HB_MAX = 128;          // hypothesis ids per workgroup, at most
 int fused_hb(const pm_ctx* ctx, long long nh);

@@ -16,10 +16,6 @@
 namespace pm_ransac {
 namespace {
 
-using pm_pnp::SLOT_DOUBLES;
-
-constexpr int RP_SYNC_WORD = 20;      // arrival ticket in ctx->sync_words (F: 0 and 2, H: 8, A: 12, E: 16)
-
 struct PnpGeom {
     static constexpr bool OWN = true;
     static constexpr int PLANES = 5, MW = 16, FLAG = 12, WORDS = 12, MAX_SLOTS = 48;
@@ -35,46 +31,13 @@ __device__ __forceinline__ bool inlier1(const float (&P)[16], float x, float y, 
     return lhs <= rhs && w > 0.0f && rhs > 0.0f && rhs < __builtin_inff();
 }
 
-struct PModel {
+// Regs, regs(), load() and mask_model() are Cand3x4's, on pnp_solve's slots: R, t for the winner, P32 for the test
+struct PModel : Cand3x4<pm_pnp::SLOT_DOUBLES, pm_pnp::WORDS, pm_pnp::FLAG, pm_pnp::M32> {
     using Geom = PnpGeom;
     static constexpr int MIN_PTS = 4;
-    static constexpr bool SHARD_OUT = false;               // key, R|t, mask and count only
     static constexpr int OUT_WORDS = 12;
-    static constexpr bool CANDIDATES = true;
-
-    // P32 in SGPR pairs: (P0, P1) (P2, P3) (P4, P5) (P6, P7) (P8, P9) (P10, P11)
-    struct Regs {
-        unsigned long long q01, q23, q45, q67, q89, qab;
-    };
-    static __device__ __forceinline__ Regs regs(const float* m)
-    {
-        return Regs{spair(m[0], m[1]), spair(m[2], m[3]), spair(m[4], m[5]), spair(m[6], m[7]), spair(m[8], m[9]),
-                    spair(m[10], m[11])};
-    }
-
-    // candidate k of the launch (id hyp_begin + k): R, t (12 doubles), P32 into the LDS model, the valid flag
-    static __device__ __forceinline__ bool load(const double* __restrict__ cand, int k, double (&F)[12], float* mdl)
-    {
-        const double* c = cand + SLOT_DOUBLES * static_cast<size_t>(k);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) F[i] = c[i];
-        float P[12];
-        __builtin_memcpy(P, c + 13, sizeof P);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) mdl[i] = P[i];
-        return c[12] != 0.0;
-    }
-
-    // the winner's P32 for the mask phase (zero without a winner: every test fails)
-    static __device__ __forceinline__ void mask_model(const double* __restrict__ cand, bool ok, unsigned long long kwin,
-                                                      int64_t hyp_begin, float (&fw)[16])
-    {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) fw[i] = 0.0f;
-        if (!ok) return;
-        const int64_t k = static_cast<int64_t>(0xFFFFFFFFu - static_cast<uint32_t>(kwin)) - hyp_begin;
-        __builtin_memcpy(fw, cand + SLOT_DOUBLES * static_cast<size_t>(k) + 13, 12 * sizeof(float));
-    }
+    static constexpr int SYNC_WORD = SYNC_P;
+    static constexpr const char* TIMER = "ransac_p_fused";
 
     // points i0, i0 + 1 of the view (xy1: X Y Z, xy2: u v; NaN past n) as the 5 packed planes of one lane
     static __device__ __forceinline__ void load_pair(const pm_points_view& v, int n, int i0, f32x2* d)
@@ -122,7 +85,7 @@ struct PModel {
 int ransac_p_enqueue(pm_ctx* ctx, const pm_points_view& v, const pm_ransac_params* q, const double* d_cand,
                      unsigned long long* d_key, double* d_Rt, uint8_t* d_mask, int mask_len, int* d_ninl)
 {
-    return fused_lds_enqueue<PModel>(ctx, v, q, RP_SYNC_WORD, "ransac_p_fused", d_key, d_Rt, d_mask, mask_len, d_ninl, d_cand);
+    return fused_lds_enqueue<PModel>(ctx, v, q, d_key, d_Rt, d_mask, mask_len, d_ninl, d_cand);
 }
 
 }  // namespace pm_ransac

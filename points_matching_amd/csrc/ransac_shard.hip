@@ -137,10 +137,10 @@ extern "C" int pm_ransac_finish_parts_dev(pm_ctx* ctx, const pm_points_view* vie
     unsigned long long* key = reinterpret_cast<unsigned long long*>(d_key);
     if (p->error_kind == PM_ERR_SAMPSON)
         hipLaunchKernelGGL(ransac_finish<PM_ERR_SAMPSON>, dim3(blocks), dim3(RF_THREADS), 0, ctx->stream, *view, d_records,
-                           n_records, thr2, key, d_F, d_mask, mask_len, d_n_inliers, d_n_total, sync + 2);
+                           n_records, thr2, key, d_F, d_mask, mask_len, d_n_inliers, d_n_total, sync + SYNC_F_FINISH);
     else
         hipLaunchKernelGGL(ransac_finish<PM_ERR_SYM_EPIPOLAR>, dim3(blocks), dim3(RF_THREADS), 0, ctx->stream, *view, d_records,
-                           n_records, thr2, key, d_F, d_mask, mask_len, d_n_inliers, d_n_total, sync + 2);
+                           n_records, thr2, key, d_F, d_mask, mask_len, d_n_inliers, d_n_total, sync + SYNC_F_FINISH);
     PM_HIP_CHECK(hipGetLastError());
     return PM_OK;
 }
