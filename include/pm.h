@@ -230,7 +230,7 @@ int pm_bf_knn_l2_f32_dev(pm_ctx* ctx, const float* d_q, int nq, const float* d_t
 /* The same matcher on u8 DESCRIPTOR ROWS (nq x dim / nt x dim bytes, 4-byte aligned device pointers in the _dev forms):
  * what a SIFT extractor holds before it widens to float, a quarter of the bytes on the host link (BASELINE config 5).
  * Output = pm_bf_knn_l2_f32 on the same values converted to float, bit for bit (distances are the canonical f32 ones).
- * dim % 4 == 0, dim <= 128, k <= 2: the u8 route (i8 matrix cores on x - 128, integer refinement); anything else is
+ * dim % 4 == 0, dim <= 128, k <= 4: the u8 route (i8 matrix cores on x - 128, integer refinement); anything else is
  * widened on the device and takes the f32 matcher.  pm_bf_knn_l2_u8_ratio_dev: + ratio test + compaction + gather, as
  * pm_bf_knn_l2_ratio_dev (the record buffer d_knn is required). */
 int pm_bf_knn_l2_u8(pm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int dim, int k, pm_match* out);
